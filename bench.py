@@ -2,6 +2,8 @@
 """Headline benchmark: SpectralMixingLayer fwd+bwd throughput on synthetic (B, N, D) fp32.
 
     python bench.py --gpus 1 --steps 50 --warmup 10            # BASELINE config C2 (the driver's line)
+    python bench.py --full                                     # ... plus roofline, box, C3/C5/F2, CPU baseline
+    python bench.py --dump-outputs DIR                         # ... and what the last timed step computed
     python bench.py --config c3 | c5                           # the other measured single-GPU configs
     python bench.py --gpus N --steps K --warmup W              # N > 1 without a launcher: bench.py starts the
                                                                # N rank processes itself (launch_ranks)
@@ -18,8 +20,13 @@ Workloads (BASELINE.json configs):
 At N > 1 GPUs the workload is per rank (weak scaling, batch sharded) and the filter/bias gradients are
 sum-all-reduced over RCCL inside backward; the schedule of that collective ("overlap" or "fused",
 tensor-cuda-fft-_amd/distributed.py) is picked by timing both before the timed region.
-Rank 0 prints one JSON line; at N = 1 with the default config it also carries the C3 and C5 measurements
-("other_configs": same binary, same box, same protocol; "f2" = fft_lm's causal convolution); "ranks_seen" is a SUM all-reduce of 1.0 per rank.
+Rank 0 prints one JSON line; "ranks_seen" is a SUM all-reduce of 1.0 per rank.  A plain run does only what the
+headline needs: set up, warm up, time the K steps, print the line.  --full adds what takes runs of its own: the two
+transform launches timed alone ("roofline"), the box's yardsticks ("box"), the CPU baseline and, at N = 1 with the
+default config, the C3 and C5 measurements ("other_configs": same binary, same box, same protocol; "f2" = fft_lm's
+causal convolution).
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed its caller (y and every gradient)
+as DIR/<name>.npy, float32; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -81,6 +88,29 @@ def cpu_baseline(B, N, D, F, iters):
             "kind": "port", "ms_per_step": dt * 1e3,
             "sample": f"{iters} fwd+bwd steps of the full (B={B},N={N},D={D}) batch, "
                       f"torch {torch.__version__} CPU, {os.cpu_count()} logical cpus"}
+
+
+DUMP_CAP = 1 << 22         # --dump-outputs: elements written per array (16 MiB of float32)
+
+
+def dump_outputs(outs, path):
+    """--dump-outputs: every tensor of `outs` as path/<name>.npy, float32 (a complex one as (..., 2) real / imag).
+    An array of more than DUMP_CAP elements is written as DUMP_CAP of them at fixed flat indices (numpy Generator
+    seeded 0, drawn without replacement, sorted): the same sample in every run of the same shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in outs.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_CAP, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.float().cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a if a.size < t.numel() else a.reshape(t.shape))
 
 
 def lib_sha256(path):
@@ -201,9 +231,16 @@ def parse_args(argv=None):
                     help="N > 1: schedule of the gradient all-reduce (auto = time both, keep the faster)")
     ap.add_argument("--opts", default="", help='plan knobs for A/B runs, "name=value;name=value" (smx_set_option); '
                                                'the line records them in config.opts')
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the transform launches alone (roofline), the box's yardsticks, the CPU baseline "
+                         "and, at N = 1 with the default config, C3 / C5 / F2 (\"other_configs\")")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (y, grad_x, parameter gradients) "
+                         f"as DIR/<name>.npy, float32; an array of more than {DUMP_CAP} elements as a fixed, "
+                         "seeded sample of that many")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N = 1, default config: do not also measure C3 and C5 (\"other_configs\" of the line)")
+                    help="--full, N = 1, default config: do not also measure C3 and C5 (\"other_configs\" of the line)")
     ap.add_argument("--no-supervise", action="store_true",
                     help="N > 1: run in this process instead of a supervised child (see supervise())")
     return ap.parse_args(argv)
@@ -351,9 +388,10 @@ def measure_f2(rt, steps):
     return out
 
 
-def measure(rt, args, cfg_name, cfg, steps, custom=False):
-    """Warm up, capture, ramp, time EXACTLY `steps` steps of one workload, then time its two transform launches
-    with HIP events.  Returns the pieces of the JSON line that belong to this workload."""
+def measure(rt, args, cfg_name, cfg, steps, custom=False, dump_dir=None):
+    """Warm up, capture, ramp, time EXACTLY `steps` steps of one workload (dump_dir: then write what the last of them
+    computed), and with --full time its two transform launches with HIP events.  Returns the pieces of the JSON line
+    that belong to this workload."""
     import tensor_cuda_fft_amd as pkg
     from tensor_cuda_fft_amd import _lib, functional
 
@@ -369,10 +407,13 @@ def measure(rt, args, cfg_name, cfg, steps, custom=False):
     x = torch.randn(B, N, D, device=dev, generator=gen).requires_grad_(True)
     g = torch.randn(B, N, D, device=dev, generator=gen)
     params = list(module.parameters())
+    param_names = ["grad_" + n.replace(".", "_") for n, _ in module.named_parameters()]
 
-    def step():
+    def step(keep=None):
         y = unit(x)
         y.backward(g)
+        if keep is not None:          # --dump-outputs: hold what this step hands its caller
+            keep.update(y=y, grad_x=x.grad, **{n: p.grad for n, p in zip(param_names, params)})
         x.grad = None
         for p in params:
             p.grad = None
@@ -385,6 +426,7 @@ def measure(rt, args, cfg_name, cfg, steps, custom=False):
         step()
     sync_all()
     steps_before_timing = n_warm
+    held = {}           # --dump-outputs: id(graph) -> the tensors its last captured step handed its caller
 
     def capture(n):
         nonlocal steps_before_timing
@@ -397,9 +439,11 @@ def measure(rt, args, cfg_name, cfg, steps, custom=False):
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         gr = torch.cuda.CUDAGraph()
+        keep = {} if dump_dir else None
         with torch.cuda.graph(gr):
-            for _ in range(n):
-                step()
+            for i in range(n):
+                step(keep if i == n - 1 else None)
+        held[id(gr)] = keep
         return gr
 
     def time_replays(gr, n):
@@ -413,6 +457,7 @@ def measure(rt, args, cfg_name, cfg, steps, custom=False):
 
     # K steps = n_full replays of a graph holding `spg` steps + one graph with the remainder
     plan_runs = []          # (callable, steps it runs)
+    last_held = None        # --dump-outputs: what the last step of the last of plan_runs hands its caller
     launch = args.mode
     sync_report = None
     if args.mode == "graph" and rt.use_dist and rt.backend != "nccl" \
@@ -440,8 +485,11 @@ def measure(rt, args, cfg_name, cfg, steps, custom=False):
                 g_full = graphs[best]
                 sync_report = {"chosen": best, "ms_per_step": {k: round(v, 4) for k, v in trial.items()}}
             plan_runs = [(g_full.replay, spg)] * n_full
+            last_held = held[id(g_full)]
             if rem:
-                plan_runs.append((capture(rem).replay, rem))
+                g_rem = capture(rem)
+                plan_runs.append((g_rem.replay, rem))
+                last_held = held[id(g_rem)]
             for _ in range(max(args.warmup // spg, 1)):
                 g_full.replay()
                 steps_before_timing += spg
@@ -463,6 +511,9 @@ def measure(rt, args, cfg_name, cfg, steps, custom=False):
             plan_runs = []
     if not plan_runs:
         plan_runs = [(step, 1)] * steps
+        if dump_dir:
+            last_held = {}
+            plan_runs[-1] = (lambda: step(last_held), 1)
         for _ in range(n_warm):
             step()
         steps_before_timing += n_warm
@@ -501,63 +552,82 @@ def measure(rt, args, cfg_name, cfg, steps, custom=False):
     value = world * B * N * D * steps / dt / 1e9
     per_call = [e0.elapsed_time(e1) / n for (e0, e1), (_, n) in zip(evs, plan_runs)]   # ms per step
 
-    # ---- the two transform launches, HIP events on the launch stream ---------------------------------
-    # One call of smx_forward / smx_backward (SPECTRUM | INVERSE) with a ready packed filter is exactly
-    # the streaming launch(es) of that direction: ONE kernel on the fused plan (c2, c5), the
-    # k_split_a / k_split_f / k_split_b group on the residue-split plan (c3).
+    if dump_dir and rank == 0:
+        dump_outputs(last_held, dump_dir)
     plan = _lib.plan(B, N, D, F)
-    xd = x.detach()
-    reps = max(steps, 20)
 
-    def timed(fn):
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize(dev)
-        for a, b in ev:
-            a.record()
-            fn()
-            b.record()
-        torch.cuda.synchronize(dev)
-        ts = [a.elapsed_time(b) for a, b in ev]
-        return sum(ts) / len(ts), min(ts)
+    def launch_roofline():
+        """--full: the two transform launches, HIP events on the launch stream.  One call of smx_forward /
+        smx_backward (SPECTRUM | INVERSE) with a ready packed filter is exactly the streaming launch(es) of that
+        direction: ONE kernel on the fused plan (c2, c5), the k_split_a / k_split_f / k_split_b group on the
+        residue-split plan (c3)."""
+        xd = x.detach()
+        reps = max(steps, 20)
 
-    with torch.no_grad():
-        pack = functional._new_pack(xd, w_re)
-        _, xk = functional.forward_raw(xd, w_re, w_im, bias, save_spectrum=True, pack=pack)
-        gx = torch.empty_like(g)
-        flat = torch.empty(2 * D * F + D, dtype=torch.float32, device=dev)
-        f_avg, f_min = timed(lambda: functional.forward_raw(xd, w_re, w_im, bias, save_spectrum=True,
-                                                            pack=pack, pack_ready=pack is not None))
-        b_avg, b_min = timed(lambda: functional.backward_raw(
-            g, xk, w_re, w_im, phases=functional.PHASE_SPECTRUM | functional.PHASE_INVERSE, grad_x=gx,
-            flat=flat, pack=pack))
-    alg = BYTES_PER_SAMPLE_DIR * B * N * D
-    nb = plan.bands
-    if plan.nsplit == 1:
-        names = {"fwd": f"smx::k_fused<{nb}, 0", "bwd": f"smx::k_fused<{nb}, 1"}
-        kind = "one fused launch per direction"
-    else:
-        names = {"fwd": f"smx::k_split_a<{nb}", "bwd": f"smx::k_split_b<{nb}"}
-        kind = (f"launch group per direction (k_split_a + k_split_f + k_split_b, "
-                f"{plan.nsplit} residue chunks)")
-    launches = {
-        "forward": {"kernel": names["fwd"], "avg_ms": round(f_avg, 4), "min_ms": round(f_min, 4),
-                    "achieved_GBps": round(alg / (f_avg * 1e-3) / 1e9, 1)},
-        "backward": {"kernel": names["bwd"], "avg_ms": round(b_avg, 4), "min_ms": round(b_min, 4),
-                     "achieved_GBps": round(alg / (b_avg * 1e-3) / 1e9, 1)},
-    }
-    dom = "backward" if b_avg >= f_avg else "forward"          # the LONGEST launch of the step
-    achieved = launches[dom]["achieved_GBps"]
+        def timed(fn):
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize(dev)
+            for a, b in ev:
+                a.record()
+                fn()
+                b.record()
+            torch.cuda.synchronize(dev)
+            ts = [a.elapsed_time(b) for a, b in ev]
+            return sum(ts) / len(ts), min(ts)
 
-    sha = lib_sha256(_lib.LIB_PATH)
-    traffic_all, traffic_src, traffic_why = (None, None, "custom shape") if custom else \
-        profile_traffic(cfg_name, sha, [names["fwd"], names["bwd"]])
-    traffic = None
-    if traffic_all:
-        traffic = traffic_all.get(names["bwd" if dom == "backward" else "fwd"])
-    prof_avg, prof_src = (None, "custom shape") if custom else \
-        profile_kernel_avg(cfg_name, sha, names["bwd" if dom == "backward" else "fwd"])
+        with torch.no_grad():
+            pack = functional._new_pack(xd, w_re)
+            _, xk = functional.forward_raw(xd, w_re, w_im, bias, save_spectrum=True, pack=pack)
+            gx = torch.empty_like(g)
+            flat = torch.empty(2 * D * F + D, dtype=torch.float32, device=dev)
+            f_avg, f_min = timed(lambda: functional.forward_raw(xd, w_re, w_im, bias, save_spectrum=True,
+                                                                pack=pack, pack_ready=pack is not None))
+            b_avg, b_min = timed(lambda: functional.backward_raw(
+                g, xk, w_re, w_im, phases=functional.PHASE_SPECTRUM | functional.PHASE_INVERSE, grad_x=gx,
+                flat=flat, pack=pack))
+        alg = BYTES_PER_SAMPLE_DIR * B * N * D
+        nb = plan.bands
+        if plan.nsplit == 1:
+            names = {"fwd": f"smx::k_fused<{nb}, 0", "bwd": f"smx::k_fused<{nb}, 1"}
+            kind = "one fused launch per direction"
+        else:
+            names = {"fwd": f"smx::k_split_a<{nb}", "bwd": f"smx::k_split_b<{nb}"}
+            kind = (f"launch group per direction (k_split_a + k_split_f + k_split_b, "
+                    f"{plan.nsplit} residue chunks)")
+        launches = {
+            "forward": {"kernel": names["fwd"], "avg_ms": round(f_avg, 4), "min_ms": round(f_min, 4),
+                        "achieved_GBps": round(alg / (f_avg * 1e-3) / 1e9, 1)},
+            "backward": {"kernel": names["bwd"], "avg_ms": round(b_avg, 4), "min_ms": round(b_min, 4),
+                         "achieved_GBps": round(alg / (b_avg * 1e-3) / 1e9, 1)},
+        }
+        dom = "backward" if b_avg >= f_avg else "forward"          # the LONGEST launch of the step
+        achieved = launches[dom]["achieved_GBps"]
+
+        sha = lib_sha256(_lib.LIB_PATH)
+        traffic_all, traffic_src, traffic_why = (None, None, "custom shape") if custom else \
+            profile_traffic(cfg_name, sha, [names["fwd"], names["bwd"]])
+        traffic = None
+        if traffic_all:
+            traffic = traffic_all.get(names["bwd" if dom == "backward" else "fwd"])
+        prof_avg, prof_src = (None, "custom shape") if custom else \
+            profile_kernel_avg(cfg_name, sha, names["bwd" if dom == "backward" else "fwd"])
+        return {"bound": "hbm", "kernel": f"{launches[dom]['kernel']}> ({dom} launch: the longest of the step; {kind})",
+                "achieved": achieved, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                "frac": round(achieved * 1e9 / HBM_PEAK, 4), "traffic": traffic,
+                "traffic_source": traffic_src, "traffic_note": traffic_why,
+                "traffic_all_launches": traffic_all,
+                "avg_launch_ms": launches[dom]["avg_ms"], "min_launch_ms": launches[dom]["min_ms"],
+                "avg_launch_source": "HIP events in this process, launches issued one at a time "
+                                     "(achieved / frac above)",
+                # the same kernel in the committed rocprofv3 --kernel-trace --stats pass of this build:
+                # average over every launch of the profiled bench command (graph replays, in-step)
+                "profile_avg_launch_ms": None if prof_avg is None else round(prof_avg * 1e-3, 4),
+                "profile_frac": None if prof_avg is None else round(alg / (prof_avg * 1e-6) / HBM_PEAK, 4),
+                "profile_source": prof_src,
+                "algorithmic_bytes_per_launch": alg, "launches": launches,
+                "libsmx_sha256": sha}
 
     api = 'spectral_mix_with_filter(WirtingerSpectralFilter)' if cfg['api'] == 'wirtinger' else 'SpectralMixingLayer'
     res = {
@@ -580,24 +650,11 @@ def measure(rt, args, cfg_name, cfg, steps, custom=False):
                    "plan": {"path": plan.path, "L": plan.L, "bands": plan.bands,
                             "nsplit": plan.nsplit, "workgroups": plan.workgroups, "groups": plan.groups}},
         "hbm_roofline_frac_fwd_bwd": round(16.0 * B * N * D / (ms_step * 1e-3) / HBM_PEAK, 4),
-        "roofline": {"bound": "hbm", "kernel": f"{launches[dom]['kernel']}> ({dom} launch: the longest of the step; {kind})",
-                     "achieved": achieved, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                     "frac": round(achieved * 1e9 / HBM_PEAK, 4), "traffic": traffic,
-                     "traffic_source": traffic_src, "traffic_note": traffic_why,
-                     "traffic_all_launches": traffic_all,
-                     "avg_launch_ms": launches[dom]["avg_ms"], "min_launch_ms": launches[dom]["min_ms"],
-                     "avg_launch_source": "HIP events in this process, launches issued one at a time "
-                                          "(achieved / frac above)",
-                     # the same kernel in the committed rocprofv3 --kernel-trace --stats pass of this build:
-                     # average over every launch of the profiled bench command (graph replays, in-step)
-                     "profile_avg_launch_ms": None if prof_avg is None else round(prof_avg * 1e-3, 4),
-                     "profile_frac": None if prof_avg is None else round(alg / (prof_avg * 1e-6) / HBM_PEAK, 4),
-                     "profile_source": prof_src,
-                     "algorithmic_bytes_per_launch": alg, "launches": launches,
-                     "libsmx_sha256": sha},
     }
+    if args.full:
+        res["roofline"] = launch_roofline()
     # give the (up to 2 GiB of) tensors of this workload back before the next one is set up
-    del x, g, gx, xk, xd, plan_runs, evs, module, unit, params
+    del x, g, plan_runs, evs, module, unit, params, held, last_held
     functional.release_workspaces()
     torch.cuda.empty_cache()
     return res
@@ -637,7 +694,8 @@ def main():
         for kv in filter(None, args.opts.split(";")):
             k, v = kv.split("=")
             _lib.set_option(k.strip(), int(v))
-    res = dry_run(rt, args) if rt.dry else measure(rt, args, args.config, cfg, args.steps, custom)
+    res = dry_run(rt, args) if rt.dry else measure(rt, args, args.config, cfg, args.steps, custom,
+                                                   dump_dir=args.dump_outputs)
     if args.opts:
         res.setdefault("config", {})["opts"] = args.opts
     out = {
@@ -653,9 +711,9 @@ def main():
     }
     out.update(res)
 
-    # ---- the other single-GPU BASELINE configs on the same line (same binary, same box, same protocol) ------
-    if (rt.world == 1 and not rt.dry and not custom and args.config == "c2" and not args.no_other_configs
-            and not rt.use_dist):
+    # ---- --full: the other single-GPU BASELINE configs on the same line (same binary, same box, same protocol) --
+    if (args.full and rt.world == 1 and not rt.dry and not custom and args.config == "c2"
+            and not args.no_other_configs and not rt.use_dist):
         others = {}
         for name in ("c3", "c5"):
             try:
@@ -678,13 +736,13 @@ def main():
             others["f2"] = {"error": f"{type(e).__name__}: {e}"}
         out["other_configs"] = others
 
-    if rt.rank == 0 and not rt.dry and os.environ.get("SMX_BENCH_NO_BOX") != "1":
+    if args.full and rt.rank == 0 and not rt.dry and os.environ.get("SMX_BENCH_NO_BOX") != "1":
         try:
             out["box"] = measure_box(rt.dev)
             out["box"]["step_over_copy"] = round(out["ms_per_step"] * 1e3 / out["box"]["copy_256MiB_us"], 3)
         except Exception as e:                                             # noqa: BLE001
             out["box"] = {"error": f"{type(e).__name__}: {e}"}
-    if rt.rank == 0 and rt.world == 1 and not rt.dry and not args.no_cpu_baseline:
+    if args.full and rt.rank == 0 and rt.world == 1 and not rt.dry and not args.no_cpu_baseline:
         iters = 8 if args.config == "c2" else 3
         out["cpu_baseline"] = cpu_baseline(cfg["B"], cfg["N"], cfg["D"], cfg["F"], iters)
     if rt.rank == 0:

@@ -83,7 +83,7 @@ def test_world_size_mismatch_is_refused():
 def test_self_launch_two_ranks_real_step_on_one_gpu(gpu):
     """Exactly the command of VERDICT r2 #1: no launcher, two ranks, the real HIP step (both ranks on cuda:0,
     gloo instead of RCCL because one device cannot host two RCCL ranks)."""
-    p, lines = _run(["--gpus", "2", "--steps", "4", "--warmup", "1"],
+    p, lines = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--full"],
                     {"SMX_BENCH_ONE_DEVICE": "1", "SMX_BENCH_BACKEND": "gloo"}, timeout=850)
     assert p.returncode == 0, p.stderr[-3000:]
     js = [l for l in lines if l.startswith("{")]

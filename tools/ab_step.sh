@@ -9,7 +9,7 @@ ROUNDS=${ROUNDS:-2}
 for round in $(seq $ROUNDS); do
   for cand in "$@"; do
     lib=${cand%%:*}; opts=""; [ "$cand" != "$lib" ] && opts=${cand#*:}
-    SMX_LIB=$C/$lib timeout -k 10 180 python3 "$C/../../bench.py" --steps 20 --warmup 5 --no-cpu-baseline --opts "$opts" ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
+    SMX_LIB=$C/$lib timeout -k 10 180 python3 "$C/../../bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --opts "$opts" ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if not l.startswith('{'): continue

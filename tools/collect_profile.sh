@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 # SMX_PROFILE_CMD overrides the profiled command (default: the bench), e.g. the block bench
 # (10 steps per hipGraph: the counter passes serialise every kernel node, and a 50-step graph of the residue-split
 #  plan -- 450 nodes per replay -- sat silent for seven minutes in the first --pmc pass of round 4)
-CMD=${SMX_PROFILE_CMD:-"python3 $R/bench.py --config $CFG --no-cpu-baseline --no-other-configs --steps 50 --warmup 10 --steps-per-graph 10"}
+CMD=${SMX_PROFILE_CMD:-"python3 $R/bench.py --full --config $CFG --no-cpu-baseline --no-other-configs --steps 50 --warmup 10 --steps-per-graph 10"}
 T="timeout -k 10 ${SMX_PROFILE_PASS_S:-300}"
 export SMX_BENCH_NO_BOX=1        # (the yardstick copies and the clock kernel are not part of the profiled step)
 $T rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- $CMD > "$O/stats.log" 2>&1

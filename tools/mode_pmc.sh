@@ -10,7 +10,7 @@ mkdir -p "$O"
 O=$(cd "$O" && pwd)
 cd /tmp && export TMPDIR=/tmp
 for i in $(seq 1 $N); do
-  rocprofv3 --pmc "$@" --output-format csv -d "$O/run$i" -- python3 $R/bench.py --no-cpu-baseline --no-other-configs --steps 50 --warmup 10 > "$O/run$i.log" 2>&1
+  rocprofv3 --pmc "$@" --output-format csv -d "$O/run$i" -- python3 $R/bench.py --full --no-cpu-baseline --no-other-configs --steps 50 --warmup 10 > "$O/run$i.log" 2>&1
   echo "run $i done: $(grep -h '^{' $O/run$i.log | tail -1 | cut -c1-120)"
 done
 python3 $R/tools/mode_pmc_summary.py "$O" > "$O/summary.json"

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp SMX_BENCH_NO_BOX=1
 for i in $(seq $N); do
   O=$R/gpurun_out/mode_probe/$i
   rm -rf "$O"; mkdir -p "$O"
-  timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -- python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > "$O/log.txt" 2>&1
+  timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > "$O/log.txt" 2>&1
   python3 - "$O" <<'PY'
 import sys, json, glob, csv
 o = sys.argv[1]

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${1:-r04}
 for sp in 4 0 16; do
   SMX_PROFILE_EXTRA=1 SMX_PROFILE_ONLY_L2=1 SMX_PROFILE_PASS_S=120 \
-  SMX_PROFILE_CMD="python3 $R/bench.py --config c2 --no-cpu-baseline --no-other-configs --steps 30 --warmup 10 --steps-per-graph 10 --opts st_plain=$sp" \
+  SMX_PROFILE_CMD="python3 $R/bench.py --full --config c2 --no-cpu-baseline --no-other-configs --steps 30 --warmup 10 --steps-per-graph 10 --opts st_plain=$sp" \
     bash "$R/tools/collect_profile.sh" "${TAG}sp$sp" c2 > /dev/null 2>&1
   echo "st_plain=$sp done" >> "$R/gpurun_out/pmc_l2_progress.txt"
 done

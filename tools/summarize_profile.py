@@ -22,7 +22,7 @@ def csrc_sha256():
     return h.hexdigest()
 
 
-def main(o, tag, cmd="python3 bench.py --no-cpu-baseline --steps 50 --warmup 10", git_sha="unknown",
+def main(o, tag, cmd="python3 bench.py --full --no-cpu-baseline --steps 50 --warmup 10", git_sha="unknown",
          lib_sha=None):
     out = {"tag": tag, "command": cmd, "git_sha": git_sha, "libsmx_sha256": lib_sha, "csrc_sha256": csrc_sha256(),
            "notes": "FETCH_SIZE/WRITE_SIZE are KiB; on gfx950 FETCH_SIZE counts half the bytes of a "
