@@ -447,6 +447,50 @@ int smx_mix_forward(const float* r, const float* a, const float* b, const float*
 int smx_mix_backward(const float* g, const float* a, const float* b, const float* w, float c3, float* grad_a, float* grad_b,
                      float* grad_c, float* grad_w, void* workspace, size_t workspace_bytes, long long n, void* stream);
 
+/* Row lines of EnhancedSpectralBlock (fft_tensor/spectral_enhancements.py:278-333), one launch each way:
+ *   smx_rope_norm_*      line 1, :321 with RotaryFrequencyEmbedding :47-71 and nn.LayerNorm norm1 / norm2 (:305-306):
+ *                          h1 = LN(x; ln1),  r = pairwise rotation of h1 by rotation[t] (complex64, (rot_rows, D/2)),
+ *                          x1 = x + M1 r,  h2 = LN(x1; ln2);  stats (2, B, T, 2) = (mean, rstd) of both norms.
+ *                        norm == 0: the standalone RotaryFrequencyEmbedding, x1 = rotation(x) (ln*, h2, stats unused).
+ *                        Backward given g1 = dL/dx1 and gh2 = dL/dh2: G = g1 + LN2'(gh2), grad_x = G + LN1'(rot^T(M1 G)),
+ *                        x1 recomputed from x in registers.  T > rot_rows -> SMX_ERR_INVALID.
+ *   smx_residual_norm_*  the residual of line 2 and norm3 (:324, :327): x2 = x1 + M2 p,  h3 = LN(x2; ln3);
+ *                        backward G = g2 + LN3'(gh3) -> grad_x1 = G, grad_p = M2 G (grad_p may be NULL without dropout:
+ *                        it is then grad_x1).
+ *   smx_gate_blend_*     line 3 after GatedSpectralUnit's two Linears (:105-114, :327): a (B, T, 2D) = gate_proj[0](h3),
+ *                        v = value_proj(h3), ln (2D) = gate_proj[1]:  [z | vt] = LN(a),  gate = sigmoid(z),
+ *                        x3 = x2 + M3 (gate v + (1 - gate) vt)  (x2 == NULL: the standalone unit, x3 = the blend);
+ *                        backward: grad_v, grad_a (grad_x2 is g3 itself); stats (B, T, 2).
+ * M = the library's dropout mask scaled by 1/(1 - p) (as the _dropout twins above: same words forward and backward,
+ * element t D + d of batch row b).  ln_* may be NULL (no affine); gradient outputs g_ln_* may be NULL.  Even D <= 1024
+ * (smx_enh_supported); every tensor 16-byte aligned; backward workspace from smx_enh_workspace_bytes, 256-byte aligned.
+ * LayerNorm parameter gradients are summed in a fixed order: bitwise reproducible. */
+int smx_enh_supported(int D);
+int smx_enh_workspace_bytes(int B, int T, int D, size_t* out);
+int smx_rope_norm_forward(const float* x, const float* rotation, int rot_rows, const float* ln1_w, const float* ln1_b,
+                          const float* ln2_w, const float* ln2_b, float eps1, float eps2, float* x1, float* h2,
+                          float* stats, int B, int T, int D, int norm, float dropout_p, const void* rng_state,
+                          void* stream);
+int smx_rope_norm_backward(const float* g1, const float* gh2, const float* x, const float* rotation, int rot_rows,
+                           const float* ln1_w, const float* ln1_b, const float* ln2_w, const float* stats, float* grad_x,
+                           float* g_ln1_w, float* g_ln1_b, float* g_ln2_w, float* g_ln2_b, void* workspace,
+                           size_t workspace_bytes, int B, int T, int D, int norm, float dropout_p,
+                           const void* rng_state, void* stream);
+int smx_residual_norm_forward(const float* x1, const float* p, const float* ln_w, const float* ln_b, float eps,
+                              float* x2, float* h3, float* stats, int B, int T, int D, float dropout_p,
+                              const void* rng_state, void* stream);
+int smx_residual_norm_backward(const float* g2, const float* gh3, const float* x2, const float* ln_w, const float* stats,
+                               float* grad_x1, float* grad_p, float* g_ln_w, float* g_ln_b, void* workspace,
+                               size_t workspace_bytes, int B, int T, int D, float dropout_p, const void* rng_state,
+                               void* stream);
+int smx_gate_blend_forward(const float* a, const float* v, const float* x2, const float* ln_w, const float* ln_b,
+                           float eps, float* x3, float* stats, int B, int T, int D, float dropout_p,
+                           const void* rng_state, void* stream);
+int smx_gate_blend_backward(const float* g3, const float* a, const float* v, const float* ln_w, const float* ln_b,
+                            const float* stats, float* grad_a, float* grad_v, float* g_ln_w, float* g_ln_b,
+                            void* workspace, size_t workspace_bytes, int B, int T, int D, float dropout_p,
+                            const void* rng_state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,8 @@ from .wirtinger_ops import (ComplexParameter, WirtingerGradient, WirtingerSpectr
                             spectral_mix_with_filter)
 from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft, rfft_bins, seq_fft,
                          spectral_block_mix, spectral_filter, spectral_mix)
-from .spectral_enhancements import MultiScaleSpectralFeatures, PhaseAwareSpectralMixing
+from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
+                                    MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
 from .frequency_ops import FrequencyAttention
 from .fixed_spectral import FixedSpectralBlock, FrequencyConvFunc, causal_spectral_conv
@@ -20,7 +21,8 @@ __all__ = [
     "SpectralMixingLayer", "SpectralMLPBlock", "HybridSpectralAttention", "ComplexParameter", "WirtingerGradient",
     "WirtingerSpectralFilter", "spectral_mix_with_filter", "spectral_mix", "spectral_block_mix",
     "pruned_rfft", "DropoutState", "spectral_filter", "rfft_bins", "seq_fft", "hermitian_scale",
-    "PhaseAwareSpectralMixing", "MultiScaleSpectralFeatures", "ComplexRoPE", "GatedLinearUnit",
+    "PhaseAwareSpectralMixing", "MultiScaleSpectralFeatures", "RotaryFrequencyEmbedding", "GatedSpectralUnit",
+    "CausalFrequencyMask", "EnhancedSpectralBlock", "ComplexRoPE", "GatedLinearUnit",
     "ComplexRoPESpectralLayer", "FrequencyAttention", "FixedSpectralBlock", "FrequencyConvFunc",
     "causal_spectral_conv", "rfft", "irfft", "FrequencyNativeBlock", "BicameralBlock", "PhaseShift", "SpectralFFN",
     "SpectralLayerNorm",

@@ -112,6 +112,15 @@ _SIGS = {
     "smx_mix_workspace_bytes": (_I, [ctypes.POINTER(_SZ)]),
     "smx_mix_forward": (_I, [_P] * 5 + [ctypes.c_float, _P, _LL, _P]),
     "smx_mix_backward": (_I, [_P] * 4 + [ctypes.c_float] + [_P] * 5 + [_SZ, _LL, _P]),
+    "smx_enh_supported": (_I, [_I]),
+    "smx_enh_workspace_bytes": (_I, [_I, _I, _I, ctypes.POINTER(_SZ)]),
+    "smx_rope_norm_forward": (_I, [_P, _P, _I] + [_P] * 4 + [ctypes.c_float] * 2 + [_P] * 3
+                              + [_I] * 4 + [ctypes.c_float, _P, _P]),
+    "smx_rope_norm_backward": (_I, [_P] * 4 + [_I] + [_P] * 10 + [_SZ] + [_I] * 4 + [ctypes.c_float, _P, _P]),
+    "smx_residual_norm_forward": (_I, [_P] * 4 + [ctypes.c_float] + [_P] * 3 + [_I] * 3 + [ctypes.c_float, _P, _P]),
+    "smx_residual_norm_backward": (_I, [_P] * 10 + [_SZ] + [_I] * 3 + [ctypes.c_float, _P, _P]),
+    "smx_gate_blend_forward": (_I, [_P] * 5 + [ctypes.c_float] + [_P] * 2 + [_I] * 3 + [ctypes.c_float, _P, _P]),
+    "smx_gate_blend_backward": (_I, [_P] * 11 + [_SZ] + [_I] * 3 + [ctypes.c_float, _P, _P]),
 }
 
 
@@ -120,7 +129,9 @@ _SINCE = {"smx_diag_clock": 302, "smx_dwconv3_workspace_bytes": 302, "smx_dwconv
           "smx_spectral_ln_backward": 302, "smx_planar_cmul_forward": 302, "smx_planar_cmul_backward": 302,
           "smx_planar_add": 302, "smx_planar_split": 302, "smx_spectral_gate_workspace_bytes": 303,
           "smx_spectral_gate_forward": 303, "smx_spectral_gate_backward": 303, "smx_mix_workspace_bytes": 303,
-          "smx_mix_forward": 303, "smx_mix_backward": 303}        # entry points younger than the oldest library the A/B tools still load
+          "smx_mix_forward": 303, "smx_mix_backward": 303, "smx_enh_supported": 303, "smx_enh_workspace_bytes": 303,
+          "smx_rope_norm_forward": 303, "smx_rope_norm_backward": 303, "smx_residual_norm_forward": 303,
+          "smx_residual_norm_backward": 303, "smx_gate_blend_forward": 303, "smx_gate_blend_backward": 303}        # entry points younger than the oldest library the A/B tools still load
 
 
 def load(path: str):

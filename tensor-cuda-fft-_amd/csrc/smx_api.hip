@@ -1,4 +1,5 @@
 // smx_api.hip -- C ABI (include/smx.h): validation, plan selection, twiddle-table cache, dispatch.
+#include <initializer_list>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -1783,6 +1784,116 @@ int smx_mix_backward(const float* g, const float* a, const float* b, const float
     return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes (smx_mix_workspace_bytes)", need);
   HIP_TRY(launch_mix_bwd(g, a, b, w, c3, grad_a, grad_b, grad_c, grad_w, (float*)((char*)workspace + SYNC_BYTES), n,
                          (hipStream_t)stream));
+  return SMX_OK;
+}
+
+
+// ---- EnhancedSpectralBlock row lines (smx_enh.hip) ----
+int smx_enh_supported(int D) { return enh_supported(D) ? 1 : 0; }
+int smx_enh_workspace_bytes(int B, int T, int D, size_t* out) {
+  if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
+  if (B <= 0 || T <= 0 || D <= 0) return fail(SMX_ERR_INVALID, "shape must be positive: B=%d T=%d D=%d", B, T, D);
+  *out = SYNC_BYTES + al(enh_part_floats((long long)B * T, D) * sizeof(float));
+  return SMX_OK;
+}
+static int enh_check(int B, int T, int D, std::initializer_list<const void*> ptrs) {
+  if (B <= 0 || T <= 0) return fail(SMX_ERR_INVALID, "shape must be positive: B=%d T=%d D=%d", B, T, D);
+  if (!enh_supported(D)) return fail(SMX_ERR_UNSUPPORTED, "the enhanced-block row kernels take an even D <= %d, got %d", ENH_MAX_D, D);
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 15) return fail(SMX_ERR_INVALID, "tensors must be 16-byte aligned");
+  return SMX_OK;
+}
+static int enh_ws(void* workspace, size_t workspace_bytes, int B, int T, int D, float** part) {
+  const size_t need = SYNC_BYTES + al(enh_part_floats((long long)B * T, D) * sizeof(float));
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
+    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes (smx_enh_workspace_bytes)", need);
+  *part = (float*)((char*)workspace + SYNC_BYTES);
+  return SMX_OK;
+}
+int smx_rope_norm_forward(const float* x, const float* rotation, int rot_rows, const float* ln1_w, const float* ln1_b,
+                          const float* ln2_w, const float* ln2_b, float eps1, float eps2, float* x1, float* h2,
+                          float* stats, int B, int T, int D, int norm, float dropout_p, const void* rng_state,
+                          void* stream) {
+  if (!x || !rotation || !x1) return fail(SMX_ERR_INVALID, "x, rotation, x1 must be non-NULL");
+  if (norm && (!h2 || !stats)) return fail(SMX_ERR_INVALID, "h2 and stats must be non-NULL with norm != 0");
+  if (int rc = enh_check(B, T, D, {x, rotation, ln1_w, ln1_b, ln2_w, ln2_b, x1, h2, stats})) return rc;
+  if (T > rot_rows) return fail(SMX_ERR_INVALID, "T = %d is longer than the rotation table (%d rows)", T, rot_rows);
+  DropCfg dc;
+  if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
+  if (!norm && dc.thr) return fail(SMX_ERR_INVALID, "dropout needs norm != 0 (the block line)");
+  HIP_TRY(launch_rope_fwd(x, rotation, ln1_w, ln1_b, ln2_w, ln2_b, eps1, eps2, x1, h2, (cf*)stats, B, T, D, norm != 0,
+                          dc.thr, dc.scale, dc.rng, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_rope_norm_backward(const float* g1, const float* gh2, const float* x, const float* rotation, int rot_rows,
+                           const float* ln1_w, const float* ln1_b, const float* ln2_w, const float* stats, float* grad_x,
+                           float* g_ln1_w, float* g_ln1_b, float* g_ln2_w, float* g_ln2_b, void* workspace,
+                           size_t workspace_bytes, int B, int T, int D, int norm, float dropout_p,
+                           const void* rng_state, void* stream) {
+  if (!g1 || !rotation || !grad_x) return fail(SMX_ERR_INVALID, "g1, rotation, grad_x must be non-NULL");
+  if (norm && (!gh2 || !x || !stats)) return fail(SMX_ERR_INVALID, "gh2, x and stats must be non-NULL with norm != 0");
+  if (int rc = enh_check(B, T, D, {g1, gh2, x, rotation, ln1_w, ln1_b, ln2_w, stats, grad_x})) return rc;
+  if (T > rot_rows) return fail(SMX_ERR_INVALID, "T = %d is longer than the rotation table (%d rows)", T, rot_rows);
+  DropCfg dc;
+  if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
+  if (!norm && dc.thr) return fail(SMX_ERR_INVALID, "dropout needs norm != 0 (the block line)");
+  float* part = nullptr;
+  if (norm)
+    if (int rc = enh_ws(workspace, workspace_bytes, B, T, D, &part)) return rc;
+  HIP_TRY(launch_rope_bwd(g1, gh2, x, rotation, ln1_w, ln1_b, ln2_w, (const cf*)stats, grad_x, g_ln1_w, g_ln1_b, g_ln2_w,
+                          g_ln2_b, part, B, T, D, norm != 0, dc.thr, dc.scale, dc.rng, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_residual_norm_forward(const float* x1, const float* p, const float* ln_w, const float* ln_b, float eps,
+                              float* x2, float* h3, float* stats, int B, int T, int D, float dropout_p,
+                              const void* rng_state, void* stream) {
+  if (!x1 || !p || !x2 || !h3 || !stats) return fail(SMX_ERR_INVALID, "x1, p, x2, h3, stats must be non-NULL");
+  if (int rc = enh_check(B, T, D, {x1, p, ln_w, ln_b, x2, h3, stats})) return rc;
+  DropCfg dc;
+  if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
+  HIP_TRY(launch_res_fwd(x1, p, ln_w, ln_b, eps, x2, h3, (cf*)stats, B, T, D, dc.thr, dc.scale, dc.rng,
+                         (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_residual_norm_backward(const float* g2, const float* gh3, const float* x2, const float* ln_w, const float* stats,
+                               float* grad_x1, float* grad_p, float* g_ln_w, float* g_ln_b, void* workspace,
+                               size_t workspace_bytes, int B, int T, int D, float dropout_p, const void* rng_state,
+                               void* stream) {
+  if (!g2 || !gh3 || !x2 || !stats || !grad_x1) return fail(SMX_ERR_INVALID, "g2, gh3, x2, stats, grad_x1 must be non-NULL");
+  if (int rc = enh_check(B, T, D, {g2, gh3, x2, ln_w, stats, grad_x1, grad_p})) return rc;
+  DropCfg dc;
+  if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
+  if (dc.thr && !grad_p) return fail(SMX_ERR_INVALID, "grad_p must be non-NULL with dropout p > 0");
+  float* part = nullptr;
+  if (int rc = enh_ws(workspace, workspace_bytes, B, T, D, &part)) return rc;
+  HIP_TRY(launch_res_bwd(g2, gh3, x2, ln_w, (const cf*)stats, grad_x1, grad_p, g_ln_w, g_ln_b, part, B, T, D, dc.thr,
+                         dc.scale, dc.rng, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_gate_blend_forward(const float* a, const float* v, const float* x2, const float* ln_w, const float* ln_b,
+                           float eps, float* x3, float* stats, int B, int T, int D, float dropout_p,
+                           const void* rng_state, void* stream) {
+  if (!a || !v || !x3 || !stats) return fail(SMX_ERR_INVALID, "a, v, x3, stats must be non-NULL");
+  if (int rc = enh_check(B, T, D, {a, v, x2, ln_w, ln_b, x3, stats})) return rc;
+  DropCfg dc;
+  if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
+  HIP_TRY(launch_gate_blend_fwd(a, v, x2, ln_w, ln_b, eps, x3, (cf*)stats, B, T, D, dc.thr, dc.scale, dc.rng,
+                                (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_gate_blend_backward(const float* g3, const float* a, const float* v, const float* ln_w, const float* ln_b,
+                            const float* stats, float* grad_a, float* grad_v, float* g_ln_w, float* g_ln_b,
+                            void* workspace, size_t workspace_bytes, int B, int T, int D, float dropout_p,
+                            const void* rng_state, void* stream) {
+  if (!g3 || !a || !v || !stats || !grad_a || !grad_v)
+    return fail(SMX_ERR_INVALID, "g3, a, v, stats, grad_a, grad_v must be non-NULL");
+  if (int rc = enh_check(B, T, D, {g3, a, v, ln_w, ln_b, stats, grad_a, grad_v})) return rc;
+  DropCfg dc;
+  if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
+  float* part = nullptr;
+  if (int rc = enh_ws(workspace, workspace_bytes, B, T, D, &part)) return rc;
+  HIP_TRY(launch_gate_blend_bwd(g3, a, v, ln_w, ln_b, (const cf*)stats, grad_a, grad_v, g_ln_w, g_ln_b, part, B, T, D,
+                                dc.thr, dc.scale, dc.rng, (hipStream_t)stream));
   return SMX_OK;
 }
 

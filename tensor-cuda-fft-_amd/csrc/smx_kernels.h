@@ -227,5 +227,36 @@ hipError_t launch_add_rows(float* y, const float* x, size_t total, hipStream_t s
 hipError_t launch_ln_bwd(float* gh_dx, const float* x, const float* g, const cf* stats,
                          const float* gamma, float* part, float* g_gamma, float* g_beta,
                          long long rows, int D, hipStream_t s);
+// g_gamma[d] = sum_blk part[blk][0][d], g_beta[d] = sum_blk part[blk][1][d] (fixed order; either may be null)
+hipError_t launch_ln_colsum(const float* part, int nblk, int D, float* g_gamma, float* g_beta, hipStream_t s);
+
+// ---- row kernels of EnhancedSpectralBlock (smx_enh.hip) --------------------------------------------
+constexpr int ENH_MAX_D = 1024;          // widest row (even) held in one wavefront's registers; the gate row is 2D
+bool enh_supported(int D);
+// partial-sum scratch of the backward launches: ln_num_blocks(rows) x 4 x D floats
+size_t enh_part_floats(long long rows, int D);
+// A: x1 = x + M1 rot(LN1(x)), h2 = LN2(x1), stats (2, B T) (mean, rstd) of both norms; norm == false: x1 = rot(x)
+hipError_t launch_rope_fwd(const float* x, const float* rot, const float* w1, const float* b1, const float* w2,
+                           const float* b2, float eps1, float eps2, float* x1, float* h2, cf* stats, int B, int T,
+                           int D, bool norm, unsigned thr, float scale, const unsigned long long* rng, hipStream_t s);
+hipError_t launch_rope_bwd(const float* g1, const float* gh2, const float* x, const float* rot, const float* w1,
+                           const float* b1, const float* w2, const cf* stats, float* gx, float* gw1, float* gb1,
+                           float* gw2, float* gb2, float* part, int B, int T, int D, bool norm, unsigned thr,
+                           float scale, const unsigned long long* rng, hipStream_t s);
+// B: x2 = x1 + M2 p, h3 = LN3(x2)
+hipError_t launch_res_fwd(const float* x1, const float* p, const float* w3, const float* b3, float eps, float* x2,
+                          float* h3, cf* stats, int B, int T, int D, unsigned thr, float scale,
+                          const unsigned long long* rng, hipStream_t s);
+hipError_t launch_res_bwd(const float* g2, const float* gh3, const float* x2, const float* w3, const cf* stats,
+                          float* gx1, float* gp, float* gw3, float* gb3, float* part, int B, int T, int D, unsigned thr,
+                          float scale, const unsigned long long* rng, hipStream_t s);
+// C: x3 = x2 + M3 (gate v + (1 - gate) vt), [gate pre-activation | vt] = LN_2D(a); x2 may be null
+hipError_t launch_gate_blend_fwd(const float* a, const float* v, const float* x2, const float* wg, const float* bg,
+                                 float eps, float* x3, cf* stats, int B, int T, int D, unsigned thr, float scale,
+                                 const unsigned long long* rng, hipStream_t s);
+hipError_t launch_gate_blend_bwd(const float* g3, const float* a, const float* v, const float* wg, const float* bg,
+                                 const cf* stats, float* ga, float* gv, float* gwg, float* gbg, float* part, int B,
+                                 int T, int D, unsigned thr, float scale, const unsigned long long* rng,
+                                 hipStream_t s);
 
 }  // namespace smx

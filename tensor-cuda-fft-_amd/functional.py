@@ -1470,3 +1470,220 @@ def rank_one_conv(x: torch.Tensor, h_re: torch.Tensor, h_im: torch.Tensor,
         raise ValueError(f"rank_one_conv does not take (B={B}, rows={R}, D={D}, n_fft={n_fft}); use spectral_filter")
     return _RankOneConv.apply(_dense(x), _dense(h_re), _dense(h_im), _dense(scale), int(n_fft),
                               torch.is_grad_enabled())
+
+
+# ---- row lines of EnhancedSpectralBlock (reference fft_tensor/spectral_enhancements.py:278-333), smx_enh.hip -------
+
+_enh_supported_cache: dict = {}
+
+
+def enh_supported(D: int) -> bool:
+    """Even D <= 1024: the row kernels of the enhanced block hold a row (the gate row: 2D) in one wavefront."""
+    D = int(D)
+    v = _enh_supported_cache.get(D)
+    if v is None:
+        v = _enh_supported_cache[D] = bool(_lib.lib().smx_enh_supported(D))
+    return v
+
+
+def _enh_workspace(dev: torch.device, B: int, T: int, D: int) -> torch.Tensor:
+    import ctypes
+    nb = ctypes.c_size_t()
+    _lib.check(_lib.lib().smx_enh_workspace_bytes(B, T, D, ctypes.byref(nb)))
+    return _workspace(dev, int(nb.value))
+
+
+def _grad_buf(t: Optional[torch.Tensor], needed: bool) -> Optional[torch.Tensor]:
+    return torch.empty_like(t) if (t is not None and needed) else None
+
+
+def _g(g: Optional[torch.Tensor], like: torch.Tensor) -> torch.Tensor:
+    """An upstream gradient autograd left undefined (output unused) is zero."""
+    if g is None:
+        return torch.zeros_like(like)
+    return _dense(g.float() if g.dtype != torch.float32 else g)
+
+
+class _RopeNorm(torch.autograd.Function):
+    """Line 1 of the block and the norm of line 2 (reference :321, :324):  x1 = x + M1 rope(norm1(x)),
+    h2 = norm2(x1), through smx_rope_norm_forward / _backward.  norm = False: the standalone rotation."""
+
+    @staticmethod
+    def forward(ctx, x, rot, rot_rows, w1, b1, w2, b2, eps1, eps2, norm, dropout_p, drop_state):
+        B, T, D = x.shape
+        rng = drop_state.next() if dropout_p > 0.0 else None
+        x1 = torch.empty_like(x)
+        h2 = torch.empty_like(x) if norm else None
+        stats = torch.empty((2, B, T, 2), dtype=torch.float32, device=x.device) if norm else None
+        with _on_device(x.device):
+            _lib.check(_lib.lib().smx_rope_norm_forward(
+                x.data_ptr(), rot.data_ptr(), rot_rows, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(eps1),
+                float(eps2), x1.data_ptr(), _ptr(h2), _ptr(stats), B, T, D, int(norm), float(dropout_p), _ptr(rng),
+                _stream(x.device)))
+        ctx.meta = (rot_rows, norm, dropout_p, rng)
+        ctx.save_for_backward(x if norm else None, rot, w1, b1, w2, stats)
+        if not norm:
+            return x1
+        return x1, h2
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g1, gh2=None):
+        x, rot, w1, b1, w2, stats = ctx.saved_tensors
+        rot_rows, norm, dropout_p, rng = ctx.meta
+        g1 = _g(g1, x) if norm else _dense(g1.float() if g1.dtype != torch.float32 else g1)
+        B, T, D = g1.shape
+        nig = ctx.needs_input_grad
+        gx = torch.empty_like(g1)
+        gw1, gb1, gw2 = _grad_buf(w1, nig[3]), _grad_buf(b1, nig[4]), _grad_buf(w2, nig[5])
+        gb2 = torch.empty(D, dtype=torch.float32, device=g1.device) if (norm and nig[6]) else None
+        ws = _enh_workspace(g1.device, B, T, D) if norm else None
+        gh2 = _g(gh2, g1) if norm else None
+        with _on_device(g1.device):
+            _lib.check(_lib.lib().smx_rope_norm_backward(
+                g1.data_ptr(), _ptr(gh2), _ptr(x), rot.data_ptr(), rot_rows, _ptr(w1), _ptr(b1), _ptr(w2),
+                _ptr(stats), gx.data_ptr(), _ptr(gw1), _ptr(gb1), _ptr(gw2), _ptr(gb2), _ptr(ws),
+                0 if ws is None else ws.numel(), B, T, D, int(norm), float(dropout_p), _ptr(rng), _stream(g1.device)))
+        return gx, None, None, gw1, gb1, gw2, gb2, None, None, None, None, None
+
+
+class _ResidualNorm(torch.autograd.Function):
+    """The residual of line 2 and norm3 (reference :324, :327): x2 = x1 + M2 p, h3 = norm3(x2)."""
+
+    @staticmethod
+    def forward(ctx, x1, p, w3, b3, eps, dropout_p, drop_state):
+        B, T, D = x1.shape
+        rng = drop_state.next() if dropout_p > 0.0 else None
+        x2, h3 = torch.empty_like(x1), torch.empty_like(x1)
+        stats = torch.empty((B, T, 2), dtype=torch.float32, device=x1.device)
+        with _on_device(x1.device):
+            _lib.check(_lib.lib().smx_residual_norm_forward(
+                x1.data_ptr(), p.data_ptr(), _ptr(w3), _ptr(b3), float(eps), x2.data_ptr(), h3.data_ptr(),
+                stats.data_ptr(), B, T, D, float(dropout_p), _ptr(rng), _stream(x1.device)))
+        ctx.meta = (dropout_p, rng)
+        ctx.save_for_backward(x2, w3, b3, stats)
+        return x2, h3
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g2, gh3):
+        x2, w3, b3, stats = ctx.saved_tensors
+        dropout_p, rng = ctx.meta
+        g2, gh3 = _g(g2, x2), _g(gh3, x2)
+        B, T, D = x2.shape
+        nig = ctx.needs_input_grad
+        gx1 = torch.empty_like(x2)
+        gp = torch.empty_like(x2) if dropout_p > 0.0 else None      # without dropout grad_p is grad_x1 itself
+        gw3, gb3 = _grad_buf(w3, nig[2]), _grad_buf(b3, nig[3])
+        ws = _enh_workspace(x2.device, B, T, D)
+        with _on_device(x2.device):
+            _lib.check(_lib.lib().smx_residual_norm_backward(
+                g2.data_ptr(), gh3.data_ptr(), x2.data_ptr(), _ptr(w3), stats.data_ptr(), gx1.data_ptr(), _ptr(gp),
+                _ptr(gw3), _ptr(gb3), ws.data_ptr(), ws.numel(), B, T, D, float(dropout_p), _ptr(rng),
+                _stream(x2.device)))
+        return gx1, (gp if gp is not None else gx1), gw3, gb3, None, None, None
+
+
+class _GateBlend(torch.autograd.Function):
+    """GatedSpectralUnit after its two Linears, plus the residual of line 3 (reference :105-114, :327):
+    [z | vt] = LayerNorm_2D(a),  x3 = x2 + M3 (sigmoid(z) v + (1 - sigmoid(z)) vt)  (x2 None: the unit alone)."""
+
+    @staticmethod
+    def forward(ctx, a, v, x2, wg, bg, eps, dropout_p, drop_state):
+        B, T, D = v.shape
+        rng = drop_state.next() if dropout_p > 0.0 else None
+        x3 = torch.empty_like(v)
+        stats = torch.empty((B, T, 2), dtype=torch.float32, device=v.device)
+        with _on_device(v.device):
+            _lib.check(_lib.lib().smx_gate_blend_forward(
+                a.data_ptr(), v.data_ptr(), _ptr(x2), _ptr(wg), _ptr(bg), float(eps), x3.data_ptr(), stats.data_ptr(),
+                B, T, D, float(dropout_p), _ptr(rng), _stream(v.device)))
+        ctx.meta = (dropout_p, rng)
+        ctx.save_for_backward(a, v, wg, bg, stats)
+        return x3
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g3):
+        a, v, wg, bg, stats = ctx.saved_tensors
+        dropout_p, rng = ctx.meta
+        g3 = _g(g3, v)
+        B, T, D = v.shape
+        nig = ctx.needs_input_grad
+        ga, gv = torch.empty_like(a), torch.empty_like(v)
+        gwg, gbg = _grad_buf(wg, nig[3]), _grad_buf(bg, nig[4])
+        ws = _enh_workspace(v.device, B, T, D)
+        with _on_device(v.device):
+            _lib.check(_lib.lib().smx_gate_blend_backward(
+                g3.data_ptr(), a.data_ptr(), v.data_ptr(), _ptr(wg), _ptr(bg), stats.data_ptr(), ga.data_ptr(),
+                gv.data_ptr(), _ptr(gwg), _ptr(gbg), ws.data_ptr(), ws.numel(), B, T, D, float(dropout_p), _ptr(rng),
+                _stream(v.device)))
+        return ga, gv, (g3 if nig[2] else None), gwg, gbg, None, None, None
+
+
+def _rotation_rows(rotation: torch.Tensor, D: int):
+    """(float view of the complex64 table with rows of D floats, its row count)."""
+    if rotation.dtype != torch.complex64:
+        raise TypeError(f"rotation must be complex64, got {rotation.dtype}")
+    if rotation.shape[1] != D // 2:
+        rotation = rotation[:, :D // 2]
+    return _dense(torch.view_as_real(rotation)), int(rotation.shape[0])
+
+
+def _check_rows(x: torch.Tensor, D: int) -> None:
+    _require_gpu_f32("x", x)
+    if x.dim() != 3 or x.shape[-1] != D:
+        raise ValueError(f"expected (B, T, {D}), got {tuple(x.shape)}")
+    if not enh_supported(D):
+        raise ValueError(f"the enhanced-block row kernels take an even D <= 1024, got {D}")
+
+
+def rope_rotate(x: torch.Tensor, rotation: torch.Tensor) -> torch.Tensor:
+    """RotaryFrequencyEmbedding.forward (reference :47-71): channel pairs of x (B, T, D) as complex numbers times
+    rotation[t] ((max_seq_len, >= D/2) complex64), one launch each way."""
+    B, T, D = x.shape
+    _check_rows(x, D)
+    rot, rows = _rotation_rows(rotation, D)
+    if T > rows:
+        raise RuntimeError(f"sequence length {T} exceeds the rotation table ({rows} positions)")
+    return _RopeNorm.apply(_dense(x), rot, rows, None, None, None, None, 0.0, 0.0, False, 0.0, None)
+
+
+def rope_norm(x: torch.Tensor, rotation: torch.Tensor, w1, b1, w2, b2, eps1: float, eps2: float,
+              dropout_p: float = 0.0, drop_state: Optional[DropoutState] = None):
+    """(x1, h2) = (x + dropout(rope(LayerNorm(x; w1, b1))), LayerNorm(x1; w2, b2)): line 1 of the block."""
+    B, T, D = x.shape
+    _check_rows(x, D)
+    rot, rows = _rotation_rows(rotation, D)
+    if T > rows:
+        raise RuntimeError(f"sequence length {T} exceeds the rotation table ({rows} positions)")
+    p = _check_p(dropout_p)
+    return _RopeNorm.apply(_dense(x), rot, rows, _dense(w1), _dense(b1), _dense(w2), _dense(b2), float(eps1),
+                           float(eps2), True, p, drop_state if p > 0.0 else None)
+
+
+def residual_norm(x1: torch.Tensor, p_in: torch.Tensor, w3, b3, eps: float, dropout_p: float = 0.0,
+                  drop_state: Optional[DropoutState] = None):
+    """(x2, h3) = (x1 + dropout(p_in), LayerNorm(x2; w3, b3))."""
+    B, T, D = x1.shape
+    _check_rows(x1, D)
+    _check_rows(p_in, D)
+    p = _check_p(dropout_p)
+    return _ResidualNorm.apply(_dense(x1), _dense(p_in), _dense(w3), _dense(b3), float(eps), p,
+                               drop_state if p > 0.0 else None)
+
+
+def gate_blend(a: torch.Tensor, v: torch.Tensor, x2: Optional[torch.Tensor], wg, bg, eps: float,
+               dropout_p: float = 0.0, drop_state: Optional[DropoutState] = None) -> torch.Tensor:
+    """x2 + dropout(g v + (1 - g) vt) with [z | vt] = LayerNorm(a; wg, bg) over 2D and g = sigmoid(z) (x2 None:
+    the blend alone, GatedSpectralUnit.forward after its Linears)."""
+    B, T, D = v.shape
+    _check_rows(v, D)
+    _require_gpu_f32("a", a)
+    if tuple(a.shape) != (B, T, 2 * D):
+        raise ValueError(f"a must be (B, T, 2D) = ({B}, {T}, {2 * D}), got {tuple(a.shape)}")
+    if x2 is not None:
+        _check_rows(x2, D)
+    p = _check_p(dropout_p)
+    return _GateBlend.apply(_dense(a), _dense(v), _dense(x2), _dense(wg), _dense(bg), float(eps), p,
+                            drop_state if p > 0.0 else None)
