@@ -360,6 +360,29 @@ int smx_backward_dropout(const float* g, const float* xk, const float* w_re, con
                          size_t workspace_bytes, int B, int N, int D, int F, int phases,
                          float dropout_p, const void* rng_state, const float* filter_pack,
                          void* stream);
+/* ---- 2-byte activations ------------------------------------------------------------------------------------------
+ * smx_forward_io / smx_backward_io: smx_forward_dropout / smx_backward_dropout with x, y, g, grad_x in the element
+ * type `io` -- SMX_IO_F32 (exactly the f32 entries), SMX_IO_BF16 or SMX_IO_F16.  Everything else keeps its f32 type:
+ * the filter, bias and their gradients, the saved spectrum xk, the workspace (same size).  Arithmetic is f32: the
+ * 2-byte input is widened on load (exact), y / grad_x are rounded once at the store, to nearest even (a NaN stays a
+ * NaN, fp16 overflow goes to +-inf) -- every output equals the f32 entry's output on the widened input, rounded to
+ * `io`, bit for bit; xk and the parameter gradients equal the f32 entry's, bit for bit.
+ * Native 2-byte I/O exists on the single-launch and residue-split plans with k <= 512 of the layer shapes
+ * (smx_io_supported == 1).  Any other plan returns SMX_ERR_UNSUPPORTED: the caller widens the input itself and
+ * calls the f32 entry.  Pointers: x / y / g / grad_x 4-byte aligned for a 2-byte `io` (8 for SMX_IO_F32).
+ * Replaces: reference fft_tensor/spectral_layers.py:88-116 (the layer forward) and its autograd backward, in
+ * bf16 / fp16 -- which the reference's torch.fft refuses (bf16) or runs in complex32 for powers of two only (fp16). */
+#define SMX_IO_F32 0
+#define SMX_IO_BF16 1
+#define SMX_IO_F16 2
+int smx_io_supported(int B, int N, int D, int F, int io);
+int smx_forward_io(const void* x, const float* w_re, const float* w_im, const float* bias, void* y,
+                   float* xk_save, void* workspace, size_t workspace_bytes, int B, int N, int D, int F,
+                   int conj_w, float dropout_p, const void* rng_state, float* filter_pack, void* stream, int io);
+int smx_backward_io(const void* g, const float* xk, const float* w_re, const float* w_im, void* grad_x,
+                    float* gw_re, float* gw_im, float* gbias, void* workspace, size_t workspace_bytes, int B,
+                    int N, int D, int F, int phases, float dropout_p, const void* rng_state,
+                    const float* filter_pack, void* stream, int io);
 int smx_block_forward_dropout(const float* x, const float* ln_w, const float* ln_b, float eps,
                               const float* w_re, const float* w_im, const float* bias, float* y,
                               float* xk_save, float* ln_stats, void* workspace,

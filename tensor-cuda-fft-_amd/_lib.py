@@ -121,6 +121,10 @@ _SIGS = {
     "smx_residual_norm_backward": (_I, [_P] * 10 + [_SZ] + [_I] * 3 + [ctypes.c_float, _P, _P]),
     "smx_gate_blend_forward": (_I, [_P] * 5 + [ctypes.c_float] + [_P] * 2 + [_I] * 3 + [ctypes.c_float, _P, _P]),
     "smx_gate_blend_backward": (_I, [_P] * 11 + [_SZ] + [_I] * 3 + [ctypes.c_float, _P, _P]),
+    "smx_io_supported": (_I, [_I] * 5),
+    "smx_forward_io": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I]),
+    "smx_backward_io": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, ctypes.c_float,
+                             _P, _P, _P, _I]),
 }
 
 
@@ -131,7 +135,8 @@ _SINCE = {"smx_diag_clock": 302, "smx_dwconv3_workspace_bytes": 302, "smx_dwconv
           "smx_spectral_gate_forward": 303, "smx_spectral_gate_backward": 303, "smx_mix_workspace_bytes": 303,
           "smx_mix_forward": 303, "smx_mix_backward": 303, "smx_enh_supported": 303, "smx_enh_workspace_bytes": 303,
           "smx_rope_norm_forward": 303, "smx_rope_norm_backward": 303, "smx_residual_norm_forward": 303,
-          "smx_residual_norm_backward": 303, "smx_gate_blend_forward": 303, "smx_gate_blend_backward": 303}        # entry points younger than the oldest library the A/B tools still load
+          "smx_residual_norm_backward": 303, "smx_gate_blend_forward": 303, "smx_gate_blend_backward": 303,
+          "smx_io_supported": 303, "smx_forward_io": 303, "smx_backward_io": 303}        # entry points younger than the oldest library the A/B tools still load
 
 
 def load(path: str):
@@ -184,6 +189,14 @@ def plan(B: int, N: int, D: int, F: int) -> smx_plan:
     p = smx_plan()
     check(lib().smx_plan_query(B, N, D, F, ctypes.byref(p)))
     return p
+
+
+SMX_IO_F32, SMX_IO_BF16, SMX_IO_F16 = 0, 1, 2       # include/smx.h: element type of x / y / g / grad_x
+
+
+def io_supported(B: int, N: int, D: int, F: int, io: int) -> bool:
+    """True when the plan of this layer shape (current options) reads and writes `io` elements natively."""
+    return bool(lib().smx_io_supported(B, N, D, F, io))
 
 
 def workspace_bytes(B: int, N: int, D: int, F: int) -> int:

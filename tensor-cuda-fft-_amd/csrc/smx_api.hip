@@ -414,7 +414,8 @@ int need_ws(const Ws& w, void* ws, size_t bytes) {
   return SMX_OK;
 }
 
-DecimArgs decim_args(const Plan& p, const Tables& t, const Shape& h, char* ws, const Ws& w) {
+// elem: bytes per element of the streamed x / y (4; 2 for the 2-byte activations of smx_forward_io / smx_backward_io)
+DecimArgs decim_args(const Plan& p, const Tables& t, const Shape& h, char* ws, const Ws& w, int elem = 4) {
   const int B = h.B, N = h.N, D = h.D, F = h.F;
   DecimArgs a{};
   a.tw = t.tw; a.bt = t.bt; a.tq = t.tq;
@@ -428,8 +429,9 @@ DecimArgs decim_args(const Plan& p, const Tables& t, const Shape& h, char* ws, c
   // Measured at step level on five shapes (profiles/r04_store_policy.txt): L2 + Infinity Cache take about 64 MiB of
   // dirty lines per launch sequence at no cost -- those stores retire at cache speed and drain while the next
   // launch reads -- all-streaming stores leave that unused (C2 +9 % step time), all-cached ones overflow it (+13 %).
+  // (stated in bytes of the output: a 2-byte output of the same shape is half as many MiB)
   {
-    const double mib = 4.0 * B * (double)h.R * D / (1 << 20);
+    const double mib = (double)elem * B * (double)h.R * D / (1 << 20);
     // (the residue-split plan writes the whole tensor in ONE write-only launch: four rows up to 768 MiB -- C3 0.448 ms
     //  against 0.452 with two and 0.480 with none)
     const int aut = mib <= (p.nsplit > 1 ? 768 : 320) ? 4 : mib <= 768 ? 2 : mib <= 1536 ? 1 : 0;
@@ -1897,4 +1899,134 @@ int smx_gate_blend_backward(const float* g3, const float* a, const float* v, con
   return SMX_OK;
 }
 
+// ---- 2-byte activations (bf16 / fp16 x, y, g, grad_x) ---------------------------------------------------------------
+// Replaces: reference fft_tensor/spectral_layers.py:88 (fft), :94-109 (filter), :112-116 (ifft, bias) and their autograd
+// backward for half-precision activations (the reference's torch.fft refuses bf16 and takes fp16 for powers of two only).
+// Same plan, launches, work items and summation order as the f32 entries; only the streaming kernels' row I/O differs
+// (k_fused_io / k_split_a_io / k_split_b_io), so the outputs are the f32 outputs rounded once (include/smx.h).
+static bool io_native(const Plan& p) {
+  return p.path == SMX_PATH_DECIMATED && p.groups == 1 && !p.fs && !p.full8;
+}
+static int io_check(int io) {
+  if (io != SMX_IO_F32 && io != SMX_IO_BF16 && io != SMX_IO_F16)
+    return fail(SMX_ERR_INVALID, "io must be SMX_IO_F32, SMX_IO_BF16 or SMX_IO_F16, got %d", io);
+  return SMX_OK;
+}
+
+int smx_io_supported(int B, int N, int D, int F, int io) {
+  if (io_check(io) || check_shape(B, N, D, F)) return 0;
+  if (io == SMX_IO_F32) return 1;
+  return io_native(make_plan(layer_shape(B, N, D, F))) ? 1 : 0;
+}
+
+int smx_forward_io(const void* x, const float* w_re, const float* w_im, const float* bias, void* y,
+                   float* xk_save, void* workspace, size_t workspace_bytes, int B, int N, int D, int F,
+                   int conj_w, float dropout_p, const void* rng_state, float* filter_pack, void* stream, int io) {
+  if (int rc = io_check(io)) return rc;
+  if (io == SMX_IO_F32)
+    return smx_forward_dropout((const float*)x, w_re, w_im, bias, (float*)y, xk_save, workspace, workspace_bytes, B, N,
+                               D, F, conj_w, dropout_p, rng_state, filter_pack, stream);
+  if (int rc = check_shape(B, N, D, F)) return rc;
+  const Shape h = layer_shape(B, N, D, F);
+  DropCfg dc;
+  if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
+  const bool pack_ready = (conj_w & SMX_FILTER_PACK_READY) != 0;
+  conj_w &= 1;
+  if (pack_ready && !filter_pack) return fail(SMX_ERR_INVALID, "SMX_FILTER_PACK_READY without filter_pack");
+  if (!x || !w_re || !w_im || !y) return fail(SMX_ERR_INVALID, "x, w_re, w_im, y must be non-NULL");
+  if (((uintptr_t)x | (uintptr_t)y) & 3) return fail(SMX_ERR_INVALID, "2-byte x and y must be 4-byte aligned");
+  if ((uintptr_t)xk_save & 15) return fail(SMX_ERR_INVALID, "xk_save must be 16-byte aligned");
+  const Plan p = make_plan(h);
+  if (!io_native(p))
+    return fail(SMX_ERR_UNSUPPORTED, "no 2-byte I/O on this plan (smx_io_supported): widen the input and call "
+                "smx_forward_dropout");
+  hipStream_t s = (hipStream_t)stream;
+  const Ws w = ws_layout(p, B, N, D);
+  if (p.nsplit > 1) if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
+  TableRef t;
+  if (int rc = get_tables(N, &t, s)) return rc;
+  char* ws = (char*)workspace;
+  DecimArgs a = decim_args(p, t, h, ws, w, 2);
+  a.in = (const float*)x; a.out = (float*)y;                 // 2-byte rows: read by the k_*_io kernels only
+  a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.bias = bias; a.fa.conj_w = conj_w;
+  a.fa.xk_out = xk_save;
+  set_drop(a, dc);
+  if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F,
+                           pack_ready ? filter_pack : nullptr, pack_ready ? nullptr : filter_pack, s))
+    return rc;
+  if (p.nsplit == 1) {
+    if (workspace && workspace_bytes >= w.total && !((uintptr_t)workspace & 255) &&
+        sync_words(B, D) * sizeof(unsigned) <= SYNC_BYTES)
+      a.sync = (unsigned*)(ws + w.sync);
+    HIP_TRY(launch_fused_io(a, p.nb, 0, io, s));
+  } else {
+    HIP_TRY(launch_split_a_io(a, p.nb, false, io, s));
+    HIP_TRY(launch_split_f(a, p.nb, 0, s));
+    HIP_TRY(launch_split_b_io(a, p.nb, true, io, s));
+  }
+  return SMX_OK;
+}
+
+int smx_backward_io(const void* g, const float* xk, const float* w_re, const float* w_im, void* grad_x,
+                    float* gw_re, float* gw_im, float* gbias, void* workspace, size_t workspace_bytes, int B,
+                    int N, int D, int F, int phases, float dropout_p, const void* rng_state,
+                    const float* filter_pack, void* stream, int io) {
+  if (int rc = io_check(io)) return rc;
+  if (io == SMX_IO_F32)
+    return smx_backward_dropout((const float*)g, xk, w_re, w_im, (float*)grad_x, gw_re, gw_im, gbias, workspace,
+                                workspace_bytes, B, N, D, F, phases, dropout_p, rng_state, filter_pack, stream);
+  if (int rc = check_shape(B, N, D, F)) return rc;
+  const Shape h = layer_shape(B, N, D, F);
+  DropCfg dc;
+  if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
+  if (!g || !w_re || !w_im) return fail(SMX_ERR_INVALID, "g, w_re, w_im must be non-NULL");
+  phases &= ~SMX_PHASE_SYNC_CLEAN;              // (no folded reduction here: the sync area is not used)
+  if (phases < 1 || phases > 7) return fail(SMX_ERR_INVALID, "phases must be a combination of 1, 2, 4");
+  if ((phases & SMX_PHASE_INVERSE) && !grad_x) return fail(SMX_ERR_INVALID, "grad_x is NULL");
+  const bool want_w = gw_re || gw_im || gbias;
+  if (want_w && !(gw_re && gw_im && gbias)) return fail(SMX_ERR_INVALID, "gw_re, gw_im, gbias must be given together");
+  if (((uintptr_t)g | (uintptr_t)grad_x) & 3) return fail(SMX_ERR_INVALID, "2-byte g and grad_x must be 4-byte aligned");
+  if ((uintptr_t)xk & 15) return fail(SMX_ERR_INVALID, "xk must be 16-byte aligned");
+  const Plan p = make_plan(h);
+  if (!io_native(p))
+    return fail(SMX_ERR_UNSUPPORTED, "no 2-byte I/O on this plan (smx_io_supported): widen g and call "
+                "smx_backward_dropout");
+  if ((want_w || dc.thr) && !xk && p.k > 0) return fail(SMX_ERR_INVALID, "xk (saved spectrum) is NULL");
+  hipStream_t s = (hipStream_t)stream;
+  const Ws w = ws_layout(p, B, N, D);
+  if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
+  TableRef t;
+  if (int rc = get_tables(N, &t, s)) return rc;
+  char* ws = (char*)workspace;
+  const bool do_spec = phases & SMX_PHASE_SPECTRUM, do_inv = phases & SMX_PHASE_INVERSE;
+  const bool do_par = (phases & SMX_PHASE_PARAMS) && want_w;
+  DecimArgs a = decim_args(p, t, h, ws, w, 2);
+  a.in = (const float*)g; a.out = (float*)grad_x;            // 2-byte rows: read by the k_*_io kernels only
+  a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.conj_w = 1;
+  a.fa.xk_in = xk; a.fa.pslab = (float*)(ws + w.slab); a.fa.gb_part = (float*)(ws + w.gbp);
+  set_drop(a, dc);
+  const int mode = (want_w || dc.thr) ? 1 : 0;                // (the mask is applied by the mode-1 load)
+  if (do_spec)
+    if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F, filter_pack, nullptr, s)) return rc;
+  if (do_spec && do_inv && p.nsplit == 1) {
+    HIP_TRY(launch_fused_io(a, p.nb, mode, io, s));
+  } else {
+    if (do_spec) {
+      if (p.nsplit == 1) {             // forward half + filter in one launch, S parked in the workspace
+        DecimArgs sp = a;
+        sp.out = nullptr;
+        HIP_TRY(launch_fused_io(sp, p.nb, mode, io, s));
+      } else {
+        HIP_TRY(launch_split_a_io(a, p.nb, true, io, s));
+        HIP_TRY(launch_split_f(a, p.nb, mode, s));
+      }
+    }
+    if (do_inv) HIP_TRY(launch_split_b_io(a, p.nb, false, io, s));
+  }
+  if (do_par)
+    HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, B, D, F, p.k, s));
+  return SMX_OK;
+}
+
 }  // extern "C"
+

@@ -86,8 +86,8 @@ __device__ __forceinline__ void load_stats(const cf* __restrict__ sb, const Geom
 // instructions after the burst: the whole memory latency exposed once per tile).
 // DROP (backward launches): the tile is g, multiplied by the dropout mask of the forward pass as it
 // is moved into the working registers.  pj = this thread's pair index inside a row, (d >> 1).
-template <int NB, bool LN, bool DROP, bool PAD, bool LAST>
-__device__ __forceinline__ void forward_tile(TState<NB>& st, cf* E, const RowBuf& xb,
+template <int NB, bool LN, bool DROP, bool PAD, bool LAST, class XB>
+__device__ __forceinline__ void forward_tile(TState<NB>& st, cf* E, const XB& xb,
                                              const DecimArgs& a, int t, int j, int r, int rn, cf (&nx)[16],
                                              cf (&ns)[LN ? 16 : 1], const LnLoad* ln, Drop dr, unsigned pj) {
   const Geom& g = a.g;
@@ -125,8 +125,8 @@ __device__ __forceinline__ void forward_tile(TState<NB>& st, cf* E, const RowBuf
 }
 
 // forward half: accumulate residues [rbeg, rbeg+cnt) (visited in rotated order) into st.acc.
-template <int NB, bool LN = false, bool DROP = false, bool PAD = false>
-__device__ __forceinline__ void forward_loop(TState<NB>& st, cf* lds, const RowBuf& xb,
+template <int NB, bool LN = false, bool DROP = false, bool PAD = false, class XB>
+__device__ __forceinline__ void forward_loop(TState<NB>& st, cf* lds, const XB& xb,
                                              const DecimArgs& a, int t, int j, int rbeg, int cnt,
                                              int rot, const LnLoad* ln = nullptr, Drop dr = Drop{},
                                              unsigned pj = 0) {
@@ -164,10 +164,10 @@ __device__ __forceinline__ void forward_loop(TState<NB>& st, cf* lds, const RowB
 // Cache, was measured: no gain inside a fwd+bwd sequence -- tools/probe_mall.hip shows re-reads at
 // HBM rate whatever the footprint.)
 // DROP (forward launches): dropout of the tile before the residual add and the store.
-template <int NB, bool RES, bool DROP, bool PAD, bool LAST>
-__device__ __forceinline__ void inverse_tile(TState<NB>& st, cf* E, const RowBuf& yb, const DecimArgs& a,
+template <int NB, bool RES, bool DROP, bool PAD, bool LAST, class YB, class RB>
+__device__ __forceinline__ void inverse_tile(TState<NB>& st, cf* E, const YB& yb, const DecimArgs& a,
                                              int t, int j, int r, int rn,
-                                             const RowBuf& res, cf (&rx)[RES ? 16 : 1], Drop dr,
+                                             const RB& res, cf (&rx)[RES ? 16 : 1], Drop dr,
                                              unsigned pj) {
   const Geom& g = a.g;
   inv_phase1<NB, true>(st, a.bt + (size_t)r * BT_STRIDE, E, t, j);
@@ -196,10 +196,10 @@ __device__ __forceinline__ void inverse_tile(TState<NB>& st, cf* E, const RowBuf
   store_rows<PAD>(yb, r, st.v, a.st_plain);
 }
 
-template <int NB, bool RES = false, bool DROP = false, bool PAD = false>
-__device__ __forceinline__ void inverse_loop(TState<NB>& st, cf* lds, const RowBuf& yb,
+template <int NB, bool RES = false, bool DROP = false, bool PAD = false, class YB, class RB>
+__device__ __forceinline__ void inverse_loop(TState<NB>& st, cf* lds, const YB& yb,
                                              const DecimArgs& a, int t, int j, int rbeg,
-                                             int cnt, int rot, const RowBuf& res, Drop dr = Drop{},
+                                             int cnt, int rot, const RB& res, Drop dr = Drop{},
                                              unsigned pj = 0) {
   const Geom& g = a.g;
   int r = rbeg + rot;
@@ -829,6 +829,98 @@ __global__ __launch_bounds__(TPB, 2) void k_split_b(const DecimArgs a) {
                                    (unsigned)((valid ? d : g.D - 2) >> 1));
 }
 
+// ---- 2-byte activations: bf16 / fp16 x, y, g, grad_x (IO = SMX_IO_BF16 / SMX_IO_F16) ------------------------------
+// k_fused / k_split_a / k_split_b with the streamed rows in 2-byte elements (RowBufIO, smx_launch.h) and everything
+// else unchanged: the same work items and residue rotation (wg_map -- the order in which a workgroup accumulates
+// its residues), the same tile arithmetic, f32 spectra.  The results are therefore the f32 kernels' results on the
+// widened input, rounded once at the store.  Only the configurations smx_api routes here
+// exist: no zero-padded rows, no accumulating band groups, no folded parameter-gradient reduction (the half
+// backward reduces in k_gradw, bitwise the same sums as gradw_tail).
+template <int NB, int MODE, int IO, bool DROP>
+__global__ __launch_bounds__(TPB, 2) void k_fused_io(const DecimArgs a) {
+  SMX_LDS_DECL;
+  const Geom& g = a.g;
+  const int tid = threadIdx.x, j = tid & 15, t = tid >> 4;
+  const int ndt = (g.D + DT - 1) / DT;
+  const WgItem w = wg_map(a.bid0 + blockIdx.x, g.B, ndt, 1, g.L, a.placement);
+  const int b = w.b, d = w.dt * DT + 2 * j, rot = w.rot;
+  const bool valid = d < g.D;
+  const RowBufIO<IO> xb = row_buf_io<IO>(a.in, b, g, t, valid ? d : g.D - 2);
+  if constexpr (MODE == 0) {               // as k_fused: the sync area of this workspace left zero
+    if (a.sync != nullptr && a.bid0 + (int)blockIdx.x == 0)
+      for (int i = tid; i <= g.B * ndt; i += TPB) a.sync[i] = 0u;
+  }
+  TState<NB> st;
+  zero_acc<NB>(st);
+  if constexpr (NB == 1) prefetch_io<NB, MODE>(st, g, a.fa, b, d, valid, t);
+  WPre wp;
+  constexpr bool STAGE_W = NB == 1 && MODE != 2;
+  if constexpr (STAGE_W) prefetch_w(wp, g, a.fa.w_re, a.fa.w_im, w.dt * DT, tid);
+  Drop dr{};
+  if constexpr (DROP) dr = make_drop(a, b);
+  const unsigned pj = (unsigned)((valid ? d : g.D - 2) >> 1);
+  forward_loop<NB, false, DROP && MODE == 1, false>(st, lds, xb, a, t, j, 0, g.L, rot, nullptr, dr, pj);
+  unpack_filter<NB, MODE, false>(st, lds, g, a.fa, b, d, valid, t, j, STAGE_W ? &wp : nullptr);
+  if (a.out == nullptr) {
+    if constexpr (NB == 1) store_io<NB, MODE>(st, g, a.fa, b, d, valid, t);
+    if (a.ws_s != nullptr) {               // phase-split backward: the filtered spectrum parked for k_split_b_io
+      cf* s = a.ws_s + (size_t)(b * ndt + w.dt) * (16 * NB * TPB);
+#pragma unroll
+      for (int sl = 0; sl < 16 * NB; ++sl) s[sl * TPB + tid] = st.acc[sl];
+    }
+    return;
+  }
+  __syncthreads();
+  const RowBufIO<IO> yb = row_buf_io<IO>(a.out, b, g, t, d, valid);
+  inverse_loop<NB, false, DROP && MODE == 0, false>(st, lds, yb, a, t, j, 0, g.L, rot, yb, dr, pj);
+  if constexpr (NB == 1) store_io<NB, MODE>(st, g, a.fa, b, d, valid, t);
+}
+
+template <int NB, int IO, bool DROP>
+__global__ __launch_bounds__(TPB, 2) void k_split_a_io(const DecimArgs a) {
+  SMX_LDS_DECL;
+  const Geom& g = a.g;
+  const int tid = threadIdx.x, j = tid & 15, t = tid >> 4;
+  const int ndt = (g.D + DT - 1) / DT;
+  const WgItem w = wg_map(a.bid0 + blockIdx.x, g.B, ndt, a.nsplit, a.lc, a.placement);
+  const int c = w.c, b = w.b, wg = b * ndt + w.dt, d = w.dt * DT + 2 * j;
+  const bool valid = d < g.D;
+  const int rbeg = c * a.lc, cnt = min(a.lc, g.L - rbeg);
+  const RowBufIO<IO> xb = row_buf_io<IO>(a.in, b, g, t, valid ? d : g.D - 2);
+  const int rot = w.rot % cnt;
+  TState<NB> st;
+  zero_acc<NB>(st);
+  Drop dr{};
+  if constexpr (DROP) dr = make_drop(a, b);
+  forward_loop<NB, false, DROP, false>(st, lds, xb, a, t, j, rbeg, cnt, rot, nullptr, dr,
+                                       (unsigned)((valid ? d : g.D - 2) >> 1));
+  cf* z = a.ws_z + ((size_t)wg * a.nsplit + c) * (16 * NB * TPB);
+#pragma unroll
+  for (int sl = 0; sl < 16 * NB; ++sl) z[sl * TPB + tid] = st.acc[sl];
+}
+
+template <int NB, int IO, bool DROP>
+__global__ __launch_bounds__(TPB, 2) void k_split_b_io(const DecimArgs a) {
+  SMX_LDS_DECL;
+  const Geom& g = a.g;
+  const int tid = threadIdx.x, j = tid & 15, t = tid >> 4;
+  const int ndt = (g.D + DT - 1) / DT;
+  const WgItem w = wg_map(a.bid0 + blockIdx.x, g.B, ndt, a.nsplit, a.lc, a.placement);
+  const int c = w.c, b = w.b, wg = b * ndt + w.dt, d = w.dt * DT + 2 * j;
+  const bool valid = d < g.D;
+  const int rbeg = c * a.lc, cnt = min(a.lc, g.L - rbeg);
+  const int rot = w.rot % cnt;
+  TState<NB> st;
+  const cf* s = a.ws_s + (size_t)wg * (16 * NB * TPB);
+#pragma unroll
+  for (int sl = 0; sl < 16 * NB; ++sl) st.acc[sl] = s[sl * TPB + tid];
+  const RowBufIO<IO> yb = row_buf_io<IO>(a.out, b, g, t, d, valid);
+  Drop dr{};
+  if constexpr (DROP) dr = make_drop(a, b);
+  inverse_loop<NB, false, DROP, false>(st, lds, yb, a, t, j, rbeg, cnt, rot, yb, dr,
+                                       (unsigned)((valid ? d : g.D - 2) >> 1));
+}
+
 // ---- launchers ---------------------------------------------------------------------------------
 #ifdef SMX_MINI
 // development only (never linked): the BASELINE kernels alone, for a quick look at their ISA --
@@ -1038,6 +1130,57 @@ hipError_t launch_split_b(const DecimArgs& a, int nb, bool drop_out, hipStream_t
     } else if (nb == 1) hipLaunchKernelGGL((k_split_b<1>), grid, block, 0, s, r);
     else if (nb == 2) hipLaunchKernelGGL((k_split_b<2>), grid, block, 0, s, r);
     else hipLaunchKernelGGL((k_split_b<4>), grid, block, 0, s, r);
+  });
+}
+
+// 2-byte activations: one instance per (bands, mode, element type, dropout); the f32 launchers above are untouched
+template <int NB, int IO>
+static void launch_fused_io_t(const DecimArgs& r, int mode, dim3 grid, hipStream_t s) {
+  const dim3 block(TPB);
+  const bool drop = r.drop_thr != 0;
+  if (mode == 0 && drop) hipLaunchKernelGGL((k_fused_io<NB, 0, IO, true>), grid, block, 0, s, r);
+  else if (mode == 0) hipLaunchKernelGGL((k_fused_io<NB, 0, IO, false>), grid, block, 0, s, r);
+  else if (drop) hipLaunchKernelGGL((k_fused_io<NB, 1, IO, true>), grid, block, 0, s, r);
+  else hipLaunchKernelGGL((k_fused_io<NB, 1, IO, false>), grid, block, 0, s, r);
+}
+template <int IO>
+static void launch_fused_io_nb(const DecimArgs& r, int nb, int mode, dim3 grid, hipStream_t s) {
+  if (nb == 4) launch_fused_io_t<4, IO>(r, mode, grid, s);
+  else if (nb == 2) launch_fused_io_t<2, IO>(r, mode, grid, s);
+  else launch_fused_io_t<1, IO>(r, mode, grid, s);
+}
+hipError_t launch_fused_io(const DecimArgs& a, int nb, int mode, int io, hipStream_t s) {
+  return for_rounds(a, n_wg(a), [&](const DecimArgs& r, dim3 grid) {
+    if (io == 1) launch_fused_io_nb<1>(r, nb, mode, grid, s);
+    else launch_fused_io_nb<2>(r, nb, mode, grid, s);
+  }, nb == 4);
+}
+template <int IO, bool DROP>
+static void launch_split_a_io_t(const DecimArgs& r, int nb, dim3 grid, hipStream_t s) {
+  if (nb == 4) hipLaunchKernelGGL((k_split_a_io<4, IO, DROP>), grid, dim3(TPB), 0, s, r);
+  else if (nb == 2) hipLaunchKernelGGL((k_split_a_io<2, IO, DROP>), grid, dim3(TPB), 0, s, r);
+  else hipLaunchKernelGGL((k_split_a_io<1, IO, DROP>), grid, dim3(TPB), 0, s, r);
+}
+hipError_t launch_split_a_io(const DecimArgs& a, int nb, bool drop_in, int io, hipStream_t s) {
+  return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
+    const bool dr = drop_in && r.drop_thr != 0;
+    if (io == 1) { if (dr) launch_split_a_io_t<1, true>(r, nb, grid, s); else launch_split_a_io_t<1, false>(r, nb, grid, s); }
+    else if (dr) launch_split_a_io_t<2, true>(r, nb, grid, s);
+    else launch_split_a_io_t<2, false>(r, nb, grid, s);
+  });
+}
+template <int IO, bool DROP>
+static void launch_split_b_io_t(const DecimArgs& r, int nb, dim3 grid, hipStream_t s) {
+  if (nb == 4) hipLaunchKernelGGL((k_split_b_io<4, IO, DROP>), grid, dim3(TPB), 0, s, r);
+  else if (nb == 2) hipLaunchKernelGGL((k_split_b_io<2, IO, DROP>), grid, dim3(TPB), 0, s, r);
+  else hipLaunchKernelGGL((k_split_b_io<1, IO, DROP>), grid, dim3(TPB), 0, s, r);
+}
+hipError_t launch_split_b_io(const DecimArgs& a, int nb, bool drop_out, int io, hipStream_t s) {
+  return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
+    const bool dr = drop_out && r.drop_thr != 0;
+    if (io == 1) { if (dr) launch_split_b_io_t<1, true>(r, nb, grid, s); else launch_split_b_io_t<1, false>(r, nb, grid, s); }
+    else if (dr) launch_split_b_io_t<2, true>(r, nb, grid, s);
+    else launch_split_b_io_t<2, false>(r, nb, grid, s);
   });
 }
 

@@ -114,6 +114,11 @@ hipError_t launch_fused_block(const DecimArgs& a, int nb, hipStream_t s);
 hipError_t launch_split_a(const DecimArgs& a, int nb, bool drop_in, hipStream_t s);
 hipError_t launch_split_f(const DecimArgs& a, int nb, int mode, hipStream_t s);
 hipError_t launch_split_b(const DecimArgs& a, int nb, bool drop_out, hipStream_t s);
+// the same three streaming launches with 2-byte x / y (io = SMX_IO_BF16 or SMX_IO_F16; a.in / a.out point at
+// bf16 / fp16 rows): no zero-padded rows, no band groups, no folded parameter-gradient reduction
+hipError_t launch_fused_io(const DecimArgs& a, int nb, int mode, int io, hipStream_t s);
+hipError_t launch_split_a_io(const DecimArgs& a, int nb, bool drop_in, int io, hipStream_t s);
+hipError_t launch_split_b_io(const DecimArgs& a, int nb, bool drop_out, int io, hipStream_t s);
 
 // elementwise dropout for the plans without a fused epilogue (direct path): out = mask * scale * in
 hipError_t launch_dropout_rows(const float* in, float* out, int B, long long row_elems, unsigned thr,

@@ -53,7 +53,7 @@ __device__ __forceinline__ WgItem wg_map(int bid, int B, int ndt, int nsplit, in
 // 16 stores of a tile somewhere in the optimiser (llvm-objdump of the shipped kernel: 4 x `nt`, 12 x plain).
 // Zero-padded rows (PAD: x / y hold R < N rows): the row pitch moves into the per-thread offset, and the buffer's
 // range check (offset >= R D 4 bytes: loads return 0, stores are dropped) is the predicate.
-// Needs R D 4 < 2^31 (make_plan sends larger batch rows to the direct plan).
+// Needs R D 4 < 2^31 (make_plan sends larger batch rows to the direct plan; R D 2 for the 2-byte tensors below).
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 constexpr int BUF_NT = 2;          // cache policy operand of the buffer intrinsics: slc = `nt` on gfx950
@@ -109,12 +109,94 @@ __device__ __forceinline__ void store_rows(const RowBuf& rb, int r, const cf (&v
     else __builtin_amdgcn_raw_buffer_store_b64(w, rb.rs, vo, so, BUF_NT);
   }
 }
+// ---- 2-byte streamed tensors (IO = SMX_IO_BF16 / SMX_IO_F16, the k_*_io kernels) ----------------------------------
+// The same tile walk with a packed channel pair per row in ONE dword: buffer_load / buffer_store_dword, row pitch D 2
+// bytes, range R D 2 bytes.  Loads widen exactly (bf16: the high half of an f32; fp16: v_cvt_f32_f16), stores round
+// once, to nearest even: bf16 by the plain cast (v_cvt_pk_bf16_f32 -- a NaN stays a NaN), fp16 by the IEEE
+// conversion (v_cvt_f16_f32: overflow to +-inf; never the round-toward-zero v_cvt_pkrtz) -- the results of
+// torch.Tensor.to(dtype) on the f32 values, bit for bit.
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+template <int IO>
+struct RowBufIO {
+  __amdgpu_buffer_rsrc_t rs;       // batch row b: base + b R D elements, R D 2 bytes
+  unsigned vo;                     // (t L D + d) 2
+  unsigned su;                     // 16 L D 2
+  unsigned rowb;                   // D 2
+};
+template <int IO>
+__device__ __forceinline__ RowBufIO<IO> row_buf_io(const void* base, int b, const Geom& g, int t, int d,
+                                                   bool in_range = true) {
+  RowBufIO<IO> rb;
+  char* row0 = const_cast<char*>(static_cast<const char*>(base)) + (size_t)b * g.R * g.D * 2;
+  rb.rs = __builtin_amdgcn_make_buffer_rsrc(row0, 0, (int)((unsigned)g.R * (unsigned)g.D * 2u), 0x00020000);
+  rb.rowb = (unsigned)g.D * 2u;
+  rb.vo = in_range ? ((unsigned)t * (unsigned)g.L * (unsigned)g.D + (unsigned)d) * 2u : 0x80000000u;
+  rb.su = 16u * (unsigned)g.L * rb.rowb;
+  return rb;
+}
+template <int IO>
+__device__ __forceinline__ cf widen2(unsigned w) {
+  if constexpr (IO == 1) {
+    return mk(__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xffff0000u));
+  } else {
+    const f16x2_t h = __builtin_bit_cast(f16x2_t, w);
+    return mk((float)h.x, (float)h.y);
+  }
+}
+template <int IO>
+__device__ __forceinline__ unsigned narrow2(float fx, float fy) {
+  if constexpr (IO == 1) {
+    bf16x2_t h;
+    h.x = (__bf16)fx; h.y = (__bf16)fy;
+    return __builtin_bit_cast(unsigned, h);
+  } else {
+    // the f32 values first: left to itself the compiler folds a preceding multiply (the dropout scale) into the
+    // conversion (v_fma_mixlo_f16 -- one rounding instead of the f32 path's two: measured 80 of 0.5 M elements off)
+    asm("" : "+v"(fx));
+    asm("" : "+v"(fy));
+    f16x2_t h;
+    h.x = (_Float16)fx; h.y = (_Float16)fy;
+    return __builtin_bit_cast(unsigned, h);
+  }
+}
+template <int U0, int CNT, bool PAD, int IO>
+__device__ __forceinline__ void load_rows(const RowBufIO<IO>& rb, int r, cf (&v)[16]) {
+  const unsigned vr = rb.vo + (unsigned)r * rb.rowb;
+#pragma unroll
+  for (int u = U0; u < U0 + CNT; ++u) {
+    const unsigned w = PAD ? __builtin_amdgcn_raw_buffer_load_b32(rb.rs, vr + (unsigned)u * rb.su, 0, BUF_NT)
+                           : __builtin_amdgcn_raw_buffer_load_b32(rb.rs, vr, (unsigned)u * rb.su, BUF_NT);
+    const cf e = widen2<IO>(w);
+    float fx = e.x, fy = e.y;
+    asm("" : "+v"(fx));
+    asm("" : "+v"(fy));
+    v[u] = mk(fx, fy);
+  }
+}
+// plain: as store_rows above; DecimArgs::st_plain is chosen from the output's bytes (smx_api decim_args)
+template <bool PAD, int IO>
+__device__ __forceinline__ void store_rows(const RowBufIO<IO>& rb, int r, const cf (&v)[16], int plain) {
+  const unsigned vr = rb.vo + (unsigned)r * rb.rowb;
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    const unsigned w = narrow2<IO>(v[u].x, v[u].y);
+    const unsigned vo = PAD ? vr + (unsigned)u * rb.su : vr, so = PAD ? 0u : (unsigned)u * rb.su;
+    if (u < 4 && u < plain) __builtin_amdgcn_raw_buffer_store_b32(w, rb.rs, vo, so, 0);
+    else __builtin_amdgcn_raw_buffer_store_b32(w, rb.rs, vo, so, BUF_NT);
+  }
+}
 #else
 // host pass of hipcc: the kernels' bodies are parsed but never emitted -- declarations only
 struct RowBuf { unsigned vo, su, rowb; };
 __device__ RowBuf row_buf(const float* row0, const Geom& g, int t, int d, bool in_range = true);
 template <int U0, int CNT, bool PAD> __device__ void load_rows(const RowBuf& rb, int r, cf (&v)[16]);
 template <bool PAD> __device__ void store_rows(const RowBuf& rb, int r, const cf (&v)[16], int plain);
+template <int IO> struct RowBufIO { unsigned vo, su, rowb; };
+template <int IO>
+__device__ RowBufIO<IO> row_buf_io(const void* base, int b, const Geom& g, int t, int d, bool in_range = true);
+template <int U0, int CNT, bool PAD, int IO> __device__ void load_rows(const RowBufIO<IO>& rb, int r, cf (&v)[16]);
+template <bool PAD, int IO> __device__ void store_rows(const RowBufIO<IO>& rb, int r, const cf (&v)[16], int plain);
 #endif
 
 // ---- launch helpers ----------------------------------------------------------------------------

@@ -30,6 +30,22 @@ def _under_forward_options(backward):
     return wrapped
 
 
+# element type of the streamed x / y / g / grad_x (include/smx.h SMX_IO_*): arithmetic stays fp32 on every one
+_IO = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
+def _require_gpu_io(name: str, t: torch.Tensor) -> None:
+    """fp32, bf16 or fp16 on a ROCm device (the activations spectral_mix takes)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise RuntimeError(
+            f"{name} is on {t.device}: the MI355X spectral-mixing path has no CPU implementation "
+            f"(move the module and its input to a ROCm device)")
+    if t.dtype not in _IO:
+        raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype} (the kernels compute in fp32)")
+
+
 def _require_gpu_f32(name: str, t: torch.Tensor) -> None:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
@@ -229,11 +245,13 @@ def _check_p(p: float) -> float:
 
 
 def forward_raw(x, w_re, w_im, bias, *, conj_w=False, save_spectrum=False, dropout_p=0.0, rng=None,
-                pack=None, pack_ready=False, ws=None):
+                pack=None, pack_ready=False, ws=None, io=0):
     """y, xk = smx_forward[_dropout](...).  x (B,N,D) contiguous f32 on GPU; returns xk (B,k,D) c64 or
     None.  rng: the int64[2] device tensor from DropoutState.next() when dropout_p > 0.  pack: (k,D)
     complex64 tensor that receives the packed filter (hand it to backward_raw to skip its packing launch);
-    pack_ready=True: `pack` was filled by an earlier call with the same weights, do not pack again."""
+    pack_ready=True: `pack` was filled by an earlier call with the same weights, do not pack again.
+    io: element type of x and y (SMX_IO_BF16 / SMX_IO_F16: bf16 / fp16 x, 4-byte aligned, on a plan with
+    _lib.io_supported; y comes back in x's dtype, xk stays complex64)."""
     B, N, D = x.shape
     F = w_re.shape[1]
     k = num_bins(N, F)
@@ -243,6 +261,13 @@ def forward_raw(x, w_re, w_im, bias, *, conj_w=False, save_spectrum=False, dropo
     if ws is None:
         ws = _workspace(x.device, _ws_bytes(B, N, D, F))
     with _on_device(x.device):
+        if io:
+            _lib.check(_lib.lib().smx_forward_io(
+                x.data_ptr(), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(xk),
+                _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F,
+                int(bool(conj_w)) | (2 if pack_ready else 0), float(dropout_p), _ptr(rng), _ptr(pack),
+                _stream(x.device), int(io)))
+            return y, xk
         _lib.check(_lib.lib().smx_forward_dropout(
             x.data_ptr(), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(xk),
             _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F,
@@ -256,11 +281,12 @@ PHASE_SYNC_CLEAN = 8
 
 
 def backward_raw(g, xk, w_re, w_im, *, want_x=True, want_w=True, phases=PHASE_ALL, grad_x=None,
-                 flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, sync_clean=False):
+                 flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, sync_clean=False, io=0):
     """Runs smx_backward.  Returns (grad_x, flat) where flat = [gw_re | gw_im | gbias] fp32.
     `ws`: workspace of an earlier phase (a call made on another stream must not pick that stream's), or the
     workspace the forward call of the same autograd node used -- then `sync_clean=True` tells the library that
-    its flag words are zero (include/smx.h, SMX_PHASE_SYNC_CLEAN) and it skips clearing them."""
+    its flag words are zero (include/smx.h, SMX_PHASE_SYNC_CLEAN) and it skips clearing them.
+    io: element type of g and grad_x, as in forward_raw (the parameter gradients stay fp32)."""
     B, N, D = g.shape
     F = w_re.shape[1]
     # with dropout the direct plan stages g * mask in grad_x during the SPECTRUM phase
@@ -279,6 +305,12 @@ def backward_raw(g, xk, w_re, w_im, *, want_x=True, want_w=True, phases=PHASE_AL
         phases |= PHASE_SYNC_CLEAN
     _prepare(g.device, N)
     with _on_device(g.device):
+        if io:
+            _lib.check(_lib.lib().smx_backward_io(
+                g.data_ptr(), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(), _ptr(grad_x), _ptr(gw_re),
+                _ptr(gw_im), _ptr(gb), _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F, phases,
+                float(dropout_p), _ptr(rng), _ptr(pack), _stream(g.device), int(io)))
+            return grad_x, flat
         _lib.check(_lib.lib().smx_backward_dropout(
             g.data_ptr(), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(), _ptr(grad_x), _ptr(gw_re),
             _ptr(gw_im), _ptr(gb), _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F, phases,
@@ -324,8 +356,11 @@ class _SpectralMix(torch.autograd.Function):
         B, N, D = x.shape
         # backward runs on forward's workspace: the forward launch leaves its flag words zero (SYNC_CLEAN)
         ws = _workspace(x.device, _ws_bytes(B, N, D, w_re.shape[1]))
+        io = _IO[x.dtype]                                    # bf16 / fp16 x: plans with native 2-byte rows only
         y, xk = forward_raw(x, w_re, w_im, bias, save_spectrum=needs, dropout_p=dropout_p, rng=rng,
-                            pack=pack, ws=ws)
+                            pack=pack, ws=ws, io=io)
+        ctx.io = io
+        ctx.io_dtype = x.dtype
         ctx.ws = ws if needs else None
         ctx.sync = sync
         ctx.has_bias = bias is not None
@@ -340,14 +375,14 @@ class _SpectralMix(torch.autograd.Function):
     @_under_forward_options
     def backward(ctx, g):
         xk, w_re, w_im = ctx.saved_tensors
-        if g.dtype != torch.float32:
-            g = g.float()
+        if g.dtype != ctx.io_dtype:
+            g = g.to(ctx.io_dtype)
         g = _dense(g)
         D, F = w_re.shape
         want_x = ctx.needs_input_grad[0]
         want_w = any(ctx.needs_input_grad[1:4])
         sync = ctx.sync if (want_w and ctx.sync is not None and ctx.sync.active()) else None
-        dkw = dict(dropout_p=ctx.drop[0], rng=ctx.drop[1], pack=ctx.pack)
+        dkw = dict(dropout_p=ctx.drop[0], rng=ctx.drop[1], pack=ctx.pack, io=ctx.io)
         if sync is None:
             gx, flat = backward_raw(g, xk, w_re, w_im, want_x=want_x, want_w=want_w, ws=ctx.ws,
                                     sync_clean=ctx.ws is not None, **dkw)
@@ -377,8 +412,21 @@ def spectral_mix(x: torch.Tensor, weight_real: torch.Tensor, weight_imag: torch.
                  bias: Optional[torch.Tensor] = None, sync=None, dropout_p: float = 0.0,
                  drop_state: Optional[DropoutState] = None) -> torch.Tensor:
     """Functional form of SpectralMixingLayer.forward (learnable branch).  dropout_p > 0 applies the
-    training-mode dropout of the reference (:118) inside the same launches, masks from `drop_state`."""
-    _require_gpu_f32("x", x)
+    training-mode dropout of the reference (:118) inside the same launches, masks from `drop_state`.
+
+    x may be fp32, bf16 or fp16; y and grad_x come back in x's dtype.  The parameters are fp32 or x's dtype and are
+    read as fp32 (`.float()`, so autograd returns their gradients in their own dtype).  All arithmetic is fp32: the
+    result is the fp32 layer's on x.float(), rounded once to x's dtype -- by the kernels' stores where the plan has
+    native 2-byte rows (_lib.io_supported), by `.to(dtype)` after the fp32 op everywhere else."""
+    _require_gpu_io("x", x)
+    if x.dtype != torch.float32:
+        for name, t in (("weight_real", weight_real), ("weight_imag", weight_imag), ("bias", bias)):
+            if t is not None:
+                _require_gpu_io(name, t)
+                if t.dtype not in (torch.float32, x.dtype):
+                    raise TypeError(f"{name} must be float32 or {x.dtype} like x, got {t.dtype}")
+        return _spectral_mix_half(x, weight_real.float(), weight_imag.float(),
+                                  None if bias is None else bias.float(), sync, dropout_p, drop_state)
     _require_gpu_f32("weight_real", weight_real)
     _require_gpu_f32("weight_imag", weight_imag)
     if bias is not None:
@@ -424,6 +472,30 @@ def spectral_mix(x: torch.Tensor, weight_real: torch.Tensor, weight_imag: torch.
 
 
 _ODD_D_PAD_MIN = 1 << 18        # below this the literal kernels of the direct plan are launch-bound anyway
+
+_io_cache = _Memo()
+
+
+def _spectral_mix_half(x, w_re, w_im, bias, sync, dropout_p, drop_state):
+    """bf16 / fp16 x with fp32 parameters.  Native 2-byte rows where the plan has them (the single-launch and
+    residue-split plans with at most 512 bins); everywhere else the up-cast route x.float() -> fp32 op -> .to(dtype),
+    which is the same result by construction."""
+    if x.dim() != 3:
+        raise ValueError(f"expected x of shape (B, T, D), got {tuple(x.shape)}")
+    if w_re.shape != w_im.shape or w_re.dim() != 2 or w_re.shape[0] != x.shape[2]:
+        raise ValueError("weights must both be (D, num_filters)")
+    B, N, D = x.shape
+    F = w_re.shape[1]
+    native = x.numel() > 0 and _io_cache.get((B, N, D, F, x.dtype),
+                                            lambda: _lib.io_supported(B, N, D, F, _IO[x.dtype]))
+    if not native:
+        return spectral_mix(x.float(), w_re, w_im, bias, sync, dropout_p, drop_state).to(x.dtype)
+    dropout_p = _check_p(dropout_p)
+    if dropout_p > 0.0 and drop_state is None:
+        raise ValueError("dropout_p > 0 needs a DropoutState")
+    # _dense: contiguous and 16-byte aligned -- a view with a storage offset is copied before it reaches the library
+    return _SpectralMix.apply(_dense(x), _dense(w_re), _dense(w_im), _dense(bias), sync,
+                              dropout_p, drop_state, torch.is_grad_enabled())
 
 
 def block_forward_raw(x, ln_w, ln_b, eps, w_re, w_im, bias, *, save=True, dropout_p=0.0, rng=None,

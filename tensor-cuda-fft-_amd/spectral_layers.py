@@ -7,8 +7,10 @@ callers (`SpectralMLPBlock`, reference :135-190) keep working.  The arithmetic i
 it is the fused HIP path in csrc/ reached through the C ABI of include/smx.h.
 
 Documented deviations from the reference:
-  * inputs must be float32 on a ROCm device (the reference would run anywhere torch runs and
-    promote float64); anything else raises instead of silently taking a slower path;
+  * inputs must be float32, bfloat16 or float16 on a ROCm device (the reference would run anywhere torch runs and
+    promote float64); anything else raises instead of silently taking a slower path.  Half-precision
+    activations compute in fp32 and come back in their own dtype, an fp32 bias included (the reference
+    promotes fp16 + fp32 bias to fp32);
   * `learnable=False` returns the input itself (the reference computes ifft(fft(x)).real, which is
     x to 1.2e-7);
   * training-mode dropout (p > 0) is drawn inside the transform's launches from the library's
