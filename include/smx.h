@@ -277,6 +277,26 @@ int smx_conv_backward(const smx_shape* shape, const float* g, const float* x_spe
                       const float* h_im, const float* row_scale, float* grad_x, float* grad_h_re,
                       float* grad_h_im, float* grad_row_scale, void* workspace, size_t workspace_bytes,
                       void* stream);
+/* 2-byte activations of the convolution: smx_conv_forward_io / smx_conv_backward_io are smx_conv_forward /
+ * smx_conv_backward with x, y, g, grad_x in the element type `io` (SMX_IO_F32: exactly the f32 entries; SMX_IO_BF16,
+ * SMX_IO_F16, defined below).  Everything else keeps its f32 type and layout: h_re, h_im, row_scale, their gradients,
+ * x_spectra (same save_bytes) and the workspace (same size).  Arithmetic is f32: the input widens exactly on load,
+ * y / grad_x are rounded once at the store, to nearest even (a NaN stays a NaN, fp16 overflow goes to +-inf) -- each
+ * output equals the f32 entry's output on the widened input rounded to `io`, bit for bit; x_spectra and the gradients
+ * of h and row_scale equal the f32 entry's, bit for bit.
+ * Native 2-byte rows exist on the single-launch plan only (n_fft <= 2048, option "conv1" taking the shape:
+ * smx_conv_io_supported == 1).  Any other plan returns SMX_ERR_UNSUPPORTED: the caller widens the input itself and
+ * calls the f32 entry.  Pointers: x / y / g / grad_x 4-byte aligned for a 2-byte `io` (8 for SMX_IO_F32).
+ * Replaces: reference fft_lm/train_fixed_full.py:515-555 (rfft, response product, irfft, crop) and its autograd
+ * backward in bf16 / fp16 -- which the reference's torch.fft refuses (bf16) or runs in complex32 (fp16). */
+int smx_conv_io_supported(const smx_shape* shape, int io);
+int smx_conv_forward_io(const smx_shape* shape, const void* x, const float* h_re, const float* h_im,
+                        const float* row_scale, void* y, float* x_spectra, void* workspace,
+                        size_t workspace_bytes, int io, void* stream);
+int smx_conv_backward_io(const smx_shape* shape, const void* g, const float* x_spectra, const float* h_re,
+                         const float* h_im, const float* row_scale, void* grad_x, float* grad_h_re,
+                         float* grad_h_im, float* grad_row_scale, void* workspace, size_t workspace_bytes,
+                         int io, void* stream);
 
 /* The response the block hands to smx_conv_*, in one launch (reference fft_lm/train_fixed_full.py:511-513 k_freq,
  * :529 frequency gate, :540-551 cutoff mask):

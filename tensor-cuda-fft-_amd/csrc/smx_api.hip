@@ -1174,15 +1174,16 @@ int smx_conv_workspace_bytes(const smx_shape* shape, size_t* workspace_bytes, si
 }
 
 // t: the caller's TableRef -- the tables stay pinned until the entry point has enqueued its launches
+// elem: bytes per element of x / y / g / grad_x (4; 2 for smx_conv_forward_io / smx_conv_backward_io)
 static int conv_args(const Shape& h, const Plan& p, const ConvWs& w, void* workspace, size_t workspace_bytes,
                      const float* h_re, const float* h_im, const float* row_scale, hipStream_t s, TableRef& t,
-                     DecimArgs* out) {
+                     DecimArgs* out, int elem = 4) {
   if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 255))
     return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes", w.total);
   if (!h_re || !h_im) return fail(SMX_ERR_INVALID, "h_re, h_im must be non-NULL");
   if (int rc = get_tables(h.N, &t, s)) return rc;
   Ws dummy;
-  DecimArgs a = decim_args(p, t, h, (char*)workspace, dummy);
+  DecimArgs a = decim_args(p, t, h, (char*)workspace, dummy, elem);
   a.ws_z = a.ws_zs = a.ws_s = nullptr;
   a.ws_f = (cf*)((char*)workspace + w.fs);
   a.nsplit = p.fs_nsplit; a.lc = p.fs_lc;
@@ -2025,6 +2026,72 @@ int smx_backward_io(const void* g, const float* xk, const float* w_re, const flo
   }
   if (do_par)
     HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, B, D, F, p.k, s));
+  return SMX_OK;
+}
+
+// ---- 2-byte activations of the convolution (bf16 / fp16 x, y, g, grad_x) -------------------------------------------
+// Replaces: reference fft_lm/train_fixed_full.py:515-555 and its autograd backward for half-precision activations.
+// Same plan, launch, work items and summation order as smx_conv_forward / smx_conv_backward; only k_conv1's row I/O
+// differs (its IO instances), so the outputs are the f32 outputs rounded once (include/smx.h).
+static const char* const CONV_IO_PLANS = "no 2-byte I/O on this plan (smx_conv_io_supported: the single-launch plan, "
+                                         "n_fft <= 2048): widen the input and call the f32 entry";
+
+int smx_conv_io_supported(const smx_shape* shape, int io) {
+  Shape h; Plan p;
+  if (io_check(io) || conv_shape(shape, &h) || !conv_plan(h, &p)) return 0;
+  return io == SMX_IO_F32 || p.conv1 ? 1 : 0;
+}
+
+int smx_conv_forward_io(const smx_shape* shape, const void* x, const float* h_re, const float* h_im,
+                        const float* row_scale, void* y, float* x_spectra, void* workspace,
+                        size_t workspace_bytes, int io, void* stream) {
+  if (int rc = io_check(io)) return rc;
+  if (io == SMX_IO_F32)
+    return smx_conv_forward(shape, (const float*)x, h_re, h_im, row_scale, (float*)y, x_spectra, workspace,
+                            workspace_bytes, stream);
+  Shape h; Plan p;
+  if (int rc = conv_shape(shape, &h)) return rc;
+  if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, "smx_conv_* needs n_fft = 512 ... 65536 (a power of two), rows <= n_fft and an even channel count");
+  if (!p.conv1) return fail(SMX_ERR_UNSUPPORTED, "%s", CONV_IO_PLANS);
+  if (!x || !y) return fail(SMX_ERR_INVALID, "x and y must be non-NULL");
+  if (((uintptr_t)x | (uintptr_t)y) & 3) return fail(SMX_ERR_INVALID, "2-byte x and y must be 4-byte aligned");
+  if ((uintptr_t)x_spectra & 7) return fail(SMX_ERR_INVALID, "x_spectra must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const ConvWs w = conv_ws(p, h);
+  DecimArgs a;
+  TableRef t;
+  if (int rc = conv_args(h, p, w, workspace, workspace_bytes, h_re, h_im, row_scale, s, t, &a, 2)) return rc;
+  a.in = (const float*)x; a.out = (float*)y;                 // 2-byte rows: read by k_conv1's IO instances only
+  a.ws_f = (cf*)x_spectra;                                   // packed spectrum of x for backward, or NULL (inference)
+  HIP_TRY(launch_conv1(a, p.conv1_nj, 0, nullptr, nullptr, nullptr, s, io));
+  return SMX_OK;
+}
+
+int smx_conv_backward_io(const smx_shape* shape, const void* g, const float* x_spectra, const float* h_re,
+                         const float* h_im, const float* row_scale, void* grad_x, float* grad_h_re,
+                         float* grad_h_im, float* grad_row_scale, void* workspace, size_t workspace_bytes,
+                         int io, void* stream) {
+  if (int rc = io_check(io)) return rc;
+  if (io == SMX_IO_F32)
+    return smx_conv_backward(shape, (const float*)g, x_spectra, h_re, h_im, row_scale, (float*)grad_x, grad_h_re,
+                             grad_h_im, grad_row_scale, workspace, workspace_bytes, stream);
+  Shape h; Plan p;
+  if (int rc = conv_shape(shape, &h)) return rc;
+  if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, "smx_conv_* needs n_fft = 512 ... 65536 (a power of two), rows <= n_fft and an even channel count");
+  if (!p.conv1) return fail(SMX_ERR_UNSUPPORTED, "%s", CONV_IO_PLANS);
+  if (!g || !x_spectra || !grad_x) return fail(SMX_ERR_INVALID, "g, x_spectra, grad_x must be non-NULL");
+  if (((uintptr_t)g | (uintptr_t)grad_x) & 3) return fail(SMX_ERR_INVALID, "2-byte g and grad_x must be 4-byte aligned");
+  if ((uintptr_t)x_spectra & 7) return fail(SMX_ERR_INVALID, "x_spectra must be 8-byte aligned");
+  if ((grad_h_re == nullptr) != (grad_h_im == nullptr))
+    return fail(SMX_ERR_INVALID, "grad_h_re and grad_h_im must be given together");
+  hipStream_t s = (hipStream_t)stream;
+  const ConvWs w = conv_ws(p, h);
+  DecimArgs a;
+  TableRef t;
+  if (int rc = conv_args(h, p, w, workspace, workspace_bytes, h_re, h_im, row_scale, s, t, &a, 2)) return rc;
+  a.in = (const float*)g; a.out = (float*)grad_x;            // 2-byte rows: read by k_conv1's IO instances only
+  a.ca.xs = (const cf*)x_spectra;
+  HIP_TRY(launch_conv1(a, p.conv1_nj, 1, grad_h_re, grad_h_im, grad_row_scale, s, io));
   return SMX_OK;
 }
 

@@ -9,6 +9,52 @@
 
 namespace smx {
 
+// ---- 2-byte rows (IO = SMX_IO_BF16 / SMX_IO_F16) -----------------------------------------------------------------
+// x / y (forward), g / grad_x (backward) of the IO instances: a channel pair of a row is ONE dword, the rest of the
+// launch (saved spectrum, partials, response, row scale, every sum) is the f32 instance's, in the same order.  Loads
+// widen exactly (widen2: bf16 a shift / mask, fp16 v_cvt_f32_f16) before anything else -- the FOLD sums x[n] +- x[n + N/2]
+// are formed in f32 after it --, stores round once, to nearest even, after the f32 value is final (narrow2: the fp16
+// operands pinned, so the row scale's multiply is not fused into a mixed-precision conversion).  The element type is
+// a distinct struct per IO so that c1_comb_store (smx_core.h) finds the 2-byte store below through its pointer.
+template <int IO> struct io_half { unsigned short bits; };
+template <int IO> struct c1_elem { using type = io_half<IO>; };
+template <> struct c1_elem<0> { using type = float; };
+
+#if defined(__HIP_DEVICE_COMPILE__)
+template <int IO>
+__device__ __forceinline__ void c1_st_pair(io_half<IO>* p, float x, float y, bool plain) {
+  const unsigned w = narrow2<IO>(x, y);
+#if SMX_NT_STORE
+  if (plain) __hip_atomic_store(reinterpret_cast<unsigned*>(p), w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+  else __builtin_nontemporal_store(w, reinterpret_cast<unsigned*>(p));
+#else
+  (void)plain;
+  *reinterpret_cast<unsigned*>(p) = w;
+#endif
+}
+// rows u = U0 .. U0+CNT-1 of tile r, as load_part_tile<U0, CNT, PAD, false> (ordinary cached loads: both teams read them)
+template <int U0, int CNT, bool PAD, int IO>
+__device__ __forceinline__ void c1_load(const io_half<IO>* __restrict__ xb, const Geom& g, int t, int r, cf (&v)[16]) {
+  const size_t stride = (size_t)16 * g.L * g.D;
+  const io_half<IO>* p = xb + ((size_t)t * g.L + r) * g.D;
+#pragma unroll
+  for (int u = U0; u < U0 + CNT; ++u) {
+    if (PAD && (t + 16 * u) * g.L + r >= g.R) { v[u] = mk(0.f, 0.f); continue; }
+    v[u] = widen2<IO>(*reinterpret_cast<const unsigned*>(p + u * stride));
+  }
+}
+#else
+template <int IO> __device__ void c1_st_pair(io_half<IO>* p, float x, float y, bool plain);
+template <int U0, int CNT, bool PAD, int IO>
+__device__ void c1_load(const io_half<IO>* __restrict__ xb, const Geom& g, int t, int r, cf (&v)[16]);
+#endif
+// the f32 rows: exactly the loads of the f32 kernel
+template <int U0, int CNT, bool PAD>
+__device__ __forceinline__ void c1_load(const float* __restrict__ xb, const Geom& g, int t, int r, cf (&v)[16]) {
+  if constexpr (U0 == 0 && CNT == 16) load_tile<PAD, false>(xb, g, t, r, v);
+  else load_part_tile<U0, CNT, PAD, false>(xb, g, t, r, v);
+}
+
 namespace {
 
 template <int CTRL>
@@ -54,34 +100,34 @@ template <int LP, int NJ> constexpr int c1_lds_elems() { return 4 * c1_exj<NJ>()
 
 // FOLD (rows > N / 2): the tile is x[n] + x[n + N/2] for the even team, x[n] - x[n + N/2] for the odd one; the upper
 // rows (nh, padded: hh.R = rows - N/2 of them exist) are prefetched beside the lower ones (nx, all present)
-template <int LP, int R, bool PAD, int NJ, bool FOLD>
+template <int LP, int R, bool PAD, int NJ, bool FOLD, typename T>
 __device__ __forceinline__ void c1_fwd_tiles(cf (&acc)[16 * LP], cf (&nx)[16], cf (&nh)[FOLD ? 16 : 1], cf* lds,
-                                             const float* __restrict__ xb, const Geom& h, const Geom& hh,
+                                             const T* __restrict__ xb, const Geom& h, const Geom& hh,
                                              const cf (&twe)[LP], const cf (&tw2e)[LP], int N, int p, int t, int j) {
   if constexpr (R < LP) {
     constexpr bool PLO = PAD && !FOLD;           // the lower rows are all there once rows > N / 2
-    const float* xh = xb + (size_t)h.N * h.D;
+    const T* xh = xb + (size_t)h.N * h.D;
     cf v[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) v[u] = nx[u];
     if constexpr (FOLD) c1_fold_in(v, nh, p);
     if constexpr (R + 1 < LP) {
-      load_part_tile<0, 8, PLO, false>(xb, h, t, R + 1, nx);
-      if constexpr (FOLD) load_part_tile<0, 8, PAD, false>(xh, hh, t, R + 1, nh);
+      c1_load<0, 8, PLO>(xb, h, t, R + 1, nx);
+      if constexpr (FOLD) c1_load<0, 8, PAD>(xh, hh, t, R + 1, nh);
     }
     cf* E = lds + (2 * p + (R & 1)) * c1_exj<NJ>();
     c1_fwd_phase1<LP, NJ>(v, twe[R], tw2e[R], E, p, t, j);
     __syncthreads();
     if constexpr (R + 1 < LP) {
-      load_part_tile<8, 8, PLO, false>(xb, h, t, R + 1, nx);
-      if constexpr (FOLD) load_part_tile<8, 8, PAD, false>(xh, hh, t, R + 1, nh);
+      c1_load<8, 8, PLO>(xb, h, t, R + 1, nx);
+      if constexpr (FOLD) c1_load<8, 8, PAD>(xh, hh, t, R + 1, nh);
     }
     c1_fwd_phase2<LP, R, NJ>(acc, E, t, j);
     c1_fwd_tiles<LP, R + 1, PAD, NJ, FOLD>(acc, nx, nh, lds, xb, h, hh, twe, tw2e, N, p, t, j);
   }
 }
-template <int LP, int R, bool PAD, int NJ, bool FOLD>
-__device__ __forceinline__ void c1_inv_tiles(const cf (&acc)[16 * LP], cf* lds, float* __restrict__ yb, const Geom& h,
+template <int LP, int R, bool PAD, int NJ, bool FOLD, typename T>
+__device__ __forceinline__ void c1_inv_tiles(const cf (&acc)[16 * LP], cf* lds, T* __restrict__ yb, const Geom& h,
                                              const cf (&twe)[LP], const cf (&tw2e)[LP], int N, int p, int t, int j,
                                              int lt, bool valid, float sa, float sb) {
   if constexpr (R < LP) {
@@ -98,13 +144,15 @@ __device__ __forceinline__ void c1_inv_tiles(const cf (&acc)[16 * LP], cf* lds, 
   }
 }
 
+// IO: element type of x / y / g / grad_x (0 f32; 1 bf16, 2 fp16: a.in / a.out point at 2-byte rows, see io_half above)
 // DIR 0: y = s * conv(x);  a.ws_f = where the packed spectrum of x is kept (or null)
 // DIR 1: grad_x = s * conv^T(g), P partials -> a.ca.p_part[wg][N], (R1, R2) -> a.ca.r_part[wg][NJ]
 // NJ channel pairs per workgroup: 16 (512 threads, one workgroup per CU) or 8 (256 threads on 16 channels, 64-byte row
 // segments, two workgroups per CU); wg = b ceil(D / (2 NJ)) + d-tile either way.
 // FOLD: N / 2 < rows <= N (PAD: rows < N); otherwise rows <= N / 2 (PAD: rows < N / 2).
-template <int LP, int DIR, bool PAD, int NJ, bool FOLD>
+template <int LP, int DIR, bool PAD, int NJ, bool FOLD, int IO>
 __global__ __launch_bounds__(c1_tpb<NJ>(), NJ == 16 ? 1 : 2) void k_conv1(const DecimArgs a) {
+  using T = typename c1_elem<IO>::type;
   __shared__ cf lds[c1_lds_elems<LP, NJ>()];
   constexpr int EXJ = c1_exj<NJ>(), TS = 16 * NJ, DTJ = 2 * NJ;
   const Geom& g = a.g;                         // the n_fft geometry (N = 512 LP, R rows)
@@ -119,7 +167,7 @@ __global__ __launch_bounds__(c1_tpb<NJ>(), NJ == 16 ? 1 : 2) void k_conv1(const 
   const int b = w.b, wg = b * ndt + w.dt, d = w.dt * DTJ + 2 * j;
   const bool valid = d < g.D;
   const int dc = valid ? d : g.D - 2;
-  const float* xb = a.in + (size_t)b * g.R * g.D + dc;
+  const T* xb = reinterpret_cast<const T*>(a.in) + (size_t)b * g.R * g.D + dc;
   cf* Hs = lds + 4 * EXJ;
 
   cf acc[16 * LP];
@@ -129,8 +177,8 @@ __global__ __launch_bounds__(c1_tpb<NJ>(), NJ == 16 ? 1 : 2) void k_conv1(const 
   cf twe[LP], tw2e[LP];
 #pragma unroll
   for (int R = 0; R < LP; ++R) { twe[R] = a.tw[LP * t + R]; tw2e[R] = a.tw[2 * (LP * t + R)]; }
-  load_tile<PAD && !FOLD, false>(xb, h, t, 0, nx);      // (cached: both teams read the same rows)
-  if constexpr (FOLD) load_tile<PAD, false>(xb + (size_t)h.N * h.D, hh, t, 0, nh);
+  c1_load<0, 16, PAD && !FOLD>(xb, h, t, 0, nx);      // (cached: both teams read the same rows)
+  if constexpr (FOLD) c1_load<0, 16, PAD>(xb + (size_t)h.N * h.D, hh, t, 0, nh);
   float sa = 1.f, sb = 1.f;
   if (a.ca.sc) { sa = a.ca.sc[(size_t)b * g.D + dc]; sb = a.ca.sc[(size_t)b * g.D + dc + 1]; }
   c1_stage_h<NJ>(a.ca, N, g.inv_n, Hs, tid);
@@ -177,8 +225,8 @@ __global__ __launch_bounds__(c1_tpb<NJ>(), NJ == 16 ? 1 : 2) void k_conv1(const 
   c1_pin(acc);
   c1_residues<LP, +1>(acc);
   c1_pin(acc);
-  c1_inv_tiles<LP, 0, PAD, NJ, FOLD>(acc, lds, a.out + (size_t)b * g.R * g.D + d, h, twe, tw2e, N, p, t, j, lt, valid, sa,
-                                     sb);
+  c1_inv_tiles<LP, 0, PAD, NJ, FOLD>(acc, lds, reinterpret_cast<T*>(a.out) + (size_t)b * g.R * g.D + d, h, twe, tw2e, N,
+                                     p, t, j, lt, valid, sa, sb);
 }
 
 // ---- the filter's own response (reference fft_lm/train_fixed_full.py:511-513, :529, :540-551) -------------------
@@ -354,30 +402,36 @@ hipError_t launch_phase_filter_bwd(const float* m, const float* ph, const float*
 }
 
 namespace {
-template <int LP, int NJ, bool FOLD>
+template <int LP, int NJ, bool FOLD, int IO>
 void launch_conv1_f(const DecimArgs& a, int dir, bool pad, dim3 grid, dim3 block, hipStream_t s) {
-  if (dir == 0 && pad) hipLaunchKernelGGL((k_conv1<LP, 0, true, NJ, FOLD>), grid, block, 0, s, a);
-  else if (dir == 0) hipLaunchKernelGGL((k_conv1<LP, 0, false, NJ, FOLD>), grid, block, 0, s, a);
-  else if (pad) hipLaunchKernelGGL((k_conv1<LP, 1, true, NJ, FOLD>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((k_conv1<LP, 1, false, NJ, FOLD>), grid, block, 0, s, a);
+  if (dir == 0 && pad) hipLaunchKernelGGL((k_conv1<LP, 0, true, NJ, FOLD, IO>), grid, block, 0, s, a);
+  else if (dir == 0) hipLaunchKernelGGL((k_conv1<LP, 0, false, NJ, FOLD, IO>), grid, block, 0, s, a);
+  else if (pad) hipLaunchKernelGGL((k_conv1<LP, 1, true, NJ, FOLD, IO>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((k_conv1<LP, 1, false, NJ, FOLD, IO>), grid, block, 0, s, a);
 }
-template <int LP, int NJ>
+template <int LP, int NJ, int IO>
 void launch_conv1_t(const DecimArgs& a, int dir, hipStream_t s) {
   const dim3 grid(conv1_workgroups(a.g.B, a.g.D, NJ)), block(c1_tpb<NJ>());
   const bool fold = 2 * a.g.R > a.g.N;                    // rows beyond N / 2: folded onto the lower half
   const bool pad = fold ? a.g.R < a.g.N : 2 * a.g.R < a.g.N;
-  if (fold) launch_conv1_f<LP, NJ, true>(a, dir, pad, grid, block, s);
-  else launch_conv1_f<LP, NJ, false>(a, dir, pad, grid, block, s);
+  if (fold) launch_conv1_f<LP, NJ, true, IO>(a, dir, pad, grid, block, s);
+  else launch_conv1_f<LP, NJ, false, IO>(a, dir, pad, grid, block, s);
 }
-template <int NJ>
+template <int NJ, int IO>
 hipError_t launch_conv1_nj(const DecimArgs& a, int dir, hipStream_t s) {
   switch (a.g.N) {
-    case 512: launch_conv1_t<1, NJ>(a, dir, s); break;
-    case 1024: launch_conv1_t<2, NJ>(a, dir, s); break;
-    case 2048: launch_conv1_t<4, NJ>(a, dir, s); break;
+    case 512: launch_conv1_t<1, NJ, IO>(a, dir, s); break;
+    case 1024: launch_conv1_t<2, NJ, IO>(a, dir, s); break;
+    case 2048: launch_conv1_t<4, NJ, IO>(a, dir, s); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
+}
+// both workgroup widths for every IO: the width sets which channel pairs one workgroup's partial sums of P / (R1, R2)
+// hold, and so the f32 summation order of the response's gradient -- a 2-byte launch must take the f32 plan's width
+template <int IO>
+hipError_t launch_conv1_io(const DecimArgs& a, int nj, int dir, hipStream_t s) {
+  return nj == 8 ? launch_conv1_nj<8, IO>(a, dir, s) : launch_conv1_nj<16, IO>(a, dir, s);
 }
 
 }  // namespace
@@ -387,10 +441,11 @@ bool conv1_supported(int N, int R) { return (N == 512 || N == 1024 || N == 2048)
 int conv1_workgroups(int B, int D, int nj) { return B * ((D + 2 * nj - 1) / (2 * nj)); }
 
 hipError_t launch_conv1(const DecimArgs& a0, int nj, int dir, float* gh_re, float* gh_im, float* grad_scale,
-                        hipStream_t s) {
+                        hipStream_t s, int io) {
   DecimArgs a = a0;
   a.bid0 = 0;
-  const hipError_t e = nj == 8 ? launch_conv1_nj<8>(a, dir, s) : launch_conv1_nj<16>(a, dir, s);
+  const hipError_t e = io == 1 ? launch_conv1_io<1>(a, nj, dir, s)
+                     : io == 2 ? launch_conv1_io<2>(a, nj, dir, s) : launch_conv1_io<0>(a, nj, dir, s);
   if (e != hipSuccess) return e;
   if (dir == 1)                                   // (R1, R2) arrive / N, one row of nj per workgroup
     return launch_conv_reduce(a, gh_re, gh_im, grad_scale, 1, 0.5f, s, conv1_workgroups(a.g.B, a.g.D, nj), nj);

@@ -2075,12 +2075,15 @@ SMX_HD void c1_fold_in(cf (&v)[16], const cf (&hi)[16], int p) {
 #pragma unroll
   for (int u = 0; u < 16; ++u) v[u] = mk(__builtin_fmaf(sg, hi[u].x, v[u].x), __builtin_fmaf(sg, hi[u].y, v[u].y));
 }
-template <bool PAD, int NJ = 16, bool FOLD = false>
-SMX_HD void c1_comb_store(const cf (&v)[16], const cf* __restrict__ C, float* __restrict__ yb, const Geom& g,
+// one channel pair of an output row: f32 here; the 2-byte row types of k_conv1's IO instances bring their own overload
+// (smx_conv1.hip), found through the element type
+SMX_HD void c1_st_pair(float* p, float x, float y, bool plain) { st_stream(p, x, y, plain); }
+template <bool PAD, int NJ = 16, bool FOLD = false, typename T = float>
+SMX_HD void c1_comb_store(const cf (&v)[16], const cf* __restrict__ C, T* __restrict__ yb, const Geom& g,
                           int p, int t, int lt, int r, bool valid, float sa, float sb) {
   if (!valid) return;
   const size_t stride = (size_t)16 * g.L * g.D;
-  float* ptr = yb + ((size_t)t * g.L + r) * g.D;
+  T* ptr = yb + ((size_t)t * g.L + r) * g.D;
   cf o[8], o2[FOLD ? 8 : 1];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -2097,13 +2100,13 @@ SMX_HD void c1_comb_store(const cf (&v)[16], const cf* __restrict__ C, float* __
     const int u = 8 * p + k;
     const int n = (t + 16 * u) * g.L + r;              // row of the lower half; FOLD: always present, its partner n + N'
     if (!FOLD && PAD && n >= g.R) continue;            //   is present while n + N' < R (g: the N' tile geometry, R rows)
-    float* dst = ptr + (size_t)u * stride;
+    T* dst = ptr + (size_t)u * stride;
     // (each team stores 8 of the 16 rows: the first st_plain / 2 of them write-back, as store_tile's first st_plain)
-    st_stream(dst, o[k].x * sa, o[k].y * sb, k < 2 && 2 * k < g.st_plain);
+    c1_st_pair(dst, o[k].x * sa, o[k].y * sb, k < 2 && 2 * k < g.st_plain);
     if constexpr (FOLD) {
       if (PAD && n + g.N >= g.R) continue;
-      float* dst2 = dst + (size_t)g.N * g.D;
-      st_stream(dst2, o2[k].x * sa, o2[k].y * sb, k < 2 && 2 * k < g.st_plain);
+      T* dst2 = dst + (size_t)g.N * g.D;
+      c1_st_pair(dst2, o2[k].x * sa, o2[k].y * sb, k < 2 && 2 * k < g.st_plain);
     }
   }
 }

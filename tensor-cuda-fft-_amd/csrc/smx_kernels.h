@@ -95,8 +95,9 @@ hipError_t launch_conv_reduce(const DecimArgs& a, float* gh_re, float* gh_im, fl
 bool conv1_supported(int N, int R);
 // nj = channel pairs per workgroup: 16 (512 threads) or 8 (256 threads, two workgroups per CU)
 int conv1_workgroups(int B, int D, int nj);
+// io: element type of a.in / a.out (SMX_IO_*: 0 f32 rows, 1 bf16, 2 fp16 -- 2-byte rows, everything else f32)
 hipError_t launch_conv1(const DecimArgs& a, int nj, int dir, float* gh_re, float* gh_im, float* grad_scale,
-                        hipStream_t s);
+                        hipStream_t s, int io = 0);
 // the filter's own response H = rfft(zero-pad(kernel), N) * sigmoid(logits) * mask (f <= N/2) and its backward
 hipError_t launch_conv_response(const float* kernel, const float* logits, const float* mask, const cf* tw, int N,
                                 int K, float* h_re, float* h_im, hipStream_t s);

@@ -88,12 +88,25 @@ def causal_spectral_conv(x: torch.Tensor, kernel: torch.Tensor, gain: torch.Tens
     """Lines :507-555 of the reference block for x (B, T, C): causal linear convolution with the
     time-domain `kernel` via a zero-padded transform of length next_pow2(T + K - 1), per-channel `gain`,
     per-frequency sigmoid gate, per-(batch, channel) context gate `g_ctx` (already in [0, 1]) and the
-    cosine cutoff mask; returns the first T samples."""
+    cosine cutoff mask; returns the first T samples.
+
+    x may be fp32, bf16 or fp16.  For 2-byte x the parameters and g_ctx may each be fp32 or x's dtype; they are read
+    as fp32 (`.float()`, so autograd returns each gradient in its own dtype) and the result is this function's on
+    x.float(), rounded once to x's dtype: native 2-byte rows where rank_one_conv has them, the up-cast route
+    x.float() -> fp32 op -> .to(dtype) on every other shape."""
     B, T, C = x.shape
     K = kernel.shape[0]
     n_fft = next_pow2(T + K - 1)                                           # :507-509
     fbins = n_fft // 2 + 1
-    if conv_supported(B, T, C, n_fft) and x.is_cuda and x.dtype == torch.float32:
+    if x.dtype in (torch.bfloat16, torch.float16):
+        kernel, gain = kernel.float(), gain.float()
+        gate_freq_logits = None if gate_freq_logits is None else gate_freq_logits.float()
+        g_ctx = None if g_ctx is None else g_ctx.float()
+        if not (conv_supported(B, T, C, n_fft) and x.is_cuda):
+            # shapes the convolution's own kernels do not take (odd C, n_fft < 512): spectral_filter is fp32-only
+            return causal_spectral_conv(x.float(), kernel, gain, gate_freq_logits, g_ctx, cutoff,
+                                        transition_bins).to(x.dtype)
+    if conv_supported(B, T, C, n_fft) and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16, torch.float16):
         # n_fft 512 ... 65536: the convolution's own kernels -- the packed
         # spectrum times the Hermitian extension of H, gain x context gate at the store (smx_conv_*).
         # H = k_freq (:511-513) x sigmoid(gate) (:529) x mask (:551): one native launch (and one for its gradients)
@@ -110,7 +123,7 @@ def causal_spectral_conv(x: torch.Tensor, kernel: torch.Tensor, gain: torch.Tens
             if per_f is not None:
                 h_re, h_im = h_re * per_f, h_im * per_f
         s = gain.unsqueeze(0).expand(B, C) if g_ctx is None else gain.unsqueeze(0) * g_ctx   # :522, :533-536
-        return rank_one_conv(x, h_re, h_im, s.contiguous(), n_fft)
+        return rank_one_conv(x, h_re, h_im, s.contiguous(), n_fft)        # (2-byte x: y in x's dtype)
     h_re, h_im = _kernel_response(kernel, n_fft)                           # k_freq, :511-513
     scale = hermitian_scale(n_fft, fbins, x.device)                        # irfft semantics, :553
     if gate_freq_logits is not None:

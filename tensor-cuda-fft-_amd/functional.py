@@ -1037,6 +1037,9 @@ def conv_supported(B: int, R: int, D: int, n_fft: int) -> bool:
     return _conv_plan(B, R, D, n_fft) is not None
 
 
+_conv_io_cache = _Memo()
+
+
 class _RankOneConv(torch.autograd.Function):
     """y[b, n, c] = s[b, c] * irfft(rfft(zero-pad(x[b, :, c]), n_fft) * (h_re + i h_im), n_fft)[n], n < rows
     (reference fft_lm/train_fixed_full.py:507-555) through smx_conv_forward / smx_conv_backward."""
@@ -1052,10 +1055,17 @@ class _RankOneConv(torch.autograd.Function):
         _prepare(x.device, n_fft)
         ws = _workspace(x.device, wsb)
         sh = _shape(B, R, D, n_fft // 2 + 1, n_fft, n_fft // 2 + 1)
+        io = ctx.io = _IO[x.dtype]                           # bf16 / fp16 x: the single-launch plan only (rank_one_conv)
         with _on_device(x.device):
-            _lib.check(_lib.lib().smx_conv_forward(sh, x.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale),
-                                                   y.data_ptr(), _ptr(xs), ws.data_ptr(), ws.numel(),
-                                                   _stream(x.device)))
+            if io == 0:
+                _lib.check(_lib.lib().smx_conv_forward(sh, x.data_ptr(), h_re.data_ptr(), h_im.data_ptr(),
+                                                       _ptr(scale), y.data_ptr(), _ptr(xs), ws.data_ptr(),
+                                                       ws.numel(), _stream(x.device)))
+            else:
+                _lib.check(_lib.lib().smx_conv_forward_io(sh, x.data_ptr(), h_re.data_ptr(), h_im.data_ptr(),
+                                                          _ptr(scale), y.data_ptr(), _ptr(xs), ws.data_ptr(),
+                                                          ws.numel(), io, _stream(x.device)))
+        ctx.dtype = x.dtype
         ctx.n_fft = n_fft
         ctx.has_scale = scale is not None
         if needs:
@@ -1069,8 +1079,8 @@ class _RankOneConv(torch.autograd.Function):
         xs, h_re, h_im, scale = ctx.saved_tensors
         if not ctx.has_scale:
             scale = None
-        if g.dtype != torch.float32:
-            g = g.float()
+        if g.dtype != ctx.dtype:
+            g = g.to(ctx.dtype)
         g = _dense(g)
         B, R, D = g.shape
         n = ctx.n_fft
@@ -1083,10 +1093,16 @@ class _RankOneConv(torch.autograd.Function):
         ws = _workspace(g.device, wsb)
         sh = _shape(B, R, D, n // 2 + 1, n, n // 2 + 1)
         with _on_device(g.device):
-            _lib.check(_lib.lib().smx_conv_backward(
-                sh, g.data_ptr(), xs.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), gx.data_ptr(),
-                None if gh is None else gh[0].data_ptr(), None if gh is None else gh[1].data_ptr(), _ptr(gs),
-                ws.data_ptr(), ws.numel(), _stream(g.device)))
+            if ctx.io == 0:
+                _lib.check(_lib.lib().smx_conv_backward(
+                    sh, g.data_ptr(), xs.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), gx.data_ptr(),
+                    None if gh is None else gh[0].data_ptr(), None if gh is None else gh[1].data_ptr(), _ptr(gs),
+                    ws.data_ptr(), ws.numel(), _stream(g.device)))
+            else:
+                _lib.check(_lib.lib().smx_conv_backward_io(
+                    sh, g.data_ptr(), xs.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), gx.data_ptr(),
+                    None if gh is None else gh[0].data_ptr(), None if gh is None else gh[1].data_ptr(), _ptr(gs),
+                    ws.data_ptr(), ws.numel(), ctx.io, _stream(g.device)))
         return gx, None if gh is None else gh[0], None if gh is None else gh[1], gs, None, None
 
 
@@ -1526,8 +1542,12 @@ def rank_one_conv(x: torch.Tensor, h_re: torch.Tensor, h_im: torch.Tensor,
                   scale: Optional[torch.Tensor], n_fft: int) -> torch.Tensor:
     """Causal / circular convolution of every (batch, channel) column of x (B, rows, D) with the real kernel
     whose one-sided spectrum is h_re + i h_im (n_fft // 2 + 1), times scale[b, c]; needs
-    conv_supported(B, rows, D, n_fft)."""
-    _require_gpu_f32("x", x)
+    conv_supported(B, rows, D, n_fft).
+
+    x may be fp32, bf16 or fp16; y and grad_x come back in x's dtype, while h_re, h_im and scale stay fp32.  All
+    arithmetic is fp32: the result is the fp32 op's on x.float(), rounded once to x's dtype -- by the kernel's stores
+    where the plan has native 2-byte rows (_lib.conv_io_supported), by `.to(dtype)` after the fp32 op elsewhere."""
+    _require_gpu_io("x", x)
     _require_gpu_f32("h_re", h_re)
     _require_gpu_f32("h_im", h_im)
     B, R, D = x.shape
@@ -1540,6 +1560,10 @@ def rank_one_conv(x: torch.Tensor, h_re: torch.Tensor, h_im: torch.Tensor,
             raise ValueError(f"scale must be (B, D) = ({B}, {D})")
     if not conv_supported(B, R, D, n_fft):
         raise ValueError(f"rank_one_conv does not take (B={B}, rows={R}, D={D}, n_fft={n_fft}); use spectral_filter")
+    if x.dtype != torch.float32 and not _conv_io_cache.get((B, R, D, n_fft, x.dtype),
+                                                           lambda: _lib.conv_io_supported(B, R, D, n_fft, _IO[x.dtype])):
+        return rank_one_conv(x.float(), h_re, h_im, scale, n_fft).to(x.dtype)
+    # _dense: contiguous and 16-byte aligned -- a view with a storage offset is copied before it reaches the library
     return _RankOneConv.apply(_dense(x), _dense(h_re), _dense(h_im), _dense(scale), int(n_fft),
                               torch.is_grad_enabled())
 
