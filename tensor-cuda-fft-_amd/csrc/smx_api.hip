@@ -414,7 +414,7 @@ int need_ws(const Ws& w, void* ws, size_t bytes) {
   return SMX_OK;
 }
 
-// elem: bytes per element of the streamed x / y (4; 2 for the 2-byte activations of smx_forward_io / smx_backward_io)
+// elem: bytes per element of the streamed x / y (4; 2 for the 2-byte activations of the _io entries)
 DecimArgs decim_args(const Plan& p, const Tables& t, const Shape& h, char* ws, const Ws& w, int elem = 4) {
   const int B = h.B, N = h.N, D = h.D, F = h.F;
   DecimArgs a{};
@@ -654,10 +654,21 @@ int smx_forward(const float* x, const float* w_re, const float* w_im, const floa
                              conj_w, 0.f, nullptr, nullptr, stream);
 }
 
+// io (forward_impl, backward_impl): element type of x / y / g / grad_x, SMX_IO_*.  2-byte rows travel behind the
+// float pointers and are only read by the IO instances of k_fused / k_split_a / k_split_b, on the plans of io_native.
+static bool io_native(const Plan& p) {
+  return p.path == SMX_PATH_DECIMATED && p.groups == 1 && !p.fs && !p.full8;
+}
+static int io_check(int io) {
+  if (io != SMX_IO_F32 && io != SMX_IO_BF16 && io != SMX_IO_F16)
+    return fail(SMX_ERR_INVALID, "io must be SMX_IO_F32, SMX_IO_BF16 or SMX_IO_F16, got %d", io);
+  return SMX_OK;
+}
+
 static int forward_impl(const Shape& h, const float* x, const float* w_re, const float* w_im,
                         const float* bias, float* y, float* xk_save, void* workspace,
                         size_t workspace_bytes, int conj_w, float dropout_p, const void* rng_state,
-                        float* filter_pack, void* stream, const float* row_scale = nullptr);
+                        float* filter_pack, void* stream, const float* row_scale = nullptr, int io = SMX_IO_F32);
 
 int smx_forward_dropout(const float* x, const float* w_re, const float* w_im, const float* bias,
                         float* y, float* xk_save, void* workspace, size_t workspace_bytes, int B,
@@ -689,7 +700,7 @@ int smx_row_scale_supported(const smx_shape* shape) {
 static int forward_impl(const Shape& h, const float* x, const float* w_re, const float* w_im,
                         const float* bias, float* y, float* xk_save, void* workspace,
                         size_t workspace_bytes, int conj_w, float dropout_p, const void* rng_state,
-                        float* filter_pack, void* stream, const float* row_scale) {
+                        float* filter_pack, void* stream, const float* row_scale, int io) {
   const int B = h.B, N = h.N, D = h.D, F = h.F;
   DropCfg dc;
   if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
@@ -697,12 +708,19 @@ static int forward_impl(const Shape& h, const float* x, const float* w_re, const
   conj_w &= 1;
   if (pack_ready && !filter_pack) return fail(SMX_ERR_INVALID, "SMX_FILTER_PACK_READY without filter_pack");
   if (!x || !w_re || !w_im || !y) return fail(SMX_ERR_INVALID, "x, w_re, w_im, y must be non-NULL");
-  if (((uintptr_t)x | (uintptr_t)y) & 7) return fail(SMX_ERR_INVALID, "x and y must be 8-byte aligned");
+  if (io != SMX_IO_F32) {
+    if (((uintptr_t)x | (uintptr_t)y) & 3) return fail(SMX_ERR_INVALID, "2-byte x and y must be 4-byte aligned");
+  } else if (((uintptr_t)x | (uintptr_t)y) & 7) return fail(SMX_ERR_INVALID, "x and y must be 8-byte aligned");
   if ((uintptr_t)xk_save & 15) return fail(SMX_ERR_INVALID, "xk_save must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const Plan p = make_plan(h);
+  if (io != SMX_IO_F32 && !io_native(p))
+    return fail(SMX_ERR_UNSUPPORTED, "no 2-byte I/O on this plan (smx_io_supported): widen the input and call "
+                "smx_forward_dropout");
   if (dc.thr && h.R < N) return fail(SMX_ERR_UNSUPPORTED, "fused dropout is not available with zero-padded rows");
   const Ws w = ws_layout(p, B, N, D);
+  // (smx_forward_io has always looked at the workspace before the tables; the f32 entries look below, after them)
+  if (io != SMX_IO_F32 && p.nsplit > 1) if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
   TableRef t;
   if (int rc = get_tables(N, &t, s)) return rc;
   char* ws = (char*)workspace;
@@ -727,7 +745,7 @@ static int forward_impl(const Shape& h, const float* x, const float* w_re, const
   }
   if (p.path == SMX_PATH_DECIMATED) {
     if (p.nsplit > 1) if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
-    DecimArgs a = decim_args(p, t, h, ws, w);
+    DecimArgs a = decim_args(p, t, h, ws, w, io != SMX_IO_F32 ? 2 : 4);
     a.in = x; a.out = y;
     a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.bias = bias; a.fa.conj_w = conj_w;
     a.fa.xk_out = xk_save;
@@ -779,11 +797,11 @@ static int forward_impl(const Shape& h, const float* x, const float* w_re, const
       if (workspace && workspace_bytes >= w.total && !((uintptr_t)workspace & 255) &&
           sync_words(B, D) * sizeof(unsigned) <= SYNC_BYTES)
         a.sync = (unsigned*)(ws + w.sync);
-      HIP_TRY(launch_fused(a, p.nb, 0, s));
+      HIP_TRY(launch_fused(a, p.nb, 0, s, io));
     } else {
-      HIP_TRY(launch_split_a(a, p.nb, false, s));
+      HIP_TRY(launch_split_a(a, p.nb, false, s, io));
       HIP_TRY(launch_split_f(a, p.nb, 0, s));
-      HIP_TRY(launch_split_b(a, p.nb, true, s));
+      HIP_TRY(launch_split_b(a, p.nb, true, s, io));
     }
     return SMX_OK;
   }
@@ -810,7 +828,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
                          const float* w_im, float* grad_x, float* gw_re, float* gw_im, float* gbias,
                          void* workspace, size_t workspace_bytes, int phases, float dropout_p,
                          const void* rng_state, const float* filter_pack, void* stream,
-                         const float* row_scale = nullptr, float* grad_row_scale = nullptr);
+                         const float* row_scale = nullptr, float* grad_row_scale = nullptr, int io = SMX_IO_F32);
 
 int smx_backward_dropout(const float* g, const float* xk, const float* w_re, const float* w_im,
                          float* grad_x, float* gw_re, float* gw_im, float* gbias, void* workspace,
@@ -836,7 +854,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
                          const float* w_im, float* grad_x, float* gw_re, float* gw_im, float* gbias,
                          void* workspace, size_t workspace_bytes, int phases, float dropout_p,
                          const void* rng_state, const float* filter_pack, void* stream,
-                         const float* row_scale, float* grad_row_scale) {
+                         const float* row_scale, float* grad_row_scale, int io) {
   const int B = h.B, N = h.N, D = h.D, F = h.F;
   DropCfg dc;
   if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
@@ -848,11 +866,17 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
   const bool want_w = gw_re || gw_im || gbias;
   if (want_w && !(gw_re && gw_im && gbias))
     return fail(SMX_ERR_INVALID, "gw_re, gw_im, gbias must be given together");
-  if (((uintptr_t)g | (uintptr_t)grad_x) & 7)
+  if (io != SMX_IO_F32) {
+    if (((uintptr_t)g | (uintptr_t)grad_x) & 3)
+      return fail(SMX_ERR_INVALID, "2-byte g and grad_x must be 4-byte aligned");
+  } else if (((uintptr_t)g | (uintptr_t)grad_x) & 7)
     return fail(SMX_ERR_INVALID, "g and grad_x must be 8-byte aligned");
   if ((uintptr_t)xk & 15) return fail(SMX_ERR_INVALID, "xk must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const Plan p = make_plan(h);
+  if (io != SMX_IO_F32 && !io_native(p))
+    return fail(SMX_ERR_UNSUPPORTED, "no 2-byte I/O on this plan (smx_io_supported): widen g and call "
+                "smx_backward_dropout");
   if (dc.thr && h.R < N) return fail(SMX_ERR_UNSUPPORTED, "fused dropout is not available with zero-padded rows");
   if ((want_w || dc.thr || grad_row_scale) && !xk && p.k > 0)
     return fail(SMX_ERR_INVALID, "xk (saved spectrum) is NULL");
@@ -898,7 +922,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
     return SMX_OK;
   }
   if (p.path == SMX_PATH_DECIMATED) {
-    DecimArgs a = decim_args(p, t, h, ws, w);
+    DecimArgs a = decim_args(p, t, h, ws, w, io != SMX_IO_F32 ? 2 : 4);
     a.in = g; a.out = grad_x;
     a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.conj_w = 1;
     a.fa.xk_in = xk; a.fa.pslab = (float*)(ws + w.slab); a.fa.gb_part = (float*)(ws + w.gbp);
@@ -988,7 +1012,9 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
       // library clears them): the reduction workgroups inherit the transform kernel's footprint (two per CU) and
       // can only start when transform workgroups retire, so the tail is longer than k_gradw's 7.5 us + boundaries.
       // Off by default.
-      const bool fold = do_par && mode == 1 && p.nb <= 2 && cur_opts().fold_gradw != 0 &&
+      // (2-byte rows: never -- their kernels hold no gradw_tail; SMX_PHASE_SYNC_CLEAN is then
+      // accepted and has nothing to vouch for)
+      const bool fold = do_par && mode == 1 && p.nb <= 2 && cur_opts().fold_gradw != 0 && io == SMX_IO_F32 &&
                         sync_words(B, D) * sizeof(unsigned) <= SYNC_BYTES;
       if (fold) {
         a.sync = (unsigned*)(ws + w.sync);
@@ -997,20 +1023,20 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
         a.fa.slab_agent = 1;
         if (!sync_clean) HIP_TRY(hipMemsetAsync(a.sync, 0, sync_words(B, D) * sizeof(unsigned), s));
       }
-      HIP_TRY(launch_fused(a, p.nb, mode, s));
+      HIP_TRY(launch_fused(a, p.nb, mode, s, io));
       if (fold) return SMX_OK;
     } else {
       if (do_spec) {
         if (p.nsplit == 1) {          // forward half + filter in one launch, S parked in the workspace
           DecimArgs h = a;
           h.out = nullptr;
-          HIP_TRY(launch_fused(h, p.nb, mode, s));
+          HIP_TRY(launch_fused(h, p.nb, mode, s, io));
         } else {
-          HIP_TRY(launch_split_a(a, p.nb, true, s));
+          HIP_TRY(launch_split_a(a, p.nb, true, s, io));
           HIP_TRY(launch_split_f(a, p.nb, mode, s));
         }
       }
-      if (do_inv) HIP_TRY(launch_split_b(a, p.nb, false, s));
+      if (do_inv) HIP_TRY(launch_split_b(a, p.nb, false, s, io));
     }
     if (do_par)
       HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, B,
@@ -1174,7 +1200,7 @@ int smx_conv_workspace_bytes(const smx_shape* shape, size_t* workspace_bytes, si
 }
 
 // t: the caller's TableRef -- the tables stay pinned until the entry point has enqueued its launches
-// elem: bytes per element of x / y / g / grad_x (4; 2 for smx_conv_forward_io / smx_conv_backward_io)
+// elem: bytes per element of x / y / g / grad_x (4; 2 for 2-byte rows, conv_forward_impl / conv_backward_impl)
 static int conv_args(const Shape& h, const Plan& p, const ConvWs& w, void* workspace, size_t workspace_bytes,
                      const float* h_re, const float* h_im, const float* row_scale, hipStream_t s, TableRef& t,
                      DecimArgs* out, int elem = 4) {
@@ -1195,23 +1221,34 @@ static int conv_args(const Shape& h, const Plan& p, const ConvWs& w, void* works
   return SMX_OK;
 }
 
-int smx_conv_forward(const smx_shape* shape, const float* x, const float* h_re, const float* h_im,
-                     const float* row_scale, float* y, float* x_spectra, void* workspace,
-                     size_t workspace_bytes, void* stream) {
+static const char* const CONV_IO_PLANS = "no 2-byte I/O on this plan (smx_conv_io_supported: the single-launch plan, "
+                                         "n_fft <= 2048): widen the input and call the f32 entry";
+
+// io: element type of x / y (g / grad_x), SMX_IO_*; 2-byte rows travel behind the float pointers and are read by
+// k_conv1's IO instances only
+static int conv_forward_impl(const smx_shape* shape, const float* x, const float* h_re, const float* h_im,
+                             const float* row_scale, float* y, float* x_spectra, void* workspace,
+                             size_t workspace_bytes, int io, void* stream) {
   Shape h; Plan p;
   if (int rc = conv_shape(shape, &h)) return rc;
   if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, "smx_conv_* needs n_fft = 512 ... 65536 (a power of two), rows <= n_fft and an even channel count");
+  if (io != SMX_IO_F32 && !p.conv1) return fail(SMX_ERR_UNSUPPORTED, "%s", CONV_IO_PLANS);
   if (!x || !y) return fail(SMX_ERR_INVALID, "x and y must be non-NULL");
-  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)x_spectra) & 7) return fail(SMX_ERR_INVALID, "x, y, x_spectra must be 8-byte aligned");
+  if (io != SMX_IO_F32) {
+    if (((uintptr_t)x | (uintptr_t)y) & 3) return fail(SMX_ERR_INVALID, "2-byte x and y must be 4-byte aligned");
+    if ((uintptr_t)x_spectra & 7) return fail(SMX_ERR_INVALID, "x_spectra must be 8-byte aligned");
+  } else if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)x_spectra) & 7)
+    return fail(SMX_ERR_INVALID, "x, y, x_spectra must be 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const ConvWs w = conv_ws(p, h);
   DecimArgs a;
   TableRef t;
-  if (int rc = conv_args(h, p, w, workspace, workspace_bytes, h_re, h_im, row_scale, s, t, &a)) return rc;
+  if (int rc = conv_args(h, p, w, workspace, workspace_bytes, h_re, h_im, row_scale, s, t, &a, io != SMX_IO_F32 ? 2 : 4))
+    return rc;
   a.in = x; a.out = y;
   if (p.conv1) {
     a.ws_f = (cf*)x_spectra;                        // packed spectrum of x for backward, or NULL (inference)
-    HIP_TRY(launch_conv1(a, p.conv1_nj, 0, nullptr, nullptr, nullptr, s));
+    HIP_TRY(launch_conv1(a, p.conv1_nj, 0, nullptr, nullptr, nullptr, s, io));
     return SMX_OK;
   }
   cf* filtered = a.ws_f;
@@ -1223,16 +1260,27 @@ int smx_conv_forward(const smx_shape* shape, const float* x, const float* h_re, 
   HIP_TRY(launch_fs_b(a, s));
   return SMX_OK;
 }
+int smx_conv_forward(const smx_shape* shape, const float* x, const float* h_re, const float* h_im,
+                     const float* row_scale, float* y, float* x_spectra, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  return conv_forward_impl(shape, x, h_re, h_im, row_scale, y, x_spectra, workspace, workspace_bytes, SMX_IO_F32,
+                           stream);
+}
 
-int smx_conv_backward(const smx_shape* shape, const float* g, const float* x_spectra, const float* h_re,
-                      const float* h_im, const float* row_scale, float* grad_x, float* grad_h_re,
-                      float* grad_h_im, float* grad_row_scale, void* workspace, size_t workspace_bytes,
-                      void* stream) {
+static int conv_backward_impl(const smx_shape* shape, const float* g, const float* x_spectra, const float* h_re,
+                              const float* h_im, const float* row_scale, float* grad_x, float* grad_h_re,
+                              float* grad_h_im, float* grad_row_scale, void* workspace, size_t workspace_bytes,
+                              int io, void* stream) {
   Shape h; Plan p;
   if (int rc = conv_shape(shape, &h)) return rc;
   if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, "smx_conv_* needs n_fft = 512 ... 65536 (a power of two), rows <= n_fft and an even channel count");
+  if (io != SMX_IO_F32 && !p.conv1) return fail(SMX_ERR_UNSUPPORTED, "%s", CONV_IO_PLANS);
   if (!g || !x_spectra || !grad_x) return fail(SMX_ERR_INVALID, "g, x_spectra, grad_x must be non-NULL");
-  if (((uintptr_t)g | (uintptr_t)grad_x | (uintptr_t)x_spectra) & 7)
+  if (io != SMX_IO_F32) {
+    if (((uintptr_t)g | (uintptr_t)grad_x) & 3)
+      return fail(SMX_ERR_INVALID, "2-byte g and grad_x must be 4-byte aligned");
+    if ((uintptr_t)x_spectra & 7) return fail(SMX_ERR_INVALID, "x_spectra must be 8-byte aligned");
+  } else if (((uintptr_t)g | (uintptr_t)grad_x | (uintptr_t)x_spectra) & 7)
     return fail(SMX_ERR_INVALID, "g, grad_x, x_spectra must be 8-byte aligned");
   if ((grad_h_re == nullptr) != (grad_h_im == nullptr))
     return fail(SMX_ERR_INVALID, "grad_h_re and grad_h_im must be given together");
@@ -1240,11 +1288,12 @@ int smx_conv_backward(const smx_shape* shape, const float* g, const float* x_spe
   const ConvWs w = conv_ws(p, h);
   DecimArgs a;
   TableRef t;
-  if (int rc = conv_args(h, p, w, workspace, workspace_bytes, h_re, h_im, row_scale, s, t, &a)) return rc;
+  if (int rc = conv_args(h, p, w, workspace, workspace_bytes, h_re, h_im, row_scale, s, t, &a, io != SMX_IO_F32 ? 2 : 4))
+    return rc;
   a.in = g; a.out = grad_x;
   a.ca.xs = (const cf*)x_spectra;
   if (p.conv1) {
-    HIP_TRY(launch_conv1(a, p.conv1_nj, 1, grad_h_re, grad_h_im, grad_row_scale, s));
+    HIP_TRY(launch_conv1(a, p.conv1_nj, 1, grad_h_re, grad_h_im, grad_row_scale, s, io));
     return SMX_OK;
   }
   HIP_TRY(launch_fs_a(a, s));
@@ -1252,6 +1301,13 @@ int smx_conv_backward(const smx_shape* shape, const float* g, const float* x_spe
   HIP_TRY(launch_fs_conv(a, 1, grad_h_re, grad_h_im, grad_row_scale, s));
   HIP_TRY(launch_fs_b(a, s));
   return SMX_OK;
+}
+int smx_conv_backward(const smx_shape* shape, const float* g, const float* x_spectra, const float* h_re,
+                      const float* h_im, const float* row_scale, float* grad_x, float* grad_h_re,
+                      float* grad_h_im, float* grad_row_scale, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+  return conv_backward_impl(shape, g, x_spectra, h_re, h_im, row_scale, grad_x, grad_h_re, grad_h_im, grad_row_scale,
+                            workspace, workspace_bytes, SMX_IO_F32, stream);
 }
 
 int smx_phase_filter(const float* magnitude, const float* phase, int D, int k, int n_fft, float* w_re, float* w_im,
@@ -1903,17 +1959,9 @@ int smx_gate_blend_backward(const float* g3, const float* a, const float* v, con
 // ---- 2-byte activations (bf16 / fp16 x, y, g, grad_x) ---------------------------------------------------------------
 // Replaces: reference fft_tensor/spectral_layers.py:88 (fft), :94-109 (filter), :112-116 (ifft, bias) and their autograd
 // backward for half-precision activations (the reference's torch.fft refuses bf16 and takes fp16 for powers of two only).
-// Same plan, launches, work items and summation order as the f32 entries; only the streaming kernels' row I/O differs
-// (k_fused_io / k_split_a_io / k_split_b_io), so the outputs are the f32 outputs rounded once (include/smx.h).
-static bool io_native(const Plan& p) {
-  return p.path == SMX_PATH_DECIMATED && p.groups == 1 && !p.fs && !p.full8;
-}
-static int io_check(int io) {
-  if (io != SMX_IO_F32 && io != SMX_IO_BF16 && io != SMX_IO_F16)
-    return fail(SMX_ERR_INVALID, "io must be SMX_IO_F32, SMX_IO_BF16 or SMX_IO_F16, got %d", io);
-  return SMX_OK;
-}
-
+// Same implementation (forward_impl / backward_impl), plan, launches, work items and summation order as the f32
+// entries; only the streaming kernels' row I/O differs (the IO instances of k_fused / k_split_a / k_split_b), so the
+// outputs are the f32 outputs rounded once (include/smx.h).
 int smx_io_supported(int B, int N, int D, int F, int io) {
   if (io_check(io) || check_shape(B, N, D, F)) return 0;
   if (io == SMX_IO_F32) return 1;
@@ -1924,48 +1972,9 @@ int smx_forward_io(const void* x, const float* w_re, const float* w_im, const fl
                    float* xk_save, void* workspace, size_t workspace_bytes, int B, int N, int D, int F,
                    int conj_w, float dropout_p, const void* rng_state, float* filter_pack, void* stream, int io) {
   if (int rc = io_check(io)) return rc;
-  if (io == SMX_IO_F32)
-    return smx_forward_dropout((const float*)x, w_re, w_im, bias, (float*)y, xk_save, workspace, workspace_bytes, B, N,
-                               D, F, conj_w, dropout_p, rng_state, filter_pack, stream);
   if (int rc = check_shape(B, N, D, F)) return rc;
-  const Shape h = layer_shape(B, N, D, F);
-  DropCfg dc;
-  if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
-  const bool pack_ready = (conj_w & SMX_FILTER_PACK_READY) != 0;
-  conj_w &= 1;
-  if (pack_ready && !filter_pack) return fail(SMX_ERR_INVALID, "SMX_FILTER_PACK_READY without filter_pack");
-  if (!x || !w_re || !w_im || !y) return fail(SMX_ERR_INVALID, "x, w_re, w_im, y must be non-NULL");
-  if (((uintptr_t)x | (uintptr_t)y) & 3) return fail(SMX_ERR_INVALID, "2-byte x and y must be 4-byte aligned");
-  if ((uintptr_t)xk_save & 15) return fail(SMX_ERR_INVALID, "xk_save must be 16-byte aligned");
-  const Plan p = make_plan(h);
-  if (!io_native(p))
-    return fail(SMX_ERR_UNSUPPORTED, "no 2-byte I/O on this plan (smx_io_supported): widen the input and call "
-                "smx_forward_dropout");
-  hipStream_t s = (hipStream_t)stream;
-  const Ws w = ws_layout(p, B, N, D);
-  if (p.nsplit > 1) if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
-  TableRef t;
-  if (int rc = get_tables(N, &t, s)) return rc;
-  char* ws = (char*)workspace;
-  DecimArgs a = decim_args(p, t, h, ws, w, 2);
-  a.in = (const float*)x; a.out = (float*)y;                 // 2-byte rows: read by the k_*_io kernels only
-  a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.bias = bias; a.fa.conj_w = conj_w;
-  a.fa.xk_out = xk_save;
-  set_drop(a, dc);
-  if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F,
-                           pack_ready ? filter_pack : nullptr, pack_ready ? nullptr : filter_pack, s))
-    return rc;
-  if (p.nsplit == 1) {
-    if (workspace && workspace_bytes >= w.total && !((uintptr_t)workspace & 255) &&
-        sync_words(B, D) * sizeof(unsigned) <= SYNC_BYTES)
-      a.sync = (unsigned*)(ws + w.sync);
-    HIP_TRY(launch_fused_io(a, p.nb, 0, io, s));
-  } else {
-    HIP_TRY(launch_split_a_io(a, p.nb, false, io, s));
-    HIP_TRY(launch_split_f(a, p.nb, 0, s));
-    HIP_TRY(launch_split_b_io(a, p.nb, true, io, s));
-  }
-  return SMX_OK;
+  return forward_impl(layer_shape(B, N, D, F), (const float*)x, w_re, w_im, bias, (float*)y, xk_save, workspace,
+                      workspace_bytes, conj_w, dropout_p, rng_state, filter_pack, stream, nullptr, io);
 }
 
 int smx_backward_io(const void* g, const float* xk, const float* w_re, const float* w_im, void* grad_x,
@@ -1973,69 +1982,17 @@ int smx_backward_io(const void* g, const float* xk, const float* w_re, const flo
                     int N, int D, int F, int phases, float dropout_p, const void* rng_state,
                     const float* filter_pack, void* stream, int io) {
   if (int rc = io_check(io)) return rc;
-  if (io == SMX_IO_F32)
-    return smx_backward_dropout((const float*)g, xk, w_re, w_im, (float*)grad_x, gw_re, gw_im, gbias, workspace,
-                                workspace_bytes, B, N, D, F, phases, dropout_p, rng_state, filter_pack, stream);
   if (int rc = check_shape(B, N, D, F)) return rc;
-  const Shape h = layer_shape(B, N, D, F);
-  DropCfg dc;
-  if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
-  if (!g || !w_re || !w_im) return fail(SMX_ERR_INVALID, "g, w_re, w_im must be non-NULL");
-  phases &= ~SMX_PHASE_SYNC_CLEAN;              // (no folded reduction here: the sync area is not used)
-  if (phases < 1 || phases > 7) return fail(SMX_ERR_INVALID, "phases must be a combination of 1, 2, 4");
-  if ((phases & SMX_PHASE_INVERSE) && !grad_x) return fail(SMX_ERR_INVALID, "grad_x is NULL");
-  const bool want_w = gw_re || gw_im || gbias;
-  if (want_w && !(gw_re && gw_im && gbias)) return fail(SMX_ERR_INVALID, "gw_re, gw_im, gbias must be given together");
-  if (((uintptr_t)g | (uintptr_t)grad_x) & 3) return fail(SMX_ERR_INVALID, "2-byte g and grad_x must be 4-byte aligned");
-  if ((uintptr_t)xk & 15) return fail(SMX_ERR_INVALID, "xk must be 16-byte aligned");
-  const Plan p = make_plan(h);
-  if (!io_native(p))
-    return fail(SMX_ERR_UNSUPPORTED, "no 2-byte I/O on this plan (smx_io_supported): widen g and call "
-                "smx_backward_dropout");
-  if ((want_w || dc.thr) && !xk && p.k > 0) return fail(SMX_ERR_INVALID, "xk (saved spectrum) is NULL");
-  hipStream_t s = (hipStream_t)stream;
-  const Ws w = ws_layout(p, B, N, D);
-  if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
-  TableRef t;
-  if (int rc = get_tables(N, &t, s)) return rc;
-  char* ws = (char*)workspace;
-  const bool do_spec = phases & SMX_PHASE_SPECTRUM, do_inv = phases & SMX_PHASE_INVERSE;
-  const bool do_par = (phases & SMX_PHASE_PARAMS) && want_w;
-  DecimArgs a = decim_args(p, t, h, ws, w, 2);
-  a.in = (const float*)g; a.out = (float*)grad_x;            // 2-byte rows: read by the k_*_io kernels only
-  a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.conj_w = 1;
-  a.fa.xk_in = xk; a.fa.pslab = (float*)(ws + w.slab); a.fa.gb_part = (float*)(ws + w.gbp);
-  set_drop(a, dc);
-  const int mode = (want_w || dc.thr) ? 1 : 0;                // (the mask is applied by the mode-1 load)
-  if (do_spec)
-    if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F, filter_pack, nullptr, s)) return rc;
-  if (do_spec && do_inv && p.nsplit == 1) {
-    HIP_TRY(launch_fused_io(a, p.nb, mode, io, s));
-  } else {
-    if (do_spec) {
-      if (p.nsplit == 1) {             // forward half + filter in one launch, S parked in the workspace
-        DecimArgs sp = a;
-        sp.out = nullptr;
-        HIP_TRY(launch_fused_io(sp, p.nb, mode, io, s));
-      } else {
-        HIP_TRY(launch_split_a_io(a, p.nb, true, io, s));
-        HIP_TRY(launch_split_f(a, p.nb, mode, s));
-      }
-    }
-    if (do_inv) HIP_TRY(launch_split_b_io(a, p.nb, false, io, s));
-  }
-  if (do_par)
-    HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, B, D, F, p.k, s));
-  return SMX_OK;
+  return backward_impl(layer_shape(B, N, D, F), (const float*)g, xk, w_re, w_im, (float*)grad_x, gw_re, gw_im, gbias,
+                       workspace, workspace_bytes, phases, dropout_p, rng_state, filter_pack, stream, nullptr, nullptr,
+                       io);
 }
 
 // ---- 2-byte activations of the convolution (bf16 / fp16 x, y, g, grad_x) -------------------------------------------
 // Replaces: reference fft_lm/train_fixed_full.py:515-555 and its autograd backward for half-precision activations.
-// Same plan, launch, work items and summation order as smx_conv_forward / smx_conv_backward; only k_conv1's row I/O
-// differs (its IO instances), so the outputs are the f32 outputs rounded once (include/smx.h).
-static const char* const CONV_IO_PLANS = "no 2-byte I/O on this plan (smx_conv_io_supported: the single-launch plan, "
-                                         "n_fft <= 2048): widen the input and call the f32 entry";
-
+// Same implementation (conv_forward_impl / conv_backward_impl), plan, launch, work items and summation order as
+// smx_conv_forward / smx_conv_backward; only k_conv1's row I/O differs (its IO instances), so the outputs are the
+// f32 outputs rounded once (include/smx.h).
 int smx_conv_io_supported(const smx_shape* shape, int io) {
   Shape h; Plan p;
   if (io_check(io) || conv_shape(shape, &h) || !conv_plan(h, &p)) return 0;
@@ -2046,25 +2003,8 @@ int smx_conv_forward_io(const smx_shape* shape, const void* x, const float* h_re
                         const float* row_scale, void* y, float* x_spectra, void* workspace,
                         size_t workspace_bytes, int io, void* stream) {
   if (int rc = io_check(io)) return rc;
-  if (io == SMX_IO_F32)
-    return smx_conv_forward(shape, (const float*)x, h_re, h_im, row_scale, (float*)y, x_spectra, workspace,
-                            workspace_bytes, stream);
-  Shape h; Plan p;
-  if (int rc = conv_shape(shape, &h)) return rc;
-  if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, "smx_conv_* needs n_fft = 512 ... 65536 (a power of two), rows <= n_fft and an even channel count");
-  if (!p.conv1) return fail(SMX_ERR_UNSUPPORTED, "%s", CONV_IO_PLANS);
-  if (!x || !y) return fail(SMX_ERR_INVALID, "x and y must be non-NULL");
-  if (((uintptr_t)x | (uintptr_t)y) & 3) return fail(SMX_ERR_INVALID, "2-byte x and y must be 4-byte aligned");
-  if ((uintptr_t)x_spectra & 7) return fail(SMX_ERR_INVALID, "x_spectra must be 8-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const ConvWs w = conv_ws(p, h);
-  DecimArgs a;
-  TableRef t;
-  if (int rc = conv_args(h, p, w, workspace, workspace_bytes, h_re, h_im, row_scale, s, t, &a, 2)) return rc;
-  a.in = (const float*)x; a.out = (float*)y;                 // 2-byte rows: read by k_conv1's IO instances only
-  a.ws_f = (cf*)x_spectra;                                   // packed spectrum of x for backward, or NULL (inference)
-  HIP_TRY(launch_conv1(a, p.conv1_nj, 0, nullptr, nullptr, nullptr, s, io));
-  return SMX_OK;
+  return conv_forward_impl(shape, (const float*)x, h_re, h_im, row_scale, (float*)y, x_spectra, workspace,
+                           workspace_bytes, io, stream);
 }
 
 int smx_conv_backward_io(const smx_shape* shape, const void* g, const float* x_spectra, const float* h_re,
@@ -2072,27 +2012,8 @@ int smx_conv_backward_io(const smx_shape* shape, const void* g, const float* x_s
                          float* grad_h_im, float* grad_row_scale, void* workspace, size_t workspace_bytes,
                          int io, void* stream) {
   if (int rc = io_check(io)) return rc;
-  if (io == SMX_IO_F32)
-    return smx_conv_backward(shape, (const float*)g, x_spectra, h_re, h_im, row_scale, (float*)grad_x, grad_h_re,
-                             grad_h_im, grad_row_scale, workspace, workspace_bytes, stream);
-  Shape h; Plan p;
-  if (int rc = conv_shape(shape, &h)) return rc;
-  if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, "smx_conv_* needs n_fft = 512 ... 65536 (a power of two), rows <= n_fft and an even channel count");
-  if (!p.conv1) return fail(SMX_ERR_UNSUPPORTED, "%s", CONV_IO_PLANS);
-  if (!g || !x_spectra || !grad_x) return fail(SMX_ERR_INVALID, "g, x_spectra, grad_x must be non-NULL");
-  if (((uintptr_t)g | (uintptr_t)grad_x) & 3) return fail(SMX_ERR_INVALID, "2-byte g and grad_x must be 4-byte aligned");
-  if ((uintptr_t)x_spectra & 7) return fail(SMX_ERR_INVALID, "x_spectra must be 8-byte aligned");
-  if ((grad_h_re == nullptr) != (grad_h_im == nullptr))
-    return fail(SMX_ERR_INVALID, "grad_h_re and grad_h_im must be given together");
-  hipStream_t s = (hipStream_t)stream;
-  const ConvWs w = conv_ws(p, h);
-  DecimArgs a;
-  TableRef t;
-  if (int rc = conv_args(h, p, w, workspace, workspace_bytes, h_re, h_im, row_scale, s, t, &a, 2)) return rc;
-  a.in = (const float*)g; a.out = (float*)grad_x;            // 2-byte rows: read by k_conv1's IO instances only
-  a.ca.xs = (const cf*)x_spectra;
-  HIP_TRY(launch_conv1(a, p.conv1_nj, 1, grad_h_re, grad_h_im, grad_row_scale, s, io));
-  return SMX_OK;
+  return conv_backward_impl(shape, (const float*)g, x_spectra, h_re, h_im, row_scale, (float*)grad_x, grad_h_re,
+                            grad_h_im, grad_row_scale, workspace, workspace_bytes, io, stream);
 }
 
 }  // extern "C"

@@ -341,13 +341,21 @@ __device__ __forceinline__ void gradw_tail(const DecimArgs& a, cf* lds, int cb) 
 // ACC (band groups after the first, k > 512): the launch adds its bins' contribution to what the
 // earlier groups stored, read-modify-write per tile by the workgroup that owns it.
 // PAD: x / y hold R < N rows (zero-padded transform, cropped output).
-template <int NB, int MODE, bool DROP = false, bool ACC = false, bool PAD = false>
+// IO: element type of the streamed rows of a.in / a.out (RowBufT, smx_launch.h): 0 f32, 1 bf16, 2 fp16.  Only the row
+// I/O differs: the same work items and residue rotation (wg_map -- the order in which a workgroup accumulates its
+// residues), the same tile arithmetic, f32 spectra.  The 2-byte results are therefore the f32 kernel's results on
+// the widened input, rounded once at the store.  IO != 0 never holds the folded
+// parameter-gradient reduction (no gradw_tail, no __builtin_trap, no extra registers: the half backward reduces in
+// k_gradw, bitwise the same sums), and only the configurations smx_api routes there are instantiated (launch_fused).
+template <int NB, int MODE, bool DROP = false, bool ACC = false, bool PAD = false, int IO = 0>
 __global__ __launch_bounds__(TPB, 2) void k_fused(const DecimArgs a) {
   SMX_LDS_DECL;
   const Geom& g = a.g;
   const int tid = threadIdx.x, j = tid & 15, t = tid >> 4;
   const int ndt = (g.D + DT - 1) / DT;
-  if constexpr (MODE == 1 && !ACC && NB <= 2) {     // (four bands: no register room, smx_api keeps k_gradw)
+  // (four bands: no register room, smx_api keeps k_gradw; 2-byte rows: never, see above)
+  constexpr bool FOLD_GRADW = MODE == 1 && !ACC && NB <= 2 && IO == 0;
+  if constexpr (FOLD_GRADW) {
     if (a.n_cons > 0 && a.bid0 + (int)blockIdx.x >= g.B * ndt) {      // appended reduction workgroup
       gradw_tail(a, lds, a.bid0 + (int)blockIdx.x - g.B * ndt);
       return;
@@ -356,7 +364,9 @@ __global__ __launch_bounds__(TPB, 2) void k_fused(const DecimArgs a) {
   const WgItem w = wg_map(a.bid0 + blockIdx.x, g.B, ndt, 1, g.L, a.placement);
   const int b = w.b, d = w.dt * DT + 2 * j, rot = w.rot;
   const bool valid = d < g.D;
-  const RowBuf xb = row_buf(a.in + (size_t)b * g.R * g.D, g, t, valid ? d : g.D - 2);
+  RowBufT<IO> xb;
+  if constexpr (IO == 0) xb = row_buf(a.in + (size_t)b * g.R * g.D, g, t, valid ? d : g.D - 2);
+  else xb = row_buf<IO>(a.in, b, g, t, valid ? d : g.D - 2);
 
   if constexpr (MODE == 0 && !ACC) {       // forward: leave the sync area of this workspace zero for the backward
     if (a.sync != nullptr && a.bid0 + (int)blockIdx.x == 0)       // call that trusts it (SMX_PHASE_SYNC_CLEAN)
@@ -393,10 +403,12 @@ __global__ __launch_bounds__(TPB, 2) void k_fused(const DecimArgs a) {
     return;
   }
   __syncthreads();
-  const RowBuf yb = row_buf(a.out + (size_t)b * g.R * g.D, g, t, d, valid);   // (ACC: also read back)
+  RowBufT<IO> yb;   // (ACC: also read back)
+  if constexpr (IO == 0) yb = row_buf(a.out + (size_t)b * g.R * g.D, g, t, d, valid);
+  else yb = row_buf<IO>(a.out, b, g, t, d, valid);
   inverse_loop<NB, ACC, DROP && MODE == 0, PAD>(st, lds, yb, a, t, j, 0, g.L, rot, yb, dr, pj);
   if constexpr (NB == 1) store_io<NB, MODE>(st, g, a.fa, b, d, valid, t);     // saved spectrum / grad slab
-  if constexpr (MODE == 1 && !ACC && NB <= 2) {     // (four bands: no register room, smx_api keeps k_gradw)
+  if constexpr (FOLD_GRADW) {
     if (a.n_cons > 0) {        // tell the appended reduction workgroups that this (b, d-tile)'s slab rows are out
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's write-through stores have landed
       __syncthreads();
@@ -702,7 +714,7 @@ __global__ __launch_bounds__(TPB, NB > 2 ? 1 : 2) void k_fused_blk(const DecimAr
 }
 
 // ---- split path: (A) partial forward over a chunk of residues ---------------------------------
-template <int NB, bool DROP = false, bool PAD = false>
+template <int NB, bool DROP = false, bool PAD = false, int IO = 0>
 __global__ __launch_bounds__(TPB, 2) void k_split_a(const DecimArgs a) {
   SMX_LDS_DECL;
   const Geom& g = a.g;
@@ -712,7 +724,9 @@ __global__ __launch_bounds__(TPB, 2) void k_split_a(const DecimArgs a) {
   const int c = w.c, b = w.b, wg = b * ndt + w.dt, d = w.dt * DT + 2 * j;
   const bool valid = d < g.D;
   const int rbeg = c * a.lc, cnt = min(a.lc, g.L - rbeg);
-  const RowBuf xb = row_buf(a.in + (size_t)b * g.R * g.D, g, t, valid ? d : g.D - 2);
+  RowBufT<IO> xb;
+  if constexpr (IO == 0) xb = row_buf(a.in + (size_t)b * g.R * g.D, g, t, valid ? d : g.D - 2);
+  else xb = row_buf<IO>(a.in, b, g, t, valid ? d : g.D - 2);
   const int rot = w.rot % cnt;
 
   TState<NB> st;
@@ -807,7 +821,7 @@ __global__ __launch_bounds__(TPB, NB > 1 ? 1 : 2) void k_split_f(const DecimArgs
 // (B) inverse over a chunk of residues, from the filtered spectrum parked by k_split_f / k_fused.
 // (Folding the unpack + filter into this launch was measured: every chunk workgroup repeating the
 // latency-bound prologue cost 33 us at C3, against 15 us for the separate B*ndt-block launch.)
-template <int NB, bool DROP = false, bool ACC = false, bool PAD = false>
+template <int NB, bool DROP = false, bool ACC = false, bool PAD = false, int IO = 0>
 __global__ __launch_bounds__(TPB, 2) void k_split_b(const DecimArgs a) {
   SMX_LDS_DECL;
   const Geom& g = a.g;
@@ -822,103 +836,13 @@ __global__ __launch_bounds__(TPB, 2) void k_split_b(const DecimArgs a) {
   const cf* s = a.ws_s + (size_t)wg * (16 * NB * TPB);
 #pragma unroll
   for (int sl = 0; sl < 16 * NB; ++sl) st.acc[sl] = s[sl * TPB + tid];
-  const RowBuf yb = row_buf(a.out + (size_t)b * g.R * g.D, g, t, d, valid);
+  RowBufT<IO> yb;
+  if constexpr (IO == 0) yb = row_buf(a.out + (size_t)b * g.R * g.D, g, t, d, valid);
+  else yb = row_buf<IO>(a.out, b, g, t, d, valid);
   Drop dr{};
   if constexpr (DROP) dr = make_drop(a, b);
   inverse_loop<NB, ACC, DROP, PAD>(st, lds, yb, a, t, j, rbeg, cnt, rot, yb, dr,
                                    (unsigned)((valid ? d : g.D - 2) >> 1));
-}
-
-// ---- 2-byte activations: bf16 / fp16 x, y, g, grad_x (IO = SMX_IO_BF16 / SMX_IO_F16) ------------------------------
-// k_fused / k_split_a / k_split_b with the streamed rows in 2-byte elements (RowBufIO, smx_launch.h) and everything
-// else unchanged: the same work items and residue rotation (wg_map -- the order in which a workgroup accumulates
-// its residues), the same tile arithmetic, f32 spectra.  The results are therefore the f32 kernels' results on the
-// widened input, rounded once at the store.  Only the configurations smx_api routes here
-// exist: no zero-padded rows, no accumulating band groups, no folded parameter-gradient reduction (the half
-// backward reduces in k_gradw, bitwise the same sums as gradw_tail).
-template <int NB, int MODE, int IO, bool DROP>
-__global__ __launch_bounds__(TPB, 2) void k_fused_io(const DecimArgs a) {
-  SMX_LDS_DECL;
-  const Geom& g = a.g;
-  const int tid = threadIdx.x, j = tid & 15, t = tid >> 4;
-  const int ndt = (g.D + DT - 1) / DT;
-  const WgItem w = wg_map(a.bid0 + blockIdx.x, g.B, ndt, 1, g.L, a.placement);
-  const int b = w.b, d = w.dt * DT + 2 * j, rot = w.rot;
-  const bool valid = d < g.D;
-  const RowBufIO<IO> xb = row_buf_io<IO>(a.in, b, g, t, valid ? d : g.D - 2);
-  if constexpr (MODE == 0) {               // as k_fused: the sync area of this workspace left zero
-    if (a.sync != nullptr && a.bid0 + (int)blockIdx.x == 0)
-      for (int i = tid; i <= g.B * ndt; i += TPB) a.sync[i] = 0u;
-  }
-  TState<NB> st;
-  zero_acc<NB>(st);
-  if constexpr (NB == 1) prefetch_io<NB, MODE>(st, g, a.fa, b, d, valid, t);
-  WPre wp;
-  constexpr bool STAGE_W = NB == 1 && MODE != 2;
-  if constexpr (STAGE_W) prefetch_w(wp, g, a.fa.w_re, a.fa.w_im, w.dt * DT, tid);
-  Drop dr{};
-  if constexpr (DROP) dr = make_drop(a, b);
-  const unsigned pj = (unsigned)((valid ? d : g.D - 2) >> 1);
-  forward_loop<NB, false, DROP && MODE == 1, false>(st, lds, xb, a, t, j, 0, g.L, rot, nullptr, dr, pj);
-  unpack_filter<NB, MODE, false>(st, lds, g, a.fa, b, d, valid, t, j, STAGE_W ? &wp : nullptr);
-  if (a.out == nullptr) {
-    if constexpr (NB == 1) store_io<NB, MODE>(st, g, a.fa, b, d, valid, t);
-    if (a.ws_s != nullptr) {               // phase-split backward: the filtered spectrum parked for k_split_b_io
-      cf* s = a.ws_s + (size_t)(b * ndt + w.dt) * (16 * NB * TPB);
-#pragma unroll
-      for (int sl = 0; sl < 16 * NB; ++sl) s[sl * TPB + tid] = st.acc[sl];
-    }
-    return;
-  }
-  __syncthreads();
-  const RowBufIO<IO> yb = row_buf_io<IO>(a.out, b, g, t, d, valid);
-  inverse_loop<NB, false, DROP && MODE == 0, false>(st, lds, yb, a, t, j, 0, g.L, rot, yb, dr, pj);
-  if constexpr (NB == 1) store_io<NB, MODE>(st, g, a.fa, b, d, valid, t);
-}
-
-template <int NB, int IO, bool DROP>
-__global__ __launch_bounds__(TPB, 2) void k_split_a_io(const DecimArgs a) {
-  SMX_LDS_DECL;
-  const Geom& g = a.g;
-  const int tid = threadIdx.x, j = tid & 15, t = tid >> 4;
-  const int ndt = (g.D + DT - 1) / DT;
-  const WgItem w = wg_map(a.bid0 + blockIdx.x, g.B, ndt, a.nsplit, a.lc, a.placement);
-  const int c = w.c, b = w.b, wg = b * ndt + w.dt, d = w.dt * DT + 2 * j;
-  const bool valid = d < g.D;
-  const int rbeg = c * a.lc, cnt = min(a.lc, g.L - rbeg);
-  const RowBufIO<IO> xb = row_buf_io<IO>(a.in, b, g, t, valid ? d : g.D - 2);
-  const int rot = w.rot % cnt;
-  TState<NB> st;
-  zero_acc<NB>(st);
-  Drop dr{};
-  if constexpr (DROP) dr = make_drop(a, b);
-  forward_loop<NB, false, DROP, false>(st, lds, xb, a, t, j, rbeg, cnt, rot, nullptr, dr,
-                                       (unsigned)((valid ? d : g.D - 2) >> 1));
-  cf* z = a.ws_z + ((size_t)wg * a.nsplit + c) * (16 * NB * TPB);
-#pragma unroll
-  for (int sl = 0; sl < 16 * NB; ++sl) z[sl * TPB + tid] = st.acc[sl];
-}
-
-template <int NB, int IO, bool DROP>
-__global__ __launch_bounds__(TPB, 2) void k_split_b_io(const DecimArgs a) {
-  SMX_LDS_DECL;
-  const Geom& g = a.g;
-  const int tid = threadIdx.x, j = tid & 15, t = tid >> 4;
-  const int ndt = (g.D + DT - 1) / DT;
-  const WgItem w = wg_map(a.bid0 + blockIdx.x, g.B, ndt, a.nsplit, a.lc, a.placement);
-  const int c = w.c, b = w.b, wg = b * ndt + w.dt, d = w.dt * DT + 2 * j;
-  const bool valid = d < g.D;
-  const int rbeg = c * a.lc, cnt = min(a.lc, g.L - rbeg);
-  const int rot = w.rot % cnt;
-  TState<NB> st;
-  const cf* s = a.ws_s + (size_t)wg * (16 * NB * TPB);
-#pragma unroll
-  for (int sl = 0; sl < 16 * NB; ++sl) st.acc[sl] = s[sl * TPB + tid];
-  const RowBufIO<IO> yb = row_buf_io<IO>(a.out, b, g, t, d, valid);
-  Drop dr{};
-  if constexpr (DROP) dr = make_drop(a, b);
-  inverse_loop<NB, false, DROP, false>(st, lds, yb, a, t, j, rbeg, cnt, rot, yb, dr,
-                                       (unsigned)((valid ? d : g.D - 2) >> 1));
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
@@ -943,35 +867,51 @@ static void launch_fused_acc(const DecimArgs& a, int mode, dim3 grid, hipStream_
   else hipLaunchKernelGGL((k_fused<4, 1, false, true>), grid, dim3(TPB), 0, s, a);
 }
 
-template <int NB>
+// 2-byte rows (io = SMX_IO_BF16 / SMX_IO_F16): only the instances smx_api routes to exist -- modes 0 and 1 with and
+// without dropout, no zero-padded rows, no accumulating band groups.  The launchers refuse everything else
+// (hipErrorInvalidValue) before the first launch: an f32 instance must never read 2-byte rows.
+static bool io_instance(const DecimArgs& a, int io) {
+  return io == 0 || ((io == 1 || io == 2) && !(a.g.R < a.g.N) && !a.accumulate);
+}
+
+template <int NB, int IO>
 static void launch_fused_t(const DecimArgs& a, int mode, dim3 grid, hipStream_t s) {
   const bool drop = a.drop_thr != 0;     // mode 0: on the stored tile, mode 1: on the loaded tile
-  if (a.g.R < a.g.N) {                   // zero-padded rows (never together with dropout, smx_api)
-    if (mode == 0) hipLaunchKernelGGL((k_fused<NB, 0, false, false, true>), grid, dim3(TPB), 0, s, a);
-    else if (mode == 1) hipLaunchKernelGGL((k_fused<NB, 1, false, false, true>), grid, dim3(TPB), 0, s, a);
-    else hipLaunchKernelGGL((k_fused<NB, 2, false, false, true>), grid, dim3(TPB), 0, s, a);
-    return;
+  if constexpr (IO == 0) {
+    if (a.g.R < a.g.N) {                 // zero-padded rows (never together with dropout, smx_api)
+      if (mode == 0) hipLaunchKernelGGL((k_fused<NB, 0, false, false, true>), grid, dim3(TPB), 0, s, a);
+      else if (mode == 1) hipLaunchKernelGGL((k_fused<NB, 1, false, false, true>), grid, dim3(TPB), 0, s, a);
+      else hipLaunchKernelGGL((k_fused<NB, 2, false, false, true>), grid, dim3(TPB), 0, s, a);
+      return;
+    }
+    if (mode != 0 && mode != 1) { hipLaunchKernelGGL((k_fused<NB, 2>), grid, dim3(TPB), 0, s, a); return; }
   }
-  if (mode == 0 && drop) hipLaunchKernelGGL((k_fused<NB, 0, true>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 0) hipLaunchKernelGGL((k_fused<NB, 0>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 1 && drop) hipLaunchKernelGGL((k_fused<NB, 1, true>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 1) hipLaunchKernelGGL((k_fused<NB, 1>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((k_fused<NB, 2>), grid, dim3(TPB), 0, s, a);
+  if (mode == 0 && drop) hipLaunchKernelGGL((k_fused<NB, 0, true, false, false, IO>), grid, dim3(TPB), 0, s, a);
+  else if (mode == 0) hipLaunchKernelGGL((k_fused<NB, 0, false, false, false, IO>), grid, dim3(TPB), 0, s, a);
+  else if (drop) hipLaunchKernelGGL((k_fused<NB, 1, true, false, false, IO>), grid, dim3(TPB), 0, s, a);
+  else hipLaunchKernelGGL((k_fused<NB, 1, false, false, false, IO>), grid, dim3(TPB), 0, s, a);
+}
+template <int IO>
+static void launch_fused_nb(const DecimArgs& a, int nb, int mode, dim3 grid, hipStream_t s) {
+  if (nb == 4) launch_fused_t<4, IO>(a, mode, grid, s);
+  else if (nb == 2) launch_fused_t<2, IO>(a, mode, grid, s);
+  else launch_fused_t<1, IO>(a, mode, grid, s);
 }
 
 int gradw_tail_blocks(int D, int F, bool bias) {
   return ((D + DT - 1) / DT) * ((F + GWT_BINS - 1) / GWT_BINS + (bias ? 1 : 0));
 }
 
-hipError_t launch_fused(const DecimArgs& a, int nb, int mode, hipStream_t s) {
+hipError_t launch_fused(const DecimArgs& a, int nb, int mode, hipStream_t s, int io) {
+  if (!io_instance(a, io) || (io != 0 && ((mode != 0 && mode != 1) || a.n_cons > 0))) return hipErrorInvalidValue;
   const int total = n_wg(a);
   return for_rounds(a, total, [&](const DecimArgs& r, dim3 grid) {
     // the reduction workgroups ride behind the LAST round's transform workgroups
     if (r.n_cons > 0 && r.bid0 + (int)grid.x >= total) grid.x += r.n_cons;
     if (r.accumulate && r.out != nullptr) launch_fused_acc(r, mode, grid, s);
-    else if (nb == 4) launch_fused_t<4>(r, mode, grid, s);
-    else if (nb == 2) launch_fused_t<2>(r, mode, grid, s);
-    else launch_fused_t<1>(r, mode, grid, s);
+    else if (io == 1) launch_fused_nb<1>(r, nb, mode, grid, s);
+    else if (io == 2) launch_fused_nb<2>(r, nb, mode, grid, s);
+    else launch_fused_nb<0>(r, nb, mode, grid, s);
   }, nb == 4);
 }
 
@@ -1074,20 +1014,31 @@ hipError_t launch_fused_block(const DecimArgs& a, int nb, hipStream_t s) {
   }, nb == 4);
 }
 
-hipError_t launch_split_a(const DecimArgs& a, int nb, bool drop_in, hipStream_t s) {
-  return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
-    const dim3 block(TPB);
+template <int IO>
+static void launch_split_a_t(const DecimArgs& r, int nb, bool drop_in, dim3 grid, hipStream_t s) {
+  const dim3 block(TPB);
+  if constexpr (IO == 0) {
     if (r.g.R < r.g.N) {
       if (nb == 4) hipLaunchKernelGGL((k_split_a<4, false, true>), grid, block, 0, s, r);
       else if (nb == 2) hipLaunchKernelGGL((k_split_a<2, false, true>), grid, block, 0, s, r);
       else hipLaunchKernelGGL((k_split_a<1, false, true>), grid, block, 0, s, r);
-    } else if (drop_in && r.drop_thr != 0) {
-      if (nb == 4) hipLaunchKernelGGL((k_split_a<4, true>), grid, block, 0, s, r);
-      else if (nb == 2) hipLaunchKernelGGL((k_split_a<2, true>), grid, block, 0, s, r);
-      else hipLaunchKernelGGL((k_split_a<1, true>), grid, block, 0, s, r);
-    } else if (nb == 4) hipLaunchKernelGGL((k_split_a<4>), grid, block, 0, s, r);
-    else if (nb == 2) hipLaunchKernelGGL((k_split_a<2>), grid, block, 0, s, r);
-    else hipLaunchKernelGGL((k_split_a<1>), grid, block, 0, s, r);
+      return;
+    }
+  }
+  if (drop_in && r.drop_thr != 0) {
+    if (nb == 4) hipLaunchKernelGGL((k_split_a<4, true, false, IO>), grid, block, 0, s, r);
+    else if (nb == 2) hipLaunchKernelGGL((k_split_a<2, true, false, IO>), grid, block, 0, s, r);
+    else hipLaunchKernelGGL((k_split_a<1, true, false, IO>), grid, block, 0, s, r);
+  } else if (nb == 4) hipLaunchKernelGGL((k_split_a<4, false, false, IO>), grid, block, 0, s, r);
+  else if (nb == 2) hipLaunchKernelGGL((k_split_a<2, false, false, IO>), grid, block, 0, s, r);
+  else hipLaunchKernelGGL((k_split_a<1, false, false, IO>), grid, block, 0, s, r);
+}
+hipError_t launch_split_a(const DecimArgs& a, int nb, bool drop_in, hipStream_t s, int io) {
+  if (!io_instance(a, io)) return hipErrorInvalidValue;
+  return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
+    if (io == 1) launch_split_a_t<1>(r, nb, drop_in, grid, s);
+    else if (io == 2) launch_split_a_t<2>(r, nb, drop_in, grid, s);
+    else launch_split_a_t<0>(r, nb, drop_in, grid, s);
   });
 }
 
@@ -1114,73 +1065,33 @@ hipError_t launch_split_f(const DecimArgs& a, int nb, int mode, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_split_b(const DecimArgs& a, int nb, bool drop_out, hipStream_t s) {
-  return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
-    const dim3 block(TPB);
+template <int IO>
+static void launch_split_b_t(const DecimArgs& r, int nb, bool drop_out, dim3 grid, hipStream_t s) {
+  const dim3 block(TPB);
+  if constexpr (IO == 0) {
     if (r.g.R < r.g.N) {
       if (r.accumulate) hipLaunchKernelGGL((k_split_b<4, false, true, true>), grid, block, 0, s, r);
       else if (nb == 1) hipLaunchKernelGGL((k_split_b<1, false, false, true>), grid, block, 0, s, r);
       else if (nb == 2) hipLaunchKernelGGL((k_split_b<2, false, false, true>), grid, block, 0, s, r);
       else hipLaunchKernelGGL((k_split_b<4, false, false, true>), grid, block, 0, s, r);
-    } else if (r.accumulate) hipLaunchKernelGGL((k_split_b<4, false, true>), grid, block, 0, s, r);
-    else if (drop_out && r.drop_thr != 0) {
-      if (nb == 1) hipLaunchKernelGGL((k_split_b<1, true>), grid, block, 0, s, r);
-      else if (nb == 2) hipLaunchKernelGGL((k_split_b<2, true>), grid, block, 0, s, r);
-      else hipLaunchKernelGGL((k_split_b<4, true>), grid, block, 0, s, r);
-    } else if (nb == 1) hipLaunchKernelGGL((k_split_b<1>), grid, block, 0, s, r);
-    else if (nb == 2) hipLaunchKernelGGL((k_split_b<2>), grid, block, 0, s, r);
-    else hipLaunchKernelGGL((k_split_b<4>), grid, block, 0, s, r);
-  });
+      return;
+    }
+    if (r.accumulate) { hipLaunchKernelGGL((k_split_b<4, false, true>), grid, block, 0, s, r); return; }
+  }
+  if (drop_out && r.drop_thr != 0) {
+    if (nb == 1) hipLaunchKernelGGL((k_split_b<1, true, false, false, IO>), grid, block, 0, s, r);
+    else if (nb == 2) hipLaunchKernelGGL((k_split_b<2, true, false, false, IO>), grid, block, 0, s, r);
+    else hipLaunchKernelGGL((k_split_b<4, true, false, false, IO>), grid, block, 0, s, r);
+  } else if (nb == 1) hipLaunchKernelGGL((k_split_b<1, false, false, false, IO>), grid, block, 0, s, r);
+  else if (nb == 2) hipLaunchKernelGGL((k_split_b<2, false, false, false, IO>), grid, block, 0, s, r);
+  else hipLaunchKernelGGL((k_split_b<4, false, false, false, IO>), grid, block, 0, s, r);
 }
-
-// 2-byte activations: one instance per (bands, mode, element type, dropout); the f32 launchers above are untouched
-template <int NB, int IO>
-static void launch_fused_io_t(const DecimArgs& r, int mode, dim3 grid, hipStream_t s) {
-  const dim3 block(TPB);
-  const bool drop = r.drop_thr != 0;
-  if (mode == 0 && drop) hipLaunchKernelGGL((k_fused_io<NB, 0, IO, true>), grid, block, 0, s, r);
-  else if (mode == 0) hipLaunchKernelGGL((k_fused_io<NB, 0, IO, false>), grid, block, 0, s, r);
-  else if (drop) hipLaunchKernelGGL((k_fused_io<NB, 1, IO, true>), grid, block, 0, s, r);
-  else hipLaunchKernelGGL((k_fused_io<NB, 1, IO, false>), grid, block, 0, s, r);
-}
-template <int IO>
-static void launch_fused_io_nb(const DecimArgs& r, int nb, int mode, dim3 grid, hipStream_t s) {
-  if (nb == 4) launch_fused_io_t<4, IO>(r, mode, grid, s);
-  else if (nb == 2) launch_fused_io_t<2, IO>(r, mode, grid, s);
-  else launch_fused_io_t<1, IO>(r, mode, grid, s);
-}
-hipError_t launch_fused_io(const DecimArgs& a, int nb, int mode, int io, hipStream_t s) {
-  return for_rounds(a, n_wg(a), [&](const DecimArgs& r, dim3 grid) {
-    if (io == 1) launch_fused_io_nb<1>(r, nb, mode, grid, s);
-    else launch_fused_io_nb<2>(r, nb, mode, grid, s);
-  }, nb == 4);
-}
-template <int IO, bool DROP>
-static void launch_split_a_io_t(const DecimArgs& r, int nb, dim3 grid, hipStream_t s) {
-  if (nb == 4) hipLaunchKernelGGL((k_split_a_io<4, IO, DROP>), grid, dim3(TPB), 0, s, r);
-  else if (nb == 2) hipLaunchKernelGGL((k_split_a_io<2, IO, DROP>), grid, dim3(TPB), 0, s, r);
-  else hipLaunchKernelGGL((k_split_a_io<1, IO, DROP>), grid, dim3(TPB), 0, s, r);
-}
-hipError_t launch_split_a_io(const DecimArgs& a, int nb, bool drop_in, int io, hipStream_t s) {
+hipError_t launch_split_b(const DecimArgs& a, int nb, bool drop_out, hipStream_t s, int io) {
+  if (!io_instance(a, io)) return hipErrorInvalidValue;
   return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
-    const bool dr = drop_in && r.drop_thr != 0;
-    if (io == 1) { if (dr) launch_split_a_io_t<1, true>(r, nb, grid, s); else launch_split_a_io_t<1, false>(r, nb, grid, s); }
-    else if (dr) launch_split_a_io_t<2, true>(r, nb, grid, s);
-    else launch_split_a_io_t<2, false>(r, nb, grid, s);
-  });
-}
-template <int IO, bool DROP>
-static void launch_split_b_io_t(const DecimArgs& r, int nb, dim3 grid, hipStream_t s) {
-  if (nb == 4) hipLaunchKernelGGL((k_split_b_io<4, IO, DROP>), grid, dim3(TPB), 0, s, r);
-  else if (nb == 2) hipLaunchKernelGGL((k_split_b_io<2, IO, DROP>), grid, dim3(TPB), 0, s, r);
-  else hipLaunchKernelGGL((k_split_b_io<1, IO, DROP>), grid, dim3(TPB), 0, s, r);
-}
-hipError_t launch_split_b_io(const DecimArgs& a, int nb, bool drop_out, int io, hipStream_t s) {
-  return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
-    const bool dr = drop_out && r.drop_thr != 0;
-    if (io == 1) { if (dr) launch_split_b_io_t<1, true>(r, nb, grid, s); else launch_split_b_io_t<1, false>(r, nb, grid, s); }
-    else if (dr) launch_split_b_io_t<2, true>(r, nb, grid, s);
-    else launch_split_b_io_t<2, false>(r, nb, grid, s);
+    if (io == 1) launch_split_b_t<1>(r, nb, drop_out, grid, s);
+    else if (io == 2) launch_split_b_t<2>(r, nb, drop_out, grid, s);
+    else launch_split_b_t<0>(r, nb, drop_out, grid, s);
   });
 }
 

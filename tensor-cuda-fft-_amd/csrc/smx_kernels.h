@@ -6,8 +6,8 @@
 namespace smx {
 
 struct DecimArgs {
-  const float* in;      // x (forward) or g (backward), (B,N,D) f32
-  float* out;           // y or grad_x, (B,N,D) f32; may be null (spectrum only)
+  const float* in;      // x (forward) or g (backward), (B,N,D) f32 -- or 2-byte rows behind the same pointer (io below)
+  float* out;           // y or grad_x, (B,N,D) likewise; may be null (spectrum only)
   const cf* tw;         // w_N^n, n < N
   const cf* bt;         // w_N^{16 s' r}, [L][32]
   const cf* tq;         // w_N^{q e}, [N/16][16] (N % 256 == 0): the inter-pass twiddles c^q of row-group t and residue
@@ -67,7 +67,10 @@ hipError_t launch_fused16(const DecimArgs& a, int nb, int mode, hipStream_t s);
 hipError_t launch_split16_a(const DecimArgs& a, int nb, bool drop_in, hipStream_t s);
 hipError_t launch_split16_b(const DecimArgs& a, int nb, bool drop_out, hipStream_t s);
 // fused single-launch path (nsplit == 1)
-hipError_t launch_fused(const DecimArgs& a, int nb, int mode, hipStream_t s);
+// io (here and in launch_split_a / launch_split_b): element type of the rows a.in / a.out point at (SMX_IO_*: 0 f32,
+// 1 bf16, 2 fp16 -- 2-byte rows, everything else f32).  io != 0 exists for modes 0 and 1 without zero-padded rows,
+// band groups (accumulate) or the folded parameter-gradient reduction (n_cons); anything else: hipErrorInvalidValue
+hipError_t launch_fused(const DecimArgs& a, int nb, int mode, hipStream_t s, int io = 0);
 // synthesis from a given one-sided spectrum (fa.xk_in, fa.sp_scale, fa.sp_herm): fused inverse, or the packed
 // spectrum parked for launch_split_b when out == NULL
 hipError_t launch_synth(const DecimArgs& a, int nb, hipStream_t s);
@@ -112,14 +115,9 @@ hipError_t launch_phase_filter_bwd(const float* m, const float* ph, const float*
 // forward of y = x + mix(LayerNorm(x)) in one launch (nsplit == 1 only)
 hipError_t launch_fused_block(const DecimArgs& a, int nb, hipStream_t s);
 // three-launch path: partial forward / combine+filter / inverse
-hipError_t launch_split_a(const DecimArgs& a, int nb, bool drop_in, hipStream_t s);
+hipError_t launch_split_a(const DecimArgs& a, int nb, bool drop_in, hipStream_t s, int io = 0);
 hipError_t launch_split_f(const DecimArgs& a, int nb, int mode, hipStream_t s);
-hipError_t launch_split_b(const DecimArgs& a, int nb, bool drop_out, hipStream_t s);
-// the same three streaming launches with 2-byte x / y (io = SMX_IO_BF16 or SMX_IO_F16; a.in / a.out point at
-// bf16 / fp16 rows): no zero-padded rows, no band groups, no folded parameter-gradient reduction
-hipError_t launch_fused_io(const DecimArgs& a, int nb, int mode, int io, hipStream_t s);
-hipError_t launch_split_a_io(const DecimArgs& a, int nb, bool drop_in, int io, hipStream_t s);
-hipError_t launch_split_b_io(const DecimArgs& a, int nb, bool drop_out, int io, hipStream_t s);
+hipError_t launch_split_b(const DecimArgs& a, int nb, bool drop_out, hipStream_t s, int io = 0);
 
 // elementwise dropout for the plans without a fused epilogue (direct path): out = mask * scale * in
 hipError_t launch_dropout_rows(const float* in, float* out, int B, long long row_elems, unsigned thr,

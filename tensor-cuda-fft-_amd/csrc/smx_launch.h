@@ -1,6 +1,7 @@
 // smx_launch.h -- pieces shared by the kernel translation units (smx_decim.hip, smx_fourstep.hip):
 // the LDS declaration, the workgroup -> work item map and the launch-in-rounds helper.
 #pragma once
+#include <type_traits>
 #include "smx_kernels.h"
 
 namespace smx {
@@ -53,88 +54,60 @@ __device__ __forceinline__ WgItem wg_map(int bid, int B, int ndt, int nsplit, in
 // 16 stores of a tile somewhere in the optimiser (llvm-objdump of the shipped kernel: 4 x `nt`, 12 x plain).
 // Zero-padded rows (PAD: x / y hold R < N rows): the row pitch moves into the per-thread offset, and the buffer's
 // range check (offset >= R D 4 bytes: loads return 0, stores are dropped) is the predicate.
-// Needs R D 4 < 2^31 (make_plan sends larger batch rows to the direct plan; R D 2 for the 2-byte tensors below).
+// Needs R D 4 < 2^31 (make_plan sends larger batch rows to the direct plan; R D 2 for 2-byte tensors, IO below).
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 constexpr int BUF_NT = 2;          // cache policy operand of the buffer intrinsics: slc = `nt` on gfx950
-struct RowBuf {
-  __amdgpu_buffer_rsrc_t rs;       // batch row b: base + b R D floats, R D 4 bytes
-  unsigned vo;                     // (t L D + d) 4: this thread's channel pair in row t L
-  unsigned su;                     // 16 L D 4: bytes between a thread's consecutive rows
-  unsigned rowb;                   // D 4
+// IO = element type of the streamed tensor (SMX_IO_*): 0 f32 -- a channel pair is buffer_load / buffer_store_dwordx2;
+// 1 bf16, 2 fp16 -- the same tile walk with the packed channel pair in ONE dword (buffer_load / buffer_store_dword),
+// every pitch and the range in 2-byte elements.  ES = bytes per element.
+template <int IO>
+struct RowBufT {
+  static constexpr unsigned ES = IO == 0 ? 4u : 2u;
+  __amdgpu_buffer_rsrc_t rs;       // batch row b: base + b R D elements, R D ES bytes
+  unsigned vo;                     // (t L D + d) ES: this thread's channel pair in row t L
+  unsigned su;                     // 16 L D ES: bytes between a thread's consecutive rows
+  unsigned rowb;                   // D ES
 };
+using RowBuf = RowBufT<0>;
+// row0 = the batch row, base + b R D elements (f32: the caller forms it, see below).
 // in_range = false (a lane whose channel pair lies past D): every offset the lane forms is 2^31 + (an offset inside
 // the batch row) -- in [2^31, 2^32), past any buffer and short of wrapping: its stores are dropped and its loads
 // return 0 without a branch around the tile code
-__device__ __forceinline__ RowBuf row_buf(const float* row0, const Geom& g, int t, int d, bool in_range = true) {
-  RowBuf rb;
-  rb.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row0), 0, (int)((unsigned)g.R * (unsigned)g.D * 4u),
+template <int IO = 0>
+__device__ __forceinline__ RowBufT<IO> row_buf(const void* row0, const Geom& g, int t, int d, bool in_range = true) {
+  constexpr unsigned ES = RowBufT<IO>::ES;
+  RowBufT<IO> rb;
+  rb.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(row0), 0, (int)((unsigned)g.R * (unsigned)g.D * ES),
                                             0x00020000);
-  rb.rowb = (unsigned)g.D * 4u;
-  rb.vo = in_range ? ((unsigned)t * (unsigned)g.L * (unsigned)g.D + (unsigned)d) * 4u : 0x80000000u;
+  rb.rowb = (unsigned)g.D * ES;
+  rb.vo = in_range ? ((unsigned)t * (unsigned)g.L * (unsigned)g.D + (unsigned)d) * ES : 0x80000000u;
   rb.su = 16u * (unsigned)g.L * rb.rowb;                 // (uniform: it is the instructions' scalar offset)
   return rb;
 }
-// rows u = U0 .. U0+CNT-1 of tile r: row (t + 16 u) L + r
-template <int U0, int CNT, bool PAD>
-__device__ __forceinline__ void load_rows(const RowBuf& rb, int r, cf (&v)[16]) {
-  const unsigned vr = rb.vo + (unsigned)r * rb.rowb;
-#pragma unroll
-  for (int u = U0; u < U0 + CNT; ++u) {
-    const u32x2 w = PAD ? __builtin_amdgcn_raw_buffer_load_b64(rb.rs, vr + (unsigned)u * rb.su, 0, BUF_NT)
-                        : __builtin_amdgcn_raw_buffer_load_b64(rb.rs, vr, (unsigned)u * rb.su, BUF_NT);
-    const unsigned wx = w.x, wy = w.y;      // (bit_cast straight from a vector ELEMENT reads element 0 twice: clang 22)
-    float fx = __builtin_bit_cast(float, wx), fy = __builtin_bit_cast(float, wy);
-    // two scalars from here on: left as <2 x float> the optimiser turns the first butterflies into v_pk_add_f32,
-    // which issue at half the rate of the scalar adds with two waves per SIMD (tools/probe_valu.hip, round 3)
-    asm("" : "+v"(fx));
-    asm("" : "+v"(fy));
-    v[u] = mk(fx, fy);
-  }
-}
-// plain (wave-uniform: 0, 1, 2 or 4 -- DecimArgs::st_plain): the thread's first `plain` rows go out with the default
-// write-back policy, the others with the streaming hint.  About 64 MiB of an output tensor written back through
-// L2 / Infinity Cache costs nothing (it drains under the next launch's reads); all 16 rows streaming were 9 % slower
-// per C2 step, all 16 cached 13 % (profiles/r04_store_policy.txt).  Four scalar branches per tile.
-template <bool PAD>
-__device__ __forceinline__ void store_rows(const RowBuf& rb, int r, const cf (&v)[16], int plain) {
-  const unsigned vr = rb.vo + (unsigned)r * rb.rowb;
-#pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    u32x2 w;
-    const float fx = v[u].x, fy = v[u].y;
-    w.x = __builtin_bit_cast(unsigned, fx); w.y = __builtin_bit_cast(unsigned, fy);
-    const unsigned vo = PAD ? vr + (unsigned)u * rb.su : vr, so = PAD ? 0u : (unsigned)u * rb.su;
-    if (u < 4 && u < plain) __builtin_amdgcn_raw_buffer_store_b64(w, rb.rs, vo, so, 0);
-    else __builtin_amdgcn_raw_buffer_store_b64(w, rb.rs, vo, so, BUF_NT);
-  }
-}
-// ---- 2-byte streamed tensors (IO = SMX_IO_BF16 / SMX_IO_F16, the k_*_io kernels) ----------------------------------
-// The same tile walk with a packed channel pair per row in ONE dword: buffer_load / buffer_store_dword, row pitch D 2
-// bytes, range R D 2 bytes.  Loads widen exactly (bf16: the high half of an f32; fp16: v_cvt_f32_f16), stores round
-// once, to nearest even: bf16 by the plain cast (v_cvt_pk_bf16_f32 -- a NaN stays a NaN), fp16 by the IEEE
-// conversion (v_cvt_f16_f32: overflow to +-inf; never the round-toward-zero v_cvt_pkrtz) -- the results of
-// torch.Tensor.to(dtype) on the f32 values, bit for bit.
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+// The same from the tensor base and b, for the 2-byte kernels.  Two spellings on purpose: WHERE base + b R D is formed
+// (in the caller's argument list, or in here behind the other arguments) decides the instruction order of the
+// kernels' scalar prologue, and so does a call from one of these bodies into the other.  The f32
+// kernels have always formed it in the call, the 2-byte kernels in here; each keeps its spelling so that each kernel
+// keeps its machine code.  Change both bodies together.
 template <int IO>
-struct RowBufIO {
-  __amdgpu_buffer_rsrc_t rs;       // batch row b: base + b R D elements, R D 2 bytes
-  unsigned vo;                     // (t L D + d) 2
-  unsigned su;                     // 16 L D 2
-  unsigned rowb;                   // D 2
-};
-template <int IO>
-__device__ __forceinline__ RowBufIO<IO> row_buf_io(const void* base, int b, const Geom& g, int t, int d,
-                                                   bool in_range = true) {
-  RowBufIO<IO> rb;
-  char* row0 = const_cast<char*>(static_cast<const char*>(base)) + (size_t)b * g.R * g.D * 2;
-  rb.rs = __builtin_amdgcn_make_buffer_rsrc(row0, 0, (int)((unsigned)g.R * (unsigned)g.D * 2u), 0x00020000);
-  rb.rowb = (unsigned)g.D * 2u;
-  rb.vo = in_range ? ((unsigned)t * (unsigned)g.L * (unsigned)g.D + (unsigned)d) * 2u : 0x80000000u;
+__device__ __forceinline__ RowBufT<IO> row_buf(const void* base, int b, const Geom& g, int t, int d,
+                                               bool in_range = true) {
+  constexpr unsigned ES = RowBufT<IO>::ES;
+  RowBufT<IO> rb;
+  char* row0 = const_cast<char*>(static_cast<const char*>(base)) + (size_t)b * g.R * g.D * ES;
+  rb.rs = __builtin_amdgcn_make_buffer_rsrc(row0, 0, (int)((unsigned)g.R * (unsigned)g.D * ES), 0x00020000);
+  rb.rowb = (unsigned)g.D * ES;
+  rb.vo = in_range ? ((unsigned)t * (unsigned)g.L * (unsigned)g.D + (unsigned)d) * ES : 0x80000000u;
   rb.su = 16u * (unsigned)g.L * rb.rowb;
   return rb;
 }
+// 2-byte elements: loads widen exactly (bf16: the high half of an f32; fp16: v_cvt_f32_f16), stores round once, to
+// nearest even: bf16 by the plain cast (v_cvt_pk_bf16_f32 -- a NaN stays a NaN), fp16 by the IEEE conversion
+// (v_cvt_f16_f32: overflow to +-inf; never the round-toward-zero v_cvt_pkrtz) -- the results of
+// torch.Tensor.to(dtype) on the f32 values, bit for bit.
 template <int IO>
 __device__ __forceinline__ cf widen2(unsigned w) {
   if constexpr (IO == 1) {
@@ -160,43 +133,63 @@ __device__ __forceinline__ unsigned narrow2(float fx, float fy) {
     return __builtin_bit_cast(unsigned, h);
   }
 }
+// rows u = U0 .. U0+CNT-1 of tile r: row (t + 16 u) L + r
 template <int U0, int CNT, bool PAD, int IO>
-__device__ __forceinline__ void load_rows(const RowBufIO<IO>& rb, int r, cf (&v)[16]) {
+__device__ __forceinline__ void load_rows(const RowBufT<IO>& rb, int r, cf (&v)[16]) {
   const unsigned vr = rb.vo + (unsigned)r * rb.rowb;
 #pragma unroll
   for (int u = U0; u < U0 + CNT; ++u) {
-    const unsigned w = PAD ? __builtin_amdgcn_raw_buffer_load_b32(rb.rs, vr + (unsigned)u * rb.su, 0, BUF_NT)
-                           : __builtin_amdgcn_raw_buffer_load_b32(rb.rs, vr, (unsigned)u * rb.su, BUF_NT);
-    const cf e = widen2<IO>(w);
-    float fx = e.x, fy = e.y;
+    const unsigned vo = PAD ? vr + (unsigned)u * rb.su : vr, so = PAD ? 0u : (unsigned)u * rb.su;
+    float fx, fy;
+    if constexpr (IO == 0) {
+      const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rb.rs, vo, so, BUF_NT);
+      const unsigned wx = w.x, wy = w.y;      // (bit_cast straight from a vector ELEMENT reads element 0 twice: clang 22)
+      fx = __builtin_bit_cast(float, wx); fy = __builtin_bit_cast(float, wy);
+    } else {
+      const cf e = widen2<IO>(__builtin_amdgcn_raw_buffer_load_b32(rb.rs, vo, so, BUF_NT));
+      fx = e.x; fy = e.y;
+    }
+    // two scalars from here on: left as <2 x float> the optimiser turns the first butterflies into v_pk_add_f32,
+    // which issue at half the rate of the scalar adds with two waves per SIMD (tools/probe_valu.hip, round 3)
     asm("" : "+v"(fx));
     asm("" : "+v"(fy));
     v[u] = mk(fx, fy);
   }
 }
-// plain: as store_rows above; DecimArgs::st_plain is chosen from the output's bytes (smx_api decim_args)
+// plain (wave-uniform: 0, 1, 2 or 4 -- DecimArgs::st_plain, chosen from the output's bytes in smx_api decim_args): the
+// thread's first `plain` rows go out with the default write-back policy, the others with the streaming hint.  About
+// 64 MiB of an output tensor written back through L2 / Infinity Cache costs nothing (it drains under the next
+// launch's reads); all 16 rows streaming were 9 % slower per C2 step, all 16 cached 13 %
+// (profiles/r04_store_policy.txt).  Four scalar branches per tile.
 template <bool PAD, int IO>
-__device__ __forceinline__ void store_rows(const RowBufIO<IO>& rb, int r, const cf (&v)[16], int plain) {
+__device__ __forceinline__ void store_rows(const RowBufT<IO>& rb, int r, const cf (&v)[16], int plain) {
   const unsigned vr = rb.vo + (unsigned)r * rb.rowb;
 #pragma unroll
   for (int u = 0; u < 16; ++u) {
-    const unsigned w = narrow2<IO>(v[u].x, v[u].y);
+    const float fx = v[u].x, fy = v[u].y;
+    std::conditional_t<IO == 0, u32x2, unsigned> w;
+    if constexpr (IO == 0) { w.x = __builtin_bit_cast(unsigned, fx); w.y = __builtin_bit_cast(unsigned, fy); }
+    else w = narrow2<IO>(fx, fy);
     const unsigned vo = PAD ? vr + (unsigned)u * rb.su : vr, so = PAD ? 0u : (unsigned)u * rb.su;
-    if (u < 4 && u < plain) __builtin_amdgcn_raw_buffer_store_b32(w, rb.rs, vo, so, 0);
-    else __builtin_amdgcn_raw_buffer_store_b32(w, rb.rs, vo, so, BUF_NT);
+    if constexpr (IO == 0) {
+      if (u < 4 && u < plain) __builtin_amdgcn_raw_buffer_store_b64(w, rb.rs, vo, so, 0);
+      else __builtin_amdgcn_raw_buffer_store_b64(w, rb.rs, vo, so, BUF_NT);
+    } else {
+      if (u < 4 && u < plain) __builtin_amdgcn_raw_buffer_store_b32(w, rb.rs, vo, so, 0);
+      else __builtin_amdgcn_raw_buffer_store_b32(w, rb.rs, vo, so, BUF_NT);
+    }
   }
 }
 #else
 // host pass of hipcc: the kernels' bodies are parsed but never emitted -- declarations only
-struct RowBuf { unsigned vo, su, rowb; };
-__device__ RowBuf row_buf(const float* row0, const Geom& g, int t, int d, bool in_range = true);
-template <int U0, int CNT, bool PAD> __device__ void load_rows(const RowBuf& rb, int r, cf (&v)[16]);
-template <bool PAD> __device__ void store_rows(const RowBuf& rb, int r, const cf (&v)[16], int plain);
-template <int IO> struct RowBufIO { unsigned vo, su, rowb; };
+template <int IO> struct RowBufT { unsigned vo, su, rowb; };
+using RowBuf = RowBufT<0>;
+template <int IO = 0>
+__device__ RowBufT<IO> row_buf(const void* row0, const Geom& g, int t, int d, bool in_range = true);
 template <int IO>
-__device__ RowBufIO<IO> row_buf_io(const void* base, int b, const Geom& g, int t, int d, bool in_range = true);
-template <int U0, int CNT, bool PAD, int IO> __device__ void load_rows(const RowBufIO<IO>& rb, int r, cf (&v)[16]);
-template <bool PAD, int IO> __device__ void store_rows(const RowBufIO<IO>& rb, int r, const cf (&v)[16], int plain);
+__device__ RowBufT<IO> row_buf(const void* base, int b, const Geom& g, int t, int d, bool in_range = true);
+template <int U0, int CNT, bool PAD, int IO> __device__ void load_rows(const RowBufT<IO>& rb, int r, cf (&v)[16]);
+template <bool PAD, int IO> __device__ void store_rows(const RowBufT<IO>& rb, int r, const cf (&v)[16], int plain);
 #endif
 
 // ---- launch helpers ----------------------------------------------------------------------------

@@ -261,18 +261,12 @@ def forward_raw(x, w_re, w_im, bias, *, conj_w=False, save_spectrum=False, dropo
     if ws is None:
         ws = _workspace(x.device, _ws_bytes(B, N, D, F))
     with _on_device(x.device):
-        if io:
-            _lib.check(_lib.lib().smx_forward_io(
-                x.data_ptr(), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(xk),
+        args = (x.data_ptr(), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(xk),
                 _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F,
                 int(bool(conj_w)) | (2 if pack_ready else 0), float(dropout_p), _ptr(rng), _ptr(pack),
-                _stream(x.device), int(io)))
-            return y, xk
-        _lib.check(_lib.lib().smx_forward_dropout(
-            x.data_ptr(), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(xk),
-            _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F,
-            int(bool(conj_w)) | (2 if pack_ready else 0), float(dropout_p), _ptr(rng), _ptr(pack),
-            _stream(x.device)))
+                _stream(x.device))
+        # (2-byte rows through the _io entry, f32 through the f32 entry: the tests tell the routes apart by the call)
+        _lib.check(_lib.lib().smx_forward_io(*args, int(io)) if io else _lib.lib().smx_forward_dropout(*args))
     return y, xk
 
 
@@ -305,16 +299,10 @@ def backward_raw(g, xk, w_re, w_im, *, want_x=True, want_w=True, phases=PHASE_AL
         phases |= PHASE_SYNC_CLEAN
     _prepare(g.device, N)
     with _on_device(g.device):
-        if io:
-            _lib.check(_lib.lib().smx_backward_io(
-                g.data_ptr(), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(), _ptr(grad_x), _ptr(gw_re),
+        args = (g.data_ptr(), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(), _ptr(grad_x), _ptr(gw_re),
                 _ptr(gw_im), _ptr(gb), _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F, phases,
-                float(dropout_p), _ptr(rng), _ptr(pack), _stream(g.device), int(io)))
-            return grad_x, flat
-        _lib.check(_lib.lib().smx_backward_dropout(
-            g.data_ptr(), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(), _ptr(grad_x), _ptr(gw_re),
-            _ptr(gw_im), _ptr(gb), _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F, phases,
-            float(dropout_p), _ptr(rng), _ptr(pack), _stream(g.device)))
+                float(dropout_p), _ptr(rng), _ptr(pack), _stream(g.device))
+        _lib.check(_lib.lib().smx_backward_io(*args, int(io)) if io else _lib.lib().smx_backward_dropout(*args))
     return grad_x, flat
 
 
@@ -1057,14 +1045,10 @@ class _RankOneConv(torch.autograd.Function):
         sh = _shape(B, R, D, n_fft // 2 + 1, n_fft, n_fft // 2 + 1)
         io = ctx.io = _IO[x.dtype]                           # bf16 / fp16 x: the single-launch plan only (rank_one_conv)
         with _on_device(x.device):
-            if io == 0:
-                _lib.check(_lib.lib().smx_conv_forward(sh, x.data_ptr(), h_re.data_ptr(), h_im.data_ptr(),
-                                                       _ptr(scale), y.data_ptr(), _ptr(xs), ws.data_ptr(),
-                                                       ws.numel(), _stream(x.device)))
-            else:
-                _lib.check(_lib.lib().smx_conv_forward_io(sh, x.data_ptr(), h_re.data_ptr(), h_im.data_ptr(),
-                                                          _ptr(scale), y.data_ptr(), _ptr(xs), ws.data_ptr(),
-                                                          ws.numel(), io, _stream(x.device)))
+            args = (sh, x.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), y.data_ptr(), _ptr(xs),
+                    ws.data_ptr(), ws.numel())
+            s = _stream(x.device)
+            _lib.check(_lib.lib().smx_conv_forward_io(*args, io, s) if io else _lib.lib().smx_conv_forward(*args, s))
         ctx.dtype = x.dtype
         ctx.n_fft = n_fft
         ctx.has_scale = scale is not None
@@ -1093,16 +1077,11 @@ class _RankOneConv(torch.autograd.Function):
         ws = _workspace(g.device, wsb)
         sh = _shape(B, R, D, n // 2 + 1, n, n // 2 + 1)
         with _on_device(g.device):
-            if ctx.io == 0:
-                _lib.check(_lib.lib().smx_conv_backward(
-                    sh, g.data_ptr(), xs.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), gx.data_ptr(),
+            args = (sh, g.data_ptr(), xs.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), gx.data_ptr(),
                     None if gh is None else gh[0].data_ptr(), None if gh is None else gh[1].data_ptr(), _ptr(gs),
-                    ws.data_ptr(), ws.numel(), _stream(g.device)))
-            else:
-                _lib.check(_lib.lib().smx_conv_backward_io(
-                    sh, g.data_ptr(), xs.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), gx.data_ptr(),
-                    None if gh is None else gh[0].data_ptr(), None if gh is None else gh[1].data_ptr(), _ptr(gs),
-                    ws.data_ptr(), ws.numel(), ctx.io, _stream(g.device)))
+                    ws.data_ptr(), ws.numel())
+            s, io = _stream(g.device), ctx.io
+            _lib.check(_lib.lib().smx_conv_backward_io(*args, io, s) if io else _lib.lib().smx_conv_backward(*args, s))
         return gx, None if gh is None else gh[0], None if gh is None else gh[1], gs, None, None
 
 

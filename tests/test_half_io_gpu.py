@@ -7,8 +7,8 @@ The contract is bitwise: all arithmetic is fp32 and the 2-byte input widens exac
     parameter gradients == the fp32 path's (fp32 parameters)
     saved spectrum xk   == the fp32 path's
 
-on the plans with native 2-byte rows (k_fused_io, k_split_a_io / k_split_b_io) and, by construction, on the up-cast
-route every other plan takes.
+on the plans with native 2-byte rows (the IO instances of k_fused, k_split_a / k_split_b) and, by construction, on the
+up-cast route every other plan takes.
 """
 import ctypes
 

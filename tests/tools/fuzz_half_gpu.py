@@ -94,7 +94,7 @@ def main():
             fails.append((i, (B, N, D, F), str(dtype), drop, key))
     torch.cuda.synchronize()
     lines = [f"fuzz_half_gpu: {a.cases} cases, seed {a.seed}, {len(fails)} failures, {time.time() - t0:.0f} s",
-             "cases by route (native = k_fused_io / k_split_*_io, upcast = fp32 op + .to(dtype)):"]
+             "cases by route (native = IO instances of k_fused / k_split_*, upcast = fp32 op + .to(dtype)):"]
     lines += [f"  {k:28s} {v}" for k, v in sorted(tally.items())]
     lines += [f"  FAIL case {c}: shape {s} {d} dropout={dr} {k}" for c, s, d, dr, k in fails[:50]]
     print("\n".join(lines))
