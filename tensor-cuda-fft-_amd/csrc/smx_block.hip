@@ -11,8 +11,11 @@
 //   * k_ln_apply, k_add_rows   unfused fallback used with the split / direct transform paths.
 // One wavefront per row, lane l holds elements (l + 64 c) VEC + [0, VEC), c < CH, in registers:
 // every global access is a full-wave contiguous segment and a row is read exactly once.
-#include <type_traits>
-
+// Vec, wave_sum, the LayerNorm-backward accumulation, the (VEC, CH) dispatch and the launch geometry
+// (ROW_WAVES rows per block, ln_num_blocks blocks) are smx_rows.h's.  The load, statistics and partial
+// loops of the three kernels stay written out: each fuses what the toolkit keeps apart (two rows in
+// flight, one bounds test for three loads, the update fused with its store, 64-bit slab offsets), and
+// every helper spelling tried compiled to other registers.
 #include "smx_kernels.h"
 #include "smx_rows.h"
 
@@ -20,19 +23,17 @@ namespace smx {
 
 namespace {
 
-constexpr int LN_WAVES = 4;                 // wavefronts (rows in flight) per block
-
 // stats[row] = (mean, 1/sqrt(var + eps)), biased variance, two passes over the registers
 // (torch.nn.LayerNorm, used by the reference at spectral_layers.py:162,185).
 template <int VEC, int CH>
-__global__ __launch_bounds__(64 * LN_WAVES) void k_ln_stats(const float* __restrict__ x,
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_ln_stats(const float* __restrict__ x,
                                                              cf* __restrict__ stats, long long rows,
                                                              int D, float eps) {
   constexpr int R = CH <= 2 ? 2 : 1;          // rows in flight per wavefront (read-only kernel)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const float inv_d = 1.f / (float)D;
-  const long long step = (long long)gridDim.x * LN_WAVES;
-  for (long long row0 = (long long)blockIdx.x * LN_WAVES + wv; row0 < rows; row0 += R * step) {
+  const long long step = (long long)gridDim.x * ROW_WAVES;
+  for (long long row0 = (long long)blockIdx.x * ROW_WAVES + wv; row0 < rows; row0 += R * step) {
     Vec<VEC> xv[R][CH];
 #pragma unroll
     for (int q = 0; q < R; ++q) {
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(64 * LN_WAVES) void k_ln_stats(const float* __restr
 
 // h = (x - mean) rstd gamma + beta          (unfused fallback)
 template <int VEC, int CH>
-__global__ __launch_bounds__(64 * LN_WAVES) void k_ln_apply(const float* __restrict__ x,
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_ln_apply(const float* __restrict__ x,
                                                              const cf* __restrict__ stats,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta,
@@ -89,8 +90,8 @@ __global__ __launch_bounds__(64 * LN_WAVES) void k_ln_apply(const float* __restr
       if (beta) bt[c].load_cached(beta + e);
     }
   }
-  for (long long row = (long long)blockIdx.x * LN_WAVES + wv; row < rows;
-       row += (long long)gridDim.x * LN_WAVES) {
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows;
+       row += (long long)gridDim.x * ROW_WAVES) {
     const cf st = stats[row];
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
@@ -117,14 +118,14 @@ __global__ void k_add_rows(float* __restrict__ y, const float* __restrict__ x, s
 //   xh = (x - mean) rstd ; u = gamma grad_h ; grad_x = g + rstd (u - mean_d(u) - xh mean_d(u xh))
 // and per block:  part[blk][0][d] = sum_rows grad_h xh   (grad_gamma),  part[blk][1][d] = sum_rows grad_h.
 template <int VEC, int CH>
-__global__ __launch_bounds__(64 * LN_WAVES) void k_ln_bwd(float* __restrict__ gh_dx,
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_ln_bwd(float* __restrict__ gh_dx,
                                                            const float* __restrict__ x,
                                                            const float* __restrict__ g,
                                                            const cf* __restrict__ stats,
                                                            const float* __restrict__ gamma,
                                                            float* __restrict__ part, long long rows,
                                                            int D) {
-  __shared__ float red[LN_WAVES][2][64 * VEC];
+  __shared__ float red[ROW_WAVES][2][64 * VEC];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const float inv_d = 1.f / (float)D;
   Vec<VEC> gm[CH], ag[CH], ab[CH];
@@ -135,8 +136,8 @@ __global__ __launch_bounds__(64 * LN_WAVES) void k_ln_bwd(float* __restrict__ gh
     for (int i = 0; i < VEC; ++i) { gm[c].v[i] = 1.f; ag[c].v[i] = 0.f; ab[c].v[i] = 0.f; }
     if (e < D && gamma) gm[c].load_cached(gamma + e);
   }
-  for (long long row = (long long)blockIdx.x * LN_WAVES + wv; row < rows;
-       row += (long long)gridDim.x * LN_WAVES) {
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows;
+       row += (long long)gridDim.x * ROW_WAVES) {
     const size_t o = (size_t)row * D;
     Vec<VEC> hv[CH], xv[CH], gv[CH];
 #pragma unroll
@@ -159,13 +160,9 @@ __global__ __launch_bounds__(64 * LN_WAVES) void k_ln_bwd(float* __restrict__ gh
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         const float xh = e < D ? (xv[c].v[i] - st.x) * st.y : 0.f;
-        const float u = gm[c].v[i] * hv[c].v[i];
+        const float gmv = gm[c].v[i];           // read before hv: the operand order of gamma * grad_h
+        hv[c].v[i] = ln_bwd_acc(hv[c].v[i], xh, gmv, ag[c].v[i], ab[c].v[i], s1, s2);
         xv[c].v[i] = xh;
-        s1 += u;
-        s2 = fmaf(u, xh, s2);
-        ag[c].v[i] = fmaf(hv[c].v[i], xh, ag[c].v[i]);
-        ab[c].v[i] += hv[c].v[i];
-        hv[c].v[i] = u;
       }
     }
     const float m1 = wave_sum(s1) * inv_d, m2 = wave_sum(s2) * inv_d;
@@ -196,7 +193,7 @@ __global__ __launch_bounds__(64 * LN_WAVES) void k_ln_bwd(float* __restrict__ gh
         if (e + i < D) {
           float a0 = 0.f, a1 = 0.f;
 #pragma unroll
-          for (int w2 = 0; w2 < LN_WAVES; ++w2) {
+          for (int w2 = 0; w2 < ROW_WAVES; ++w2) {
             a0 += red[w2][0][lane * VEC + i];
             a1 += red[w2][1][lane * VEC + i];
           }
@@ -272,33 +269,16 @@ __global__ void k_rng_next(unsigned long long* state, unsigned long long* saved)
   }
 }
 
-int ln_blocks(long long rows) { return ln_num_blocks(rows); }
-
-// dispatch on (VEC, CH): smallest register tile that covers D
-template <typename Fn4, typename Fn1>
-bool ln_dispatch(int D, Fn4 f4, Fn1 f1) {
-  if (D % 4 == 0) {
-    const int ch = (D / 4 + 63) / 64;
-    if (ch <= 1) f4(std::integral_constant<int, 1>());
-    else if (ch <= 2) f4(std::integral_constant<int, 2>());
-    else if (ch <= 4) f4(std::integral_constant<int, 4>());
-    else if (ch <= 8) f4(std::integral_constant<int, 8>());
-    else if (ch <= 16) f4(std::integral_constant<int, 16>());
-    else return false;
-    return true;
-  }
-  const int ch = (D + 63) / 64;
-  if (ch <= 1) f1(std::integral_constant<int, 1>());
-  else if (ch <= 4) f1(std::integral_constant<int, 4>());
-  else if (ch <= 16) f1(std::integral_constant<int, 16>());
-  else return false;
-  return true;
+// (VEC, CH) of a D-wide row: Vec<4> tiles up to 16 chunks when D % 4 == 0, else scalar tiles of 1, 4, 16
+template <typename Fn>
+bool ln_dispatch(int D, Fn f) {
+  return D % 4 == 0 ? row_dispatch<4, 16>(D, f) : row_dispatch<1, 16, 4>(D, f);
 }
 
 }  // namespace
 
 int ln_num_blocks(long long rows) {
-  long long b = (rows + LN_WAVES - 1) / LN_WAVES;
+  long long b = (rows + ROW_WAVES - 1) / ROW_WAVES;
   return (int)(b < 1 ? 1 : b > LN_MAX_BLOCKS ? LN_MAX_BLOCKS : b);
 }
 
@@ -320,33 +300,18 @@ hipError_t launch_rng_next(unsigned long long* state, unsigned long long* saved,
 
 hipError_t launch_ln_stats(const float* x, cf* stats, long long rows, int D, float eps,
                            hipStream_t s) {
-  const dim3 grid(ln_blocks(rows)), block(64 * LN_WAVES);
-  ln_dispatch(
-      D,
-      [&](auto ch) {
-        hipLaunchKernelGGL((k_ln_stats<4, decltype(ch)::value>), grid, block, 0, s, x, stats, rows,
-                           D, eps);
-      },
-      [&](auto ch) {
-        hipLaunchKernelGGL((k_ln_stats<1, decltype(ch)::value>), grid, block, 0, s, x, stats, rows,
-                           D, eps);
-      });
+  ln_dispatch(D, [&](auto vec, auto ch) {
+    row_launch(k_ln_stats<decltype(vec)::value, decltype(ch)::value>, rows, s, x, stats, rows, D, eps);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_ln_apply(const float* x, const cf* stats, const float* gamma, const float* beta,
                            float* h, long long rows, int D, hipStream_t s) {
-  const dim3 grid(ln_blocks(rows)), block(64 * LN_WAVES);
-  ln_dispatch(
-      D,
-      [&](auto ch) {
-        hipLaunchKernelGGL((k_ln_apply<4, decltype(ch)::value>), grid, block, 0, s, x, stats, gamma,
-                           beta, h, rows, D);
-      },
-      [&](auto ch) {
-        hipLaunchKernelGGL((k_ln_apply<1, decltype(ch)::value>), grid, block, 0, s, x, stats, gamma,
-                           beta, h, rows, D);
-      });
+  ln_dispatch(D, [&](auto vec, auto ch) {
+    row_launch(k_ln_apply<decltype(vec)::value, decltype(ch)::value>, rows, s, x, stats, gamma, beta, h,
+               rows, D);
+  });
   return hipGetLastError();
 }
 
@@ -367,24 +332,12 @@ hipError_t launch_ln_colsum(const float* part, int nblk, int D, float* g_gamma, 
 hipError_t launch_ln_bwd(float* gh_dx, const float* x, const float* g, const cf* stats,
                          const float* gamma, float* part, float* g_gamma, float* g_beta,
                          long long rows, int D, hipStream_t s) {
-  const int nblk = ln_blocks(rows);
-  const dim3 grid(nblk), block(64 * LN_WAVES);
-  ln_dispatch(
-      D,
-      [&](auto ch) {
-        hipLaunchKernelGGL((k_ln_bwd<4, decltype(ch)::value>), grid, block, 0, s, gh_dx, x, g, stats,
-                           gamma, part, rows, D);
-      },
-      [&](auto ch) {
-        hipLaunchKernelGGL((k_ln_bwd<1, decltype(ch)::value>), grid, block, 0, s, gh_dx, x, g, stats,
-                           gamma, part, rows, D);
-      });
+  ln_dispatch(D, [&](auto vec, auto ch) {
+    row_launch(k_ln_bwd<decltype(vec)::value, decltype(ch)::value>, rows, s, gh_dx, x, g, stats, gamma,
+               part, rows, D);
+  });
   if (hipError_t e = hipGetLastError()) return e;
-  if (g_gamma || g_beta) {
-    hipLaunchKernelGGL(k_ln_colsum, dim3((D + 15) / 16, 2), dim3(1024), 0, s, part, nblk, D, g_gamma,
-                       g_beta);
-  }
-  return hipGetLastError();
+  return launch_ln_colsum(part, ln_num_blocks(rows), D, g_gamma, g_beta, s);
 }
 
 }  // namespace smx

@@ -5,12 +5,10 @@
 //                                                 sigmoid gate, blend, residual; the two Linears stay GEMMs)
 // The transforms of phase_mixing / multi_scale and the GEMMs run elsewhere; what is here is the row work torch
 // would do in many small passes.  One wavefront per (b, t) row, lane l holds elements (l + 64 c) VEC + [0, VEC),
-// c < CH, in registers (smx_rows.h); every global access is a full-wave contiguous segment, every row is read
+// c < CH, in registers; the row helpers, the LayerNorm-backward step and the launch are smx_rows.h's; every global access is a full-wave contiguous segment, every row is read
 // once and written once.  Dropout uses the library's counter-based mask (smx_core.h, Drop): element t D + d of
 // batch row b, so the backward regenerates the forward's mask from the same two words.  LayerNorm parameter
 // gradients are per-workgroup partials reduced by k_ln_colsum in a fixed order (no atomics: bitwise reproducible).
-#include <type_traits>
-
 #include "smx_kernels.h"
 #include "smx_rows.h"
 
@@ -18,131 +16,10 @@ namespace smx {
 
 namespace {
 
-constexpr int EW = 4;                        // wavefronts (rows in flight) per block
-
-template <int VEC, int CH>
-__device__ __forceinline__ void row_load(Vec<VEC> (&r)[CH], const float* p, int D, int lane) {
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int e = (lane + 64 * c) * VEC;
-    if (e < D) r[c].load(p + e);
-    else
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) r[c].v[i] = 0.f;
-  }
-}
-
-// parameters (gamma / beta, rotation rows): re-read by every wavefront, so through the caches
-template <int VEC, int CH>
-__device__ __forceinline__ void row_load_cached(Vec<VEC> (&r)[CH], const float* p, int D, int lane, float dflt) {
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int e = (lane + 64 * c) * VEC;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) r[c].v[i] = dflt;
-    if (p && e < D) r[c].load_cached(p + e);
-  }
-}
-
-template <int VEC, int CH>
-__device__ __forceinline__ void row_store(const Vec<VEC> (&r)[CH], float* p, int D, int lane) {
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int e = (lane + 64 * c) * VEC;
-    if (e < D) r[c].store(p + e);
-  }
-}
-
-template <int VEC, int CH>
-__device__ __forceinline__ float row_sum(const Vec<VEC> (&r)[CH]) {
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c)
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) s += r[c].v[i];
-  return s;
-}
-
-// sum of (r - mean)^2 over the D valid elements of this lane
-template <int VEC, int CH>
-__device__ __forceinline__ float row_sq(const Vec<VEC> (&r)[CH], float mean, int D, int lane) {
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int e = (lane + 64 * c) * VEC;
-    if (e < D)
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) { const float d = r[c].v[i] - mean; s = fmaf(d, d, s); }
-  }
-  return s;
-}
-
-// (mean, rstd) of a D-wide row: biased variance, two passes over the registers (torch.nn.LayerNorm)
-template <int VEC, int CH>
-__device__ __forceinline__ cf row_stats(const Vec<VEC> (&r)[CH], int D, int lane, float eps) {
-  const float inv_d = 1.f / (float)D;
-  const float mean = wave_sum(row_sum(r)) * inv_d;
-  const float var = wave_sum(row_sq(r, mean, D, lane)) * inv_d;
-  return mk(mean, 1.f / sqrtf(var + eps));
-}
-
-// mask * 1/(1-p) of elements e0 .. e0 + VEC - 1 of a batch row (e0 even): the pair (2i, 2i+1) shares one hash
-template <int VEC>
-__device__ __forceinline__ void drop_factors(float (&m)[VEC], unsigned key, unsigned long long e0, unsigned thr,
-                                             float scale) {
-#pragma unroll
-  for (int i = 0; i < VEC; i += 2) {
-    const unsigned h = drop_hash((unsigned)((e0 + i) >> 1), key);
-    m[i] = (h & 0xffffu) >= thr ? scale : 0.f;
-    m[i + 1] = (h >> 16) >= thr ? scale : 0.f;
-  }
-}
-
-// Block partials of a LayerNorm's gamma / beta gradients: part[0][off + e] = sum_rows ag, part[1][off + e] = sum_rows
-// ab, with part pointing at this block's (2, W) slab.  Waves are added in index order.
-template <int VEC, int CH>
-__device__ __forceinline__ void block_partials(const Vec<VEC> (&ag)[CH], const Vec<VEC> (&ab)[CH], float* part, int W,
-                                               int off, int D, float (*red)[2][64 * VEC], int lane, int wv) {
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      red[wv][0][lane * VEC + i] = ag[c].v[i];
-      red[wv][1][lane * VEC + i] = ab[c].v[i];
-    }
-    __syncthreads();
-    if (wv == 0) {
-      const int e = (lane + 64 * c) * VEC;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        if (e + i < D) {
-          float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-          for (int w2 = 0; w2 < EW; ++w2) {
-            a0 += red[w2][0][lane * VEC + i];
-            a1 += red[w2][1][lane * VEC + i];
-          }
-          part[off + e + i] = a0;
-          part[W + off + e + i] = a1;
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-
-template <int VEC, int CH>
-__device__ __forceinline__ void zero(Vec<VEC> (&r)[CH]) {
-#pragma unroll
-  for (int c = 0; c < CH; ++c)
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) r[c].v[i] = 0.f;
-}
-
 // ---- A: rope line.  NORM = false is the standalone RotaryFrequencyEmbedding: out = rot(x) ------------------------
 // rot: row t of the (max_seq_len, D/2) complex64 table, D floats (cos, sin) in the layout of a row of x.
 template <int VEC, int CH, bool NORM>
-__global__ __launch_bounds__(64 * EW) void k_rope_fwd(const float* __restrict__ x, const float* __restrict__ rot,
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_rope_fwd(const float* __restrict__ x, const float* __restrict__ rot,
                                                       const float* __restrict__ w1, const float* __restrict__ b1,
                                                       const float* __restrict__ w2, const float* __restrict__ b2,
                                                       float eps1, float eps2, float* __restrict__ x1,
@@ -156,7 +33,7 @@ __global__ __launch_bounds__(64 * EW) void k_rope_fwd(const float* __restrict__ 
     row_load_cached(gm2, w2, D, lane, 1.f); row_load_cached(bt2, b2, D, lane, 0.f);
   }
   const unsigned long long s0 = thr ? rng[0] : 0ull, s1 = thr ? rng[1] : 0ull;
-  for (long long row = (long long)blockIdx.x * EW + wv; row < rows; row += (long long)gridDim.x * EW) {
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows; row += (long long)gridDim.x * ROW_WAVES) {
     const int t = (int)(row % T), b = (int)(row / T);
     const size_t o = (size_t)row * D;
     Vec<VEC> xv[CH], h[CH], rv[CH];
@@ -203,14 +80,14 @@ __global__ __launch_bounds__(64 * EW) void k_rope_fwd(const float* __restrict__ 
 // Backward of A given g1 = dL/dx1 and gh2 = dL/dh2:  G = g1 + LN2'(gh2),  gh1 = rot^T(M1 G),  grad_x = G + LN1'(gh1),
 // x1 recomputed from x in registers.  NORM = false: grad_x = rot^T(g1).
 template <int VEC, int CH, bool NORM>
-__global__ __launch_bounds__(64 * EW) void k_rope_bwd(const float* __restrict__ g1, const float* __restrict__ gh2,
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_rope_bwd(const float* __restrict__ g1, const float* __restrict__ gh2,
                                                       const float* __restrict__ x, const float* __restrict__ rot,
                                                       const float* __restrict__ w1, const float* __restrict__ b1,
                                                       const float* __restrict__ w2, const cf* __restrict__ stats,
                                                       float* __restrict__ gx, float* __restrict__ part,
                                                       long long rows, int T, int D, unsigned thr, float scale,
                                                       const unsigned long long* __restrict__ rng) {
-  __shared__ float red[NORM ? EW : 1][2][64 * VEC];
+  __shared__ float red[NORM ? ROW_WAVES : 1][2][64 * VEC];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const float inv_d = 1.f / (float)D;
   Vec<VEC> gm1[CH], bt1[CH], gm2[CH], ag1[CH], ab1[CH], ag2[CH], ab2[CH];
@@ -220,7 +97,7 @@ __global__ __launch_bounds__(64 * EW) void k_rope_bwd(const float* __restrict__ 
     zero(ag1); zero(ab1); zero(ag2); zero(ab2);
   }
   const unsigned long long s0 = thr ? rng[0] : 0ull, s1 = thr ? rng[1] : 0ull;
-  for (long long row = (long long)blockIdx.x * EW + wv; row < rows; row += (long long)gridDim.x * EW) {
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows; row += (long long)gridDim.x * ROW_WAVES) {
     const int t = (int)(row % T), b = (int)(row / T);
     const size_t o = (size_t)row * D;
     Vec<VEC> G[CH], rv[CH], xh1[CH];
@@ -253,6 +130,8 @@ __global__ __launch_bounds__(64 * EW) void k_rope_bwd(const float* __restrict__ 
           xh2[c].v[i] = e < D ? (y0 - st2.x) * st2.y : 0.f;
           xh2[c].v[i + 1] = e < D ? (y1 - st2.x) * st2.y : 0.f;
         }
+        // ln_bwd_acc / ln_bwd_apply written out: inside this chunk loop they changed which product of the
+        // rotation below is fused into an fma in k_rope_bwd<2, 1, true>
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
           const float gh = u[c].v[i];
@@ -293,20 +172,9 @@ __global__ __launch_bounds__(64 * EW) void k_rope_bwd(const float* __restrict__ 
 #pragma unroll
     for (int c = 0; c < CH; ++c)
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        const float g = gh[c].v[i];
-        ag1[c].v[i] = fmaf(g, xh1[c].v[i], ag1[c].v[i]);
-        ab1[c].v[i] += g;
-        const float uu = gm1[c].v[i] * g;
-        gh[c].v[i] = uu;
-        s1 += uu;
-        s2 = fmaf(uu, xh1[c].v[i], s2);
-      }
-    const float m1 = wave_sum(s1) * inv_d, m2 = wave_sum(s2) * inv_d;
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) G[c].v[i] = fmaf(st1.y, gh[c].v[i] - m1 - xh1[c].v[i] * m2, G[c].v[i]);
+      for (int i = 0; i < VEC; ++i)
+        gh[c].v[i] = ln_bwd_acc(gh[c].v[i], xh1[c].v[i], gm1[c].v[i], ag1[c].v[i], ab1[c].v[i], s1, s2);
+    ln_bwd_apply(G, gh, xh1, st1.y, wave_sum(s1) * inv_d, wave_sum(s2) * inv_d);
     row_store(G, gx + o, D, lane);
   }
   if (NORM) {
@@ -318,7 +186,7 @@ __global__ __launch_bounds__(64 * EW) void k_rope_bwd(const float* __restrict__ 
 
 // ---- B: x2 = x1 + M2 p,  h3 = LN(x2) ----------------------------------------------------------------------------
 template <int VEC, int CH>
-__global__ __launch_bounds__(64 * EW) void k_res_fwd(const float* __restrict__ x1, const float* __restrict__ p,
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_res_fwd(const float* __restrict__ x1, const float* __restrict__ p,
                                                      const float* __restrict__ w3, const float* __restrict__ b3,
                                                      float eps, float* __restrict__ x2, float* __restrict__ h3,
                                                      cf* __restrict__ stats, long long rows, int T, int D,
@@ -328,7 +196,7 @@ __global__ __launch_bounds__(64 * EW) void k_res_fwd(const float* __restrict__ x
   Vec<VEC> gm[CH], bt[CH];
   row_load_cached(gm, w3, D, lane, 1.f); row_load_cached(bt, b3, D, lane, 0.f);
   const unsigned long long s0 = thr ? rng[0] : 0ull, s1 = thr ? rng[1] : 0ull;
-  for (long long row = (long long)blockIdx.x * EW + wv; row < rows; row += (long long)gridDim.x * EW) {
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows; row += (long long)gridDim.x * ROW_WAVES) {
     const int t = (int)(row % T), b = (int)(row / T);
     const size_t o = (size_t)row * D;
     Vec<VEC> xv[CH], pv[CH];
@@ -355,20 +223,20 @@ __global__ __launch_bounds__(64 * EW) void k_res_fwd(const float* __restrict__ x
 
 // G = g2 + LN3'(gh3):  grad_x1 = G,  grad_p = M2 G (not written when gp == NULL)
 template <int VEC, int CH>
-__global__ __launch_bounds__(64 * EW) void k_res_bwd(const float* __restrict__ g2, const float* __restrict__ gh3,
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_res_bwd(const float* __restrict__ g2, const float* __restrict__ gh3,
                                                      const float* __restrict__ x2, const float* __restrict__ w3,
                                                      const cf* __restrict__ stats, float* __restrict__ gx1,
                                                      float* __restrict__ gp, float* __restrict__ part, long long rows,
                                                      int T, int D, unsigned thr, float scale,
                                                      const unsigned long long* __restrict__ rng) {
-  __shared__ float red[EW][2][64 * VEC];
+  __shared__ float red[ROW_WAVES][2][64 * VEC];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const float inv_d = 1.f / (float)D;
   Vec<VEC> gm[CH], ag[CH], ab[CH];
   row_load_cached(gm, w3, D, lane, 1.f);
   zero(ag); zero(ab);
   const unsigned long long s0 = thr ? rng[0] : 0ull, s1 = thr ? rng[1] : 0ull;
-  for (long long row = (long long)blockIdx.x * EW + wv; row < rows; row += (long long)gridDim.x * EW) {
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows; row += (long long)gridDim.x * ROW_WAVES) {
     const int t = (int)(row % T), b = (int)(row / T);
     const size_t o = (size_t)row * D;
     Vec<VEC> G[CH], xh[CH], u[CH];
@@ -382,22 +250,11 @@ __global__ __launch_bounds__(64 * EW) void k_res_bwd(const float* __restrict__ g
       const int e = (lane + 64 * c) * VEC;
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
-        const float n = e < D ? (xh[c].v[i] - st.x) * st.y : 0.f;
-        const float gh = u[c].v[i];
-        xh[c].v[i] = n;
-        ag[c].v[i] = fmaf(gh, n, ag[c].v[i]);
-        ab[c].v[i] += gh;
-        const float uu = gm[c].v[i] * gh;
-        u[c].v[i] = uu;
-        sa += uu;
-        sb = fmaf(uu, n, sb);
+        xh[c].v[i] = e < D ? (xh[c].v[i] - st.x) * st.y : 0.f;
+        u[c].v[i] = ln_bwd_acc(u[c].v[i], xh[c].v[i], gm[c].v[i], ag[c].v[i], ab[c].v[i], sa, sb);
       }
     }
-    const float m1 = wave_sum(sa) * inv_d, m2 = wave_sum(sb) * inv_d;
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) G[c].v[i] = fmaf(st.y, u[c].v[i] - m1 - xh[c].v[i] * m2, G[c].v[i]);
+    ln_bwd_apply(G, u, xh, st.y, wave_sum(sa) * inv_d, wave_sum(sb) * inv_d);
     row_store(G, gx1 + o, D, lane);
     if (gp) {
       const unsigned key = thr ? drop_row_key(s0, s1, b) : 0u;
@@ -417,7 +274,7 @@ __global__ __launch_bounds__(64 * EW) void k_res_bwd(const float* __restrict__ g
 // ---- C: a (rows, 2D) = gate_proj[0](h3), v (rows, D) = value_proj(h3):
 //   â = LN_2D(a),  gate = sigmoid(â[:D]),  out = gate v + (1 - gate) â[D:],  x3 = x2 + M3 out  (x2 == NULL: x3 = out)
 template <int VEC, int CH>
-__global__ __launch_bounds__(64 * EW) void k_gate_fwd(const float* __restrict__ a, const float* __restrict__ v,
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_gate_fwd(const float* __restrict__ a, const float* __restrict__ v,
                                                       const float* __restrict__ x2, const float* __restrict__ wg,
                                                       const float* __restrict__ bg, float eps,
                                                       float* __restrict__ x3, cf* __restrict__ stats, long long rows,
@@ -429,7 +286,7 @@ __global__ __launch_bounds__(64 * EW) void k_gate_fwd(const float* __restrict__ 
   row_load_cached(gl, wg, D, lane, 1.f); row_load_cached(gh, wg ? wg + D : nullptr, D, lane, 1.f);
   row_load_cached(bl, bg, D, lane, 0.f); row_load_cached(bh, bg ? bg + D : nullptr, D, lane, 0.f);
   const unsigned long long s0 = thr ? rng[0] : 0ull, s1 = thr ? rng[1] : 0ull;
-  for (long long row = (long long)blockIdx.x * EW + wv; row < rows; row += (long long)gridDim.x * EW) {
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows; row += (long long)gridDim.x * ROW_WAVES) {
     const int t = (int)(row % T), b = (int)(row / T);
     const size_t o = (size_t)row * D;
     Vec<VEC> al[CH], ah[CH], vv[CH], rv[CH];
@@ -462,14 +319,14 @@ __global__ __launch_bounds__(64 * EW) void k_gate_fwd(const float* __restrict__ 
 
 // go = M3 g3:  grad_v = gate go,  gâ[:D] = go (v - vt) gate (1 - gate),  gâ[D:] = go (1 - gate),  grad_a = LN_2D'(gâ)
 template <int VEC, int CH>
-__global__ __launch_bounds__(64 * EW) void k_gate_bwd(const float* __restrict__ g3, const float* __restrict__ a,
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_gate_bwd(const float* __restrict__ g3, const float* __restrict__ a,
                                                       const float* __restrict__ v, const float* __restrict__ wg,
                                                       const float* __restrict__ bg, const cf* __restrict__ stats,
                                                       float* __restrict__ ga, float* __restrict__ gv,
                                                       float* __restrict__ part, long long rows, int T, int D,
                                                       unsigned thr, float scale,
                                                       const unsigned long long* __restrict__ rng) {
-  __shared__ float red[EW][2][64 * VEC];
+  __shared__ float red[ROW_WAVES][2][64 * VEC];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const float inv_w = 0.5f / (float)D;
   Vec<VEC> gl[CH], gh[CH], bl[CH], bh[CH], agl[CH], agh[CH], abl[CH], abh[CH];
@@ -477,7 +334,7 @@ __global__ __launch_bounds__(64 * EW) void k_gate_bwd(const float* __restrict__ 
   row_load_cached(bl, bg, D, lane, 0.f); row_load_cached(bh, bg ? bg + D : nullptr, D, lane, 0.f);
   zero(agl); zero(agh); zero(abl); zero(abh);
   const unsigned long long s0 = thr ? rng[0] : 0ull, s1 = thr ? rng[1] : 0ull;
-  for (long long row = (long long)blockIdx.x * EW + wv; row < rows; row += (long long)gridDim.x * EW) {
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows; row += (long long)gridDim.x * ROW_WAVES) {
     const int t = (int)(row % T), b = (int)(row / T);
     const size_t o = (size_t)row * D;
     // al / ah: the row of a, then its normalised halves;  ul / vv: the row of g3 / v, then gamma * dL/dâ of each half
@@ -510,6 +367,8 @@ __global__ __launch_bounds__(64 * EW) void k_gate_bwd(const float* __restrict__ 
         agh[c].v[i] = fmaf(dh, nh, agh[c].v[i]);
         abl[c].v[i] += dl;
         abh[c].v[i] += dh;
+        // the LayerNorm-backward step over a 2D-wide row held as two halves: both halves feed one pair of sums
+        // and nothing is added to the result, so ln_bwd_acc / ln_bwd_apply (smx_rows.h) do not fit
         const float u0 = gl[c].v[i] * dl, u1 = gh[c].v[i] * dh;
         sa += u0 + u1;
         sb = fmaf(u0, nl, fmaf(u1, nh, sb));
@@ -534,25 +393,10 @@ __global__ __launch_bounds__(64 * EW) void k_gate_bwd(const float* __restrict__ 
   block_partials(agh, abh, pb, 2 * D, D, D, red, lane, wv);
 }
 
-// smallest register tile that covers D (even, <= ENH_MAX_D): Vec<4> rows when D % 4 == 0, Vec<2> rows otherwise
+// (VEC, CH) of a D-wide row (even, <= ENH_MAX_D): Vec<4> tiles up to 4 chunks when D % 4 == 0, else Vec<2> up to 8
 template <typename Fn>
 bool enh_dispatch(int D, Fn f) {
-  using std::integral_constant;
-  if (D % 4 == 0) {
-    const int ch = (D / 4 + 63) / 64;
-    if (ch <= 1) f(integral_constant<int, 4>(), integral_constant<int, 1>());
-    else if (ch <= 2) f(integral_constant<int, 4>(), integral_constant<int, 2>());
-    else if (ch <= 4) f(integral_constant<int, 4>(), integral_constant<int, 4>());
-    else return false;
-    return true;
-  }
-  const int ch = (D / 2 + 63) / 64;
-  if (ch <= 1) f(integral_constant<int, 2>(), integral_constant<int, 1>());
-  else if (ch <= 2) f(integral_constant<int, 2>(), integral_constant<int, 2>());
-  else if (ch <= 4) f(integral_constant<int, 2>(), integral_constant<int, 4>());
-  else if (ch <= 8) f(integral_constant<int, 2>(), integral_constant<int, 8>());
-  else return false;
-  return true;
+  return D % 4 == 0 ? row_dispatch<4, 4>(D, f) : row_dispatch<2, 8>(D, f);
 }
 
 }  // namespace
@@ -565,14 +409,13 @@ hipError_t launch_rope_fwd(const float* x, const float* rot, const float* w1, co
                            const float* b2, float eps1, float eps2, float* x1, float* h2, cf* stats, int B, int T,
                            int D, bool norm, unsigned thr, float scale, const unsigned long long* rng, hipStream_t s) {
   const long long rows = (long long)B * T;
-  const dim3 grid(ln_num_blocks(rows)), block(64 * EW);
   enh_dispatch(D, [&](auto vec, auto ch) {
     constexpr int V = decltype(vec)::value, C = decltype(ch)::value;
     if (norm)
-      hipLaunchKernelGGL((k_rope_fwd<V, C, true>), grid, block, 0, s, x, rot, w1, b1, w2, b2, eps1, eps2, x1, h2,
+      row_launch(k_rope_fwd<V, C, true>, rows, s, x, rot, w1, b1, w2, b2, eps1, eps2, x1, h2,
                          stats, rows, T, D, thr, scale, rng);
     else
-      hipLaunchKernelGGL((k_rope_fwd<V, C, false>), grid, block, 0, s, x, rot, w1, b1, w2, b2, eps1, eps2, x1, h2,
+      row_launch(k_rope_fwd<V, C, false>, rows, s, x, rot, w1, b1, w2, b2, eps1, eps2, x1, h2,
                          stats, rows, T, D, 0u, 1.f, rng);
   });
   return hipGetLastError();
@@ -584,14 +427,13 @@ hipError_t launch_rope_bwd(const float* g1, const float* gh2, const float* x, co
                            float scale, const unsigned long long* rng, hipStream_t s) {
   const long long rows = (long long)B * T;
   const int nblk = ln_num_blocks(rows);
-  const dim3 grid(nblk), block(64 * EW);
   enh_dispatch(D, [&](auto vec, auto ch) {
     constexpr int V = decltype(vec)::value, C = decltype(ch)::value;
     if (norm)
-      hipLaunchKernelGGL((k_rope_bwd<V, C, true>), grid, block, 0, s, g1, gh2, x, rot, w1, b1, w2, stats, gx, part,
+      row_launch(k_rope_bwd<V, C, true>, rows, s, g1, gh2, x, rot, w1, b1, w2, stats, gx, part,
                          rows, T, D, thr, scale, rng);
     else
-      hipLaunchKernelGGL((k_rope_bwd<V, C, false>), grid, block, 0, s, g1, gh2, x, rot, w1, b1, w2, stats, gx, part,
+      row_launch(k_rope_bwd<V, C, false>, rows, s, g1, gh2, x, rot, w1, b1, w2, stats, gx, part,
                          rows, T, D, 0u, 1.f, rng);
   });
   if (hipError_t e = hipGetLastError()) return e;
@@ -604,9 +446,8 @@ hipError_t launch_res_fwd(const float* x1, const float* p, const float* w3, cons
                           float* h3, cf* stats, int B, int T, int D, unsigned thr, float scale,
                           const unsigned long long* rng, hipStream_t s) {
   const long long rows = (long long)B * T;
-  const dim3 grid(ln_num_blocks(rows)), block(64 * EW);
   enh_dispatch(D, [&](auto vec, auto ch) {
-    hipLaunchKernelGGL((k_res_fwd<decltype(vec)::value, decltype(ch)::value>), grid, block, 0, s, x1, p, w3, b3, eps,
+    row_launch(k_res_fwd<decltype(vec)::value, decltype(ch)::value>, rows, s, x1, p, w3, b3, eps,
                        x2, h3, stats, rows, T, D, thr, scale, rng);
   });
   return hipGetLastError();
@@ -617,9 +458,8 @@ hipError_t launch_res_bwd(const float* g2, const float* gh3, const float* x2, co
                           float scale, const unsigned long long* rng, hipStream_t s) {
   const long long rows = (long long)B * T;
   const int nblk = ln_num_blocks(rows);
-  const dim3 grid(nblk), block(64 * EW);
   enh_dispatch(D, [&](auto vec, auto ch) {
-    hipLaunchKernelGGL((k_res_bwd<decltype(vec)::value, decltype(ch)::value>), grid, block, 0, s, g2, gh3, x2, w3,
+    row_launch(k_res_bwd<decltype(vec)::value, decltype(ch)::value>, rows, s, g2, gh3, x2, w3,
                        stats, gx1, gp, part, rows, T, D, thr, scale, rng);
   });
   if (hipError_t e = hipGetLastError()) return e;
@@ -630,9 +470,8 @@ hipError_t launch_gate_blend_fwd(const float* a, const float* v, const float* x2
                                  float eps, float* x3, cf* stats, int B, int T, int D, unsigned thr, float scale,
                                  const unsigned long long* rng, hipStream_t s) {
   const long long rows = (long long)B * T;
-  const dim3 grid(ln_num_blocks(rows)), block(64 * EW);
   enh_dispatch(D, [&](auto vec, auto ch) {
-    hipLaunchKernelGGL((k_gate_fwd<decltype(vec)::value, decltype(ch)::value>), grid, block, 0, s, a, v, x2, wg, bg,
+    row_launch(k_gate_fwd<decltype(vec)::value, decltype(ch)::value>, rows, s, a, v, x2, wg, bg,
                        eps, x3, stats, rows, T, D, thr, scale, rng);
   });
   return hipGetLastError();
@@ -644,9 +483,8 @@ hipError_t launch_gate_blend_bwd(const float* g3, const float* a, const float* v
                                  hipStream_t s) {
   const long long rows = (long long)B * T;
   const int nblk = ln_num_blocks(rows);
-  const dim3 grid(nblk), block(64 * EW);
   enh_dispatch(D, [&](auto vec, auto ch) {
-    hipLaunchKernelGGL((k_gate_bwd<decltype(vec)::value, decltype(ch)::value>), grid, block, 0, s, g3, a, v, wg, bg,
+    row_launch(k_gate_bwd<decltype(vec)::value, decltype(ch)::value>, rows, s, g3, a, v, wg, bg,
                        stats, ga, gv, part, rows, T, D, thr, scale, rng);
   });
   if (hipError_t e = hipGetLastError()) return e;

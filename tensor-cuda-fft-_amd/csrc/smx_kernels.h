@@ -217,8 +217,9 @@ hipError_t launch_gate_bwd(const cf* g, const cf* x, const cf* a, const float* u
                            hipStream_t s);
 
 // ---- LayerNorm row kernels of the fused block (smx_block.hip) -------------------------------------
+constexpr int ROW_WAVES = 4;             // wavefronts (rows in flight) per block of the kernels sized by ln_num_blocks
 constexpr int LN_MAX_BLOCKS = 2048;      // most rows of the grad_gamma / grad_beta partial buffer
-int ln_num_blocks(long long rows);       // blocks (= partial rows) launch_ln_bwd uses for `rows` rows
+int ln_num_blocks(long long rows);       // blocks (= partial rows) a backward launch uses for `rows` rows, ROW_WAVES each
 constexpr int LN_MAX_D = 4096;           // widest row held in registers (D % 4 == 0)
 constexpr int LN_MAX_D_ODD = 1024;       // same for the scalar variant (D % 4 != 0)
 bool ln_supported(int D);

@@ -1,6 +1,12 @@
-// smx_rows.h -- per-row helpers of the one-wavefront-per-row kernels (smx_block.hip, smx_enh.hip):
-// a row lives in one wavefront's registers, lane l holding elements (l + 64 c) VEC + [0, VEC), c < CH.
+// smx_rows.h -- the toolkit of the one-wavefront-per-row kernels (smx_block.hip, smx_enh.hip, and SpectralLayerNorm,
+// the gate chain and the fusion line of smx_time.hip): a row lives in one wavefront's registers, lane l holding elements
+// (l + 64 c) VEC + [0, VEC), c < CH.  Here: the wave sum, the Vec<VEC> chunk with its load policies, free functions on
+// Vec<VEC>[CH] rows (load, store, LayerNorm statistics, the LayerNorm-backward step, the block partials of the parameter
+// gradients), the dropout factors, and the host side: the (VEC, CH) dispatch on the row width and the launch of the
+// kernels that walk rows ROW_WAVES at a time.
 #pragma once
+#include <type_traits>
+
 #include "smx_kernels.h"
 
 namespace smx {
@@ -63,6 +69,166 @@ template <> struct Vec<2> {
     __builtin_nontemporal_store(w, reinterpret_cast<f32x2*>(p));
   }
 };
+
+template <int VEC, int CH>
+__device__ __forceinline__ void zero(Vec<VEC> (&r)[CH]) {
+#pragma unroll
+  for (int c = 0; c < CH; ++c)
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) r[c].v[i] = 0.f;
+}
+
+template <int VEC, int CH>
+__device__ __forceinline__ void row_load(Vec<VEC> (&r)[CH], const float* p, int D, int lane) {
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    const int e = (lane + 64 * c) * VEC;
+    if (e < D) r[c].load(p + e);
+    else
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) r[c].v[i] = 0.f;
+  }
+}
+
+// parameters (gamma / beta, rotation rows): re-read by every wavefront, so through the caches
+template <int VEC, int CH>
+__device__ __forceinline__ void row_load_cached(Vec<VEC> (&r)[CH], const float* p, int D, int lane, float dflt) {
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    const int e = (lane + 64 * c) * VEC;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) r[c].v[i] = dflt;
+    if (p && e < D) r[c].load_cached(p + e);
+  }
+}
+
+template <int VEC, int CH>
+__device__ __forceinline__ void row_store(const Vec<VEC> (&r)[CH], float* p, int D, int lane) {
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    const int e = (lane + 64 * c) * VEC;
+    if (e < D) r[c].store(p + e);
+  }
+}
+
+template <int VEC, int CH>
+__device__ __forceinline__ float row_sum(const Vec<VEC> (&r)[CH]) {
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < CH; ++c)
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s += r[c].v[i];
+  return s;
+}
+
+// sum of (r - mean)^2 over the D valid elements of this lane
+template <int VEC, int CH>
+__device__ __forceinline__ float row_sq(const Vec<VEC> (&r)[CH], float mean, int D, int lane) {
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    const int e = (lane + 64 * c) * VEC;
+    if (e < D)
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) { const float d = r[c].v[i] - mean; s = fmaf(d, d, s); }
+  }
+  return s;
+}
+
+// (mean, rstd) of a D-wide row: biased variance, two passes over the registers (torch.nn.LayerNorm)
+template <int VEC, int CH>
+__device__ __forceinline__ cf row_stats(const Vec<VEC> (&r)[CH], int D, int lane, float eps) {
+  const float inv_d = 1.f / (float)D;
+  const float mean = wave_sum(row_sum(r)) * inv_d;
+  const float var = wave_sum(row_sq(r, mean, D, lane)) * inv_d;
+  return mk(mean, 1.f / sqrtf(var + eps));
+}
+
+// The LayerNorm-backward step of one row, in its two halves around the wave sums.  gh: gradient of the LayerNorm's
+// output, xh: its normalised input (0 on the padding), u = gamma gh:
+//   ln_bwd_acc, per element:  ag += gh xh,  ab += gh,  s1 += u,  s2 += u xh;  returns u
+//   ln_bwd_apply, per row:    G += rstd (u - m1 - xh m2),  m1 = mean_d(u) = wave_sum(s1) / D,  m2 = mean_d(u xh)
+__device__ __forceinline__ float ln_bwd_acc(float gh, float xh, float gm, float& ag, float& ab, float& s1, float& s2) {
+  const float u = gm * gh;
+  s1 += u;
+  s2 = fmaf(u, xh, s2);
+  ag = fmaf(gh, xh, ag);
+  ab += gh;
+  return u;
+}
+template <int VEC, int CH>
+__device__ __forceinline__ void ln_bwd_apply(Vec<VEC> (&G)[CH], const Vec<VEC> (&u)[CH], const Vec<VEC> (&xh)[CH],
+                                             float rstd, float m1, float m2) {
+#pragma unroll
+  for (int c = 0; c < CH; ++c)
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) G[c].v[i] = fmaf(rstd, u[c].v[i] - m1 - xh[c].v[i] * m2, G[c].v[i]);
+}
+
+// mask * 1/(1-p) of elements e0 .. e0 + VEC - 1 of a batch row (e0 even): the pair (2i, 2i+1) shares one hash
+template <int VEC>
+__device__ __forceinline__ void drop_factors(float (&m)[VEC], unsigned key, unsigned long long e0, unsigned thr,
+                                             float scale) {
+#pragma unroll
+  for (int i = 0; i < VEC; i += 2) {
+    const unsigned h = drop_hash((unsigned)((e0 + i) >> 1), key);
+    m[i] = (h & 0xffffu) >= thr ? scale : 0.f;
+    m[i + 1] = (h >> 16) >= thr ? scale : 0.f;
+  }
+}
+
+// Block partials of a LayerNorm's gamma / beta gradients: part[0][off + e] = sum_rows ag, part[1][off + e] = sum_rows
+// ab, with part pointing at this block's (2, W) slab.  Waves are added in index order.
+template <int VEC, int CH>
+__device__ __forceinline__ void block_partials(const Vec<VEC> (&ag)[CH], const Vec<VEC> (&ab)[CH], float* part, int W,
+                                               int off, int D, float (*red)[2][64 * VEC], int lane, int wv) {
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      red[wv][0][lane * VEC + i] = ag[c].v[i];
+      red[wv][1][lane * VEC + i] = ab[c].v[i];
+    }
+    __syncthreads();
+    if (wv == 0) {
+      const int e = (lane + 64 * c) * VEC;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        if (e + i < D) {
+          float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+          for (int w2 = 0; w2 < ROW_WAVES; ++w2) {
+            a0 += red[w2][0][lane * VEC + i];
+            a1 += red[w2][1][lane * VEC + i];
+          }
+          part[off + e + i] = a0;
+          part[W + off + e + i] = a1;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+// f(VEC, CH) as integral constants, CH the smallest of 1, STEP, STEP^2, ... <= MAX whose tile of 64 VEC CH elements
+// covers a D-wide row; false (and no call) when none does.  A kernel family names its vector widths and ladders.
+template <int VEC, int MAX, int STEP = 2, int CH = 1, typename Fn>
+bool row_dispatch(int D, Fn&& f) {
+  if constexpr (CH > MAX) {
+    return false;
+  } else {
+    if (D > 64 * VEC * CH) return row_dispatch<VEC, MAX, STEP, CH * STEP>(D, f);
+    f(std::integral_constant<int, VEC>(), std::integral_constant<int, CH>());
+    return true;
+  }
+}
+
+// Launch of a kernel that walks the rows ROW_WAVES at a time: its grid is what ln_num_blocks sizes the partial buffers by
+template <typename... P, typename... A>
+void row_launch(void (*k)(P...), long long rows, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(k, dim3(ln_num_blocks(rows)), dim3(64 * ROW_WAVES), 0, s, args...);
+}
 
 }  // namespace
 

@@ -16,7 +16,10 @@
 // sliding window in registers (four channels per thread, 16-byte accesses, when C % 4 == 0); grid = channel groups x
 // B * ceil(T / TR) blocks.  Backward: the per-channel sums of a block go to a partial buffer [block][5][C]; two small launches
 // add them in block order -- fixed order, bitwise reproducible.
+// Further down SpectralLayerNorm, the gate chain and the fusion line reduce over a wavefront with smx_rows.h's wave_sum,
+// and SpectralLayerNorm's launches pick their register tile with its row_dispatch.
 #include "smx_kernels.h"
+#include "smx_rows.h"
 
 namespace smx {
 
@@ -25,10 +28,11 @@ namespace {
 constexpr int DW_TR = 32;            // rows per block
 constexpr int DW_TPB = 256;
 
-// V channels per thread: 4 (one 16-byte access per row; C % 4 == 0 and 16-byte aligned bases) or 1
-template <int V> struct Vec { float v[V]; };
-template <int V> __device__ __forceinline__ Vec<V> ldv(const float* p) {
-  Vec<V> r;
+// V channels per thread: 4 (one 16-byte access per row; C % 4 == 0 and 16-byte aligned bases) or 1.  Not the Vec of
+// smx_rows.h: these are plain (cached) loads AND stores, a row chunk's are nontemporal.
+template <int V> struct ChanVec { float v[V]; };
+template <int V> __device__ __forceinline__ ChanVec<V> ldv(const float* p) {
+  ChanVec<V> r;
   if constexpr (V == 4) {
     const f32x4 q = *reinterpret_cast<const f32x4*>(p);
     r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
@@ -37,7 +41,7 @@ template <int V> __device__ __forceinline__ Vec<V> ldv(const float* p) {
   }
   return r;
 }
-template <int V> __device__ __forceinline__ void stv(float* p, const Vec<V>& a) {
+template <int V> __device__ __forceinline__ void stv(float* p, const ChanVec<V>& a) {
   if constexpr (V == 4) {
     f32x4 q; q.x = a.v[0]; q.y = a.v[1]; q.z = a.v[2]; q.w = a.v[3];
     *reinterpret_cast<f32x4*>(p) = q;
@@ -45,8 +49,8 @@ template <int V> __device__ __forceinline__ void stv(float* p, const Vec<V>& a) 
     *p = a.v[0];
   }
 }
-template <int V> __device__ __forceinline__ Vec<V> zerov() {
-  Vec<V> r;
+template <int V> __device__ __forceinline__ ChanVec<V> zerov() {
+  ChanVec<V> r;
 #pragma unroll
   for (int i = 0; i < V; ++i) r.v[i] = 0.f;
   return r;
@@ -72,13 +76,13 @@ __global__ __launch_bounds__(DW_TPB) void k_dwconv3_fwd(const float* __restrict_
   }
   const float* xb = x + (size_t)b * T * C + c;
   float* yb = y + (size_t)b * T * C + c;
-  Vec<V> xm2 = t0 >= 2 ? ldv<V>(xb + (size_t)(t0 - 2) * C) : zerov<V>();
-  Vec<V> xm1 = t0 >= 1 ? ldv<V>(xb + (size_t)(t0 - 1) * C) : zerov<V>();
+  ChanVec<V> xm2 = t0 >= 2 ? ldv<V>(xb + (size_t)(t0 - 2) * C) : zerov<V>();
+  ChanVec<V> xm1 = t0 >= 1 ? ldv<V>(xb + (size_t)(t0 - 1) * C) : zerov<V>();
 #pragma unroll 4
   for (int t = t0; t < t1; ++t) {
-    const Vec<V> xt = ldv<V>(xb + (size_t)t * C);
+    const ChanVec<V> xt = ldv<V>(xb + (size_t)t * C);
     const bool tap2 = t <= T - 2;
-    Vec<V> o;
+    ChanVec<V> o;
 #pragma unroll
     for (int i = 0; i < V; ++i) {
       float v = __builtin_fmaf(w0[i], xm2.v[i], bi[i]);
@@ -117,17 +121,17 @@ __global__ __launch_bounds__(DW_TPB) void k_dwconv3_bwd(const float* __restrict_
   const float* gb = g + (size_t)b * T * C + c;
   const float* xb = x + (size_t)b * T * C + c;
   float* gxb = gx ? gx + (size_t)b * T * C + c : nullptr;
-  Vec<V> xm2 = t0 >= 2 ? ldv<V>(xb + (size_t)(t0 - 2) * C) : zerov<V>();
-  Vec<V> xm1 = t0 >= 1 ? ldv<V>(xb + (size_t)(t0 - 1) * C) : zerov<V>();
-  Vec<V> g0 = ldv<V>(gb + (size_t)t0 * C);                       // g[t], g[t+1], g[t+2] (0 past the end)
-  Vec<V> g1 = t0 + 1 < T ? ldv<V>(gb + (size_t)(t0 + 1) * C) : zerov<V>();
-  Vec<V> a0 = zerov<V>(), a1 = zerov<V>(), a2 = zerov<V>(), ab = zerov<V>(), as = zerov<V>();
+  ChanVec<V> xm2 = t0 >= 2 ? ldv<V>(xb + (size_t)(t0 - 2) * C) : zerov<V>();
+  ChanVec<V> xm1 = t0 >= 1 ? ldv<V>(xb + (size_t)(t0 - 1) * C) : zerov<V>();
+  ChanVec<V> g0 = ldv<V>(gb + (size_t)t0 * C);                       // g[t], g[t+1], g[t+2] (0 past the end)
+  ChanVec<V> g1 = t0 + 1 < T ? ldv<V>(gb + (size_t)(t0 + 1) * C) : zerov<V>();
+  ChanVec<V> a0 = zerov<V>(), a1 = zerov<V>(), a2 = zerov<V>(), ab = zerov<V>(), as = zerov<V>();
 #pragma unroll 4
   for (int t = t0; t < t1; ++t) {
-    const Vec<V> g2 = t + 2 < T ? ldv<V>(gb + (size_t)(t + 2) * C) : zerov<V>();
-    const Vec<V> xt = ldv<V>(xb + (size_t)t * C);
+    const ChanVec<V> g2 = t + 2 < T ? ldv<V>(gb + (size_t)(t + 2) * C) : zerov<V>();
+    const ChanVec<V> xt = ldv<V>(xb + (size_t)t * C);
     const bool tap2 = t <= T - 2;
-    Vec<V> o;
+    ChanVec<V> o;
 #pragma unroll
     for (int i = 0; i < V; ++i) {
       float v = w0[i] * g2.v[i];
@@ -205,20 +209,6 @@ __global__ __launch_bounds__(DW_TPB) void k_dwconv3_sum_b(const float* __restric
 // fixed order -- bitwise reproducible, no second launch.
 constexpr int SLN_WAVES = 4;
 
-template <int CTRL, int ROW_MASK, bool BOUND>
-__device__ __forceinline__ float sln_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, BOUND));
-}
-__device__ __forceinline__ float sln_wave_sum(float v) {       // as wave_sum in smx_block.hip
-  v += sln_dpp<0x111, 0xf, true>(v);
-  v += sln_dpp<0x112, 0xf, true>(v);
-  v += sln_dpp<0x114, 0xf, true>(v);
-  v += sln_dpp<0x118, 0xf, true>(v);
-  v += sln_dpp<0x142, 0xa, false>(v);
-  v += sln_dpp<0x143, 0xc, false>(v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
 template <int CH>
 struct SlnRow {
   cf u[CH];            // unit phases
@@ -238,12 +228,12 @@ __device__ __forceinline__ void sln_stats(const cf (&z)[CH], int lane, int C, fl
     sm += o.m[k];
   }
   const float inv_c = 1.f / (float)C;
-  const float mu = sln_wave_sum(sm) * inv_c;
+  const float mu = wave_sum(sm) * inv_c;
   float v2 = 0.f;
 #pragma unroll
   for (int k = 0; k < CH; ++k)
     if (lane + 64 * k < C) { const float d = o.m[k] - mu; v2 = __builtin_fmaf(d, d, v2); }
-  o.r = 1.f / sqrtf(sln_wave_sum(v2) * inv_c + eps);
+  o.r = 1.f / sqrtf(wave_sum(v2) * inv_c + eps);
 #pragma unroll
   for (int k = 0; k < CH; ++k) o.sh[k] = (o.m[k] - mu) * o.r;
 }
@@ -326,7 +316,7 @@ __global__ __launch_bounds__(64 * SLN_WAVES) void k_sln_bwd(const cf* __restrict
       dg[k] = __builtin_fmaf(ds[k], st.sh[k], dg[k]);
       db[k] += ds[k];
     }
-    const float ma = sln_wave_sum(sa) * inv_c, mas = sln_wave_sum(sas) * inv_c;
+    const float ma = wave_sum(sa) * inv_c, mas = wave_sum(sas) * inv_c;
     if (gz) {
 #pragma unroll
       for (int k = 0; k < CH; ++k) {
@@ -355,14 +345,6 @@ __global__ __launch_bounds__(64 * SLN_WAVES) void k_sln_bwd(const cf* __restrict
   }
 }
 
-template <typename F1, typename F2, typename F4, typename F8, typename F16>
-bool sln_dispatch(int C, F1 f1, F2 f2, F4 f4, F8 f8, F16 f16) {
-  const int ch = (C + 63) / 64;
-  if (ch <= 1) f1(); else if (ch <= 2) f2(); else if (ch <= 4) f4(); else if (ch <= 8) f8(); else if (ch <= 16) f16();
-  else return false;
-  return true;
-}
-
 }  // namespace
 
 bool spectral_ln_supported(int C) { return C >= 1 && C <= 1024; }
@@ -371,20 +353,22 @@ hipError_t launch_spectral_ln_fwd(const cf* z, const float* gamma, const float* 
                                   int B, int F, int C, hipStream_t s) {
   const long long rows = (long long)B * F;
   const dim3 grid((unsigned)((rows + SLN_WAVES - 1) / SLN_WAVES)), block(64 * SLN_WAVES);
-#define SLN_F(CH) [&] { if (planar) hipLaunchKernelGGL((k_sln_fwd<CH, true>), grid, block, 0, s, z, gamma, beta, eps, out, rows, F, C); \
-                        else hipLaunchKernelGGL((k_sln_fwd<CH, false>), grid, block, 0, s, z, gamma, beta, eps, out, rows, F, C); }
-  if (!sln_dispatch(C, SLN_F(1), SLN_F(2), SLN_F(4), SLN_F(8), SLN_F(16))) return hipErrorInvalidValue;
-#undef SLN_F
-  return hipGetLastError();
+  const bool ok = row_dispatch<1, 16>(C, [&](auto, auto ch) {
+    constexpr int CH = decltype(ch)::value;
+    if (planar) hipLaunchKernelGGL((k_sln_fwd<CH, true>), grid, block, 0, s, z, gamma, beta, eps, out, rows, F, C);
+    else hipLaunchKernelGGL((k_sln_fwd<CH, false>), grid, block, 0, s, z, gamma, beta, eps, out, rows, F, C);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 hipError_t launch_spectral_ln_bwd(const cf* g, const cf* z, const float* gamma, const float* beta, float eps, cf* gz,
                                   float* ggamma, float* gbeta, int planar, int B, int F, int C, hipStream_t s) {
   const dim3 grid(F), block(64 * SLN_WAVES);
-#define SLN_B(CH) [&] { if (planar) hipLaunchKernelGGL((k_sln_bwd<CH, true>), grid, block, 0, s, g, z, gamma, beta, eps, gz, ggamma, gbeta, B, F, C); \
-                        else hipLaunchKernelGGL((k_sln_bwd<CH, false>), grid, block, 0, s, g, z, gamma, beta, eps, gz, ggamma, gbeta, B, F, C); }
-  if (!sln_dispatch(C, SLN_B(1), SLN_B(2), SLN_B(4), SLN_B(8), SLN_B(16))) return hipErrorInvalidValue;
-#undef SLN_B
-  return hipGetLastError();
+  const bool ok = row_dispatch<1, 16>(C, [&](auto, auto ch) {
+    constexpr int CH = decltype(ch)::value;
+    if (planar) hipLaunchKernelGGL((k_sln_bwd<CH, true>), grid, block, 0, s, g, z, gamma, beta, eps, gz, ggamma, gbeta, B, F, C);
+    else hipLaunchKernelGGL((k_sln_bwd<CH, false>), grid, block, 0, s, g, z, gamma, beta, eps, gz, ggamma, gbeta, B, F, C);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ---- the planar side of SpectralFFN (reference fft_lm/frequency_native.py:167-189) --------------------------------------
@@ -632,7 +616,7 @@ __global__ __launch_bounds__(64 * GT_WAVES) void k_gate_bwd(const cf* __restrict
         st4s(reinterpret_cast<float*>(&gx[((size_t)b * F + f) * C + c]), o);
       }
     }
-    s_re = sln_wave_sum(s_re); s_im = sln_wave_sum(s_im);      // lane 63 holds the totals
+    s_re = wave_sum(s_re); s_im = wave_sum(s_im);      // lane 63 holds the totals
     if (lane == 63) prt[f] = mk(s_re, s_im);
   };
   for (int f = wv; f < F; f += 2 * GT_WAVES) {                 // two bins in flight per wave
@@ -734,7 +718,7 @@ __global__ __launch_bounds__(256) void k_mix_bwd(const float* __restrict__ g, co
     if (gb) st4s(gb + 4 * i, o2);
     if (gc) st4s(gc + 4 * i, o3);
   }
-  sa = sln_wave_sum(sa); sb = sln_wave_sum(sb);
+  sa = wave_sum(sa); sb = wave_sum(sb);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 63) { red[0][wv] = sa; red[1][wv] = sb; }
   __syncthreads();
@@ -746,7 +730,7 @@ __global__ __launch_bounds__(256) void k_mix_bwd(const float* __restrict__ g, co
 __global__ __launch_bounds__(64) void k_mix_sum(const float* __restrict__ part, float* __restrict__ gw, int nb) {
   float sa = 0.f, sb = 0.f;                                        // lane-strided, then one wave sum: fixed order
   for (int i = threadIdx.x; i < nb; i += 64) { sa += part[2 * i]; sb += part[2 * i + 1]; }
-  sa = sln_wave_sum(sa); sb = sln_wave_sum(sb);
+  sa = wave_sum(sa); sb = wave_sum(sb);
   if (threadIdx.x == 63) { gw[0] = sa; gw[1] = sb; }
 }
 
