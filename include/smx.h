@@ -415,6 +415,32 @@ int smx_block_backward_dropout(const float* g, const float* x, const float* ln_s
                                size_t workspace_bytes, int B, int N, int D, int F, int phases,
                                float dropout_p, const void* rng_state, const float* filter_pack,
                                void* stream);
+/* 2-byte activations of the block line: smx_block_forward_io / smx_block_backward_io are smx_block_forward_dropout /
+ * smx_block_backward_dropout with x, y, g, grad_x in the element type `io` (SMX_IO_F32: exactly the f32 entries, grad_h
+ * ignored).  The contract of smx_forward_io: arithmetic in f32, the 2-byte input widened exactly, y and grad_x rounded
+ * once at the store to nearest even (a NaN stays a NaN, fp16 overflow goes to +-inf) -- y and grad_x equal the f32
+ * entry's on the widened input, rounded to `io`, bit for bit; ln_stats, xk_save and all five parameter gradients equal
+ * the f32 entry's, bit for bit.  Everything but the four activations keeps its f32 type; the workspace is the same.
+ * grad_h: a (B, N, D) f32 scratch of the caller, 16-byte aligned, required for a 2-byte `io`: the gradient of the
+ * LayerNorm's output stays f32 between the transform and the LayerNorm backward (a 2-byte grad_h would round it a
+ * second time), so the backward is not in place.  Phase-split calls hand the same grad_h to every phase; the LayerNorm
+ * backward belongs to SMX_PHASE_INVERSE as in smx_block_backward.
+ * Native 2-byte block rows exist on the decimated single-launch plan (smx_plan: nsplit == 1, groups == 1, k <= 512, not
+ * four-step / eight-band) with D % 4 == 0: smx_block_io_supported == 1 (for SMX_IO_F32 it is smx_block_supported(D)).
+ * Any other shape returns SMX_ERR_UNSUPPORTED with nothing written: the caller widens the input and calls the f32 entry.
+ * Pointers: x / y / g / grad_x 8-byte aligned for a 2-byte `io`.
+ * Replaces: reference fft_tensor/spectral_layers.py:185 (x + spectral_mix(norm1(x)), with :154-158 and :162) and its
+ * autograd backward in bf16 / fp16 -- there a torch LayerNorm, the layer and a torch add, each rounding the activation. */
+int smx_block_io_supported(int B, int N, int D, int F, int io);
+int smx_block_forward_io(const void* x, const float* ln_w, const float* ln_b, float eps, const float* w_re,
+                         const float* w_im, const float* bias, void* y, float* xk_save, float* ln_stats,
+                         void* workspace, size_t workspace_bytes, int B, int N, int D, int F, float dropout_p,
+                         const void* rng_state, float* filter_pack, void* stream, int io);
+int smx_block_backward_io(const void* g, const void* x, const float* ln_stats, const float* ln_w, const float* xk,
+                          const float* w_re, const float* w_im, void* grad_x, float* g_ln_w, float* g_ln_b,
+                          float* gw_re, float* gw_im, float* gbias, float* grad_h, void* workspace,
+                          size_t workspace_bytes, int B, int N, int D, int F, int phases, float dropout_p,
+                          const void* rng_state, const float* filter_pack, void* stream, int io);
 
 /* The time path of fft_lm's BicameralBlock on the block's own (B, T, C) layout (round 4):
  *   y[b, t, c] = scale[b, c] * (bias[c] + w[c,0] x[b, t-2, c] + w[c,1] x[b, t-1, c] + w[c,2] x[b, t, c] * [t <= T-2])

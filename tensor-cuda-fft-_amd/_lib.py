@@ -128,6 +128,10 @@ _SIGS = {
     "smx_conv_io_supported": (_I, [ctypes.POINTER(smx_shape), _I]),
     "smx_conv_forward_io": (_I, [ctypes.POINTER(smx_shape), _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _P]),
     "smx_conv_backward_io": (_I, [ctypes.POINTER(smx_shape), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _P]),
+    "smx_block_io_supported": (_I, [_I] * 5),
+    "smx_block_forward_io": (_I, [_P, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _SZ,
+                                  _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I]),
+    "smx_block_backward_io": (_I, [_P] * 15 + [_SZ, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I]),
 }
 
 
@@ -140,7 +144,8 @@ _SINCE = {"smx_diag_clock": 302, "smx_dwconv3_workspace_bytes": 302, "smx_dwconv
           "smx_rope_norm_forward": 303, "smx_rope_norm_backward": 303, "smx_residual_norm_forward": 303,
           "smx_residual_norm_backward": 303, "smx_gate_blend_forward": 303, "smx_gate_blend_backward": 303,
           "smx_io_supported": 303, "smx_forward_io": 303, "smx_backward_io": 303, "smx_conv_io_supported": 303,
-          "smx_conv_forward_io": 303, "smx_conv_backward_io": 303}        # entry points younger than the oldest library the A/B tools still load
+          "smx_conv_forward_io": 303, "smx_conv_backward_io": 303, "smx_block_io_supported": 303,
+          "smx_block_forward_io": 303, "smx_block_backward_io": 303}        # entry points younger than the oldest library the A/B tools still load
 
 
 def load(path: str):
@@ -201,6 +206,11 @@ SMX_IO_F32, SMX_IO_BF16, SMX_IO_F16 = 0, 1, 2       # include/smx.h: element typ
 def io_supported(B: int, N: int, D: int, F: int, io: int) -> bool:
     """True when the plan of this layer shape (current options) reads and writes `io` elements natively."""
     return bool(lib().smx_io_supported(B, N, D, F, io))
+
+
+def block_io_supported(B: int, N: int, D: int, F: int, io: int) -> bool:
+    """True when the fused block line of this shape (current options) reads and writes `io` elements natively."""
+    return bool(lib().smx_block_io_supported(B, N, D, F, io))
 
 
 def conv_io_supported(B: int, R: int, D: int, n_fft: int, io: int) -> bool:

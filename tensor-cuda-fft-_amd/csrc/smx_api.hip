@@ -828,7 +828,8 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
                          const float* w_im, float* grad_x, float* gw_re, float* gw_im, float* gbias,
                          void* workspace, size_t workspace_bytes, int phases, float dropout_p,
                          const void* rng_state, const float* filter_pack, void* stream,
-                         const float* row_scale = nullptr, float* grad_row_scale = nullptr, int io = SMX_IO_F32);
+                         const float* row_scale = nullptr, float* grad_row_scale = nullptr, int io = SMX_IO_F32,
+                         int oio = -1);
 
 int smx_backward_dropout(const float* g, const float* xk, const float* w_re, const float* w_im,
                          float* grad_x, float* gw_re, float* gw_im, float* gbias, void* workspace,
@@ -854,7 +855,10 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
                          const float* w_im, float* grad_x, float* gw_re, float* gw_im, float* gbias,
                          void* workspace, size_t workspace_bytes, int phases, float dropout_p,
                          const void* rng_state, const float* filter_pack, void* stream,
-                         const float* row_scale, float* grad_row_scale, int io) {
+                         const float* row_scale, float* grad_row_scale, int io, int oio) {
+  // oio: element type of grad_x where it is not g's (-1: io).  The 2-byte block backward alone passes SMX_IO_F32 here:
+  // its "grad_x" is grad_h, read unrounded by the LayerNorm backward.  Mode 1 then (the only such instance of k_fused).
+  if (oio < 0) oio = io;
   const int B = h.B, N = h.N, D = h.D, F = h.F;
   DropCfg dc;
   if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
@@ -866,10 +870,10 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
   const bool want_w = gw_re || gw_im || gbias;
   if (want_w && !(gw_re && gw_im && gbias))
     return fail(SMX_ERR_INVALID, "gw_re, gw_im, gbias must be given together");
-  if (io != SMX_IO_F32) {
+  if (io != SMX_IO_F32 && oio == io) {
     if (((uintptr_t)g | (uintptr_t)grad_x) & 3)
       return fail(SMX_ERR_INVALID, "2-byte g and grad_x must be 4-byte aligned");
-  } else if (((uintptr_t)g | (uintptr_t)grad_x) & 7)
+  } else if ((((uintptr_t)g) & (io != SMX_IO_F32 ? 3 : 7)) | ((uintptr_t)grad_x & 7))
     return fail(SMX_ERR_INVALID, "g and grad_x must be 8-byte aligned");
   if ((uintptr_t)xk & 15) return fail(SMX_ERR_INVALID, "xk must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
@@ -878,7 +882,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
     return fail(SMX_ERR_UNSUPPORTED, "no 2-byte I/O on this plan (smx_io_supported): widen g and call "
                 "smx_backward_dropout");
   if (dc.thr && h.R < N) return fail(SMX_ERR_UNSUPPORTED, "fused dropout is not available with zero-padded rows");
-  if ((want_w || dc.thr || grad_row_scale) && !xk && p.k > 0)
+  if ((want_w || dc.thr || grad_row_scale || oio != io) && !xk && p.k > 0)
     return fail(SMX_ERR_INVALID, "xk (saved spectrum) is NULL");
   if ((row_scale || grad_row_scale) &&
       !(p.path == SMX_PATH_DECIMATED && (p.groups == 1 || p.fs)))
@@ -922,14 +926,14 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
     return SMX_OK;
   }
   if (p.path == SMX_PATH_DECIMATED) {
-    DecimArgs a = decim_args(p, t, h, ws, w, io != SMX_IO_F32 ? 2 : 4);
+    DecimArgs a = decim_args(p, t, h, ws, w, oio != SMX_IO_F32 ? 2 : 4);
     a.in = g; a.out = grad_x;
     a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.conj_w = 1;
     a.fa.xk_in = xk; a.fa.pslab = (float*)(ws + w.slab); a.fa.gb_part = (float*)(ws + w.gbp);
     // mode 0 with xk_out == NULL: input gradient only (with dropout the mask goes on the LOADED tile,
     // which only the mode-1 instantiation does: use it, the products land in the workspace unused)
     const bool pre_drop = dc.thr && (p.fs || p.full8 || p.groups > 1);      // (see below)
-    const int mode = (want_w || (dc.thr && !pre_drop) || grad_row_scale) ? 1 : 0;
+    const int mode = (want_w || (dc.thr && !pre_drop) || grad_row_scale || oio != io) ? 1 : 0;
     a.fa.sc = row_scale; a.fa.gsc = grad_row_scale;
     if (p.fs && grad_row_scale) a.fa.gsc_part = (cf*)(ws + w.gscp);
     // four-step / eight-band plans: the masked upstream gradient is staged in grad_x first (their kernels read the whole
@@ -1023,20 +1027,20 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
         a.fa.slab_agent = 1;
         if (!sync_clean) HIP_TRY(hipMemsetAsync(a.sync, 0, sync_words(B, D) * sizeof(unsigned), s));
       }
-      HIP_TRY(launch_fused(a, p.nb, mode, s, io));
+      HIP_TRY(launch_fused(a, p.nb, mode, s, io, oio));
       if (fold) return SMX_OK;
     } else {
       if (do_spec) {
         if (p.nsplit == 1) {          // forward half + filter in one launch, S parked in the workspace
           DecimArgs h = a;
           h.out = nullptr;
-          HIP_TRY(launch_fused(h, p.nb, mode, s, io));
+          HIP_TRY(launch_fused(h, p.nb, mode, s, io, oio));
         } else {
           HIP_TRY(launch_split_a(a, p.nb, true, s, io));
           HIP_TRY(launch_split_f(a, p.nb, mode, s));
         }
       }
-      if (do_inv) HIP_TRY(launch_split_b(a, p.nb, false, s, io));
+      if (do_inv) HIP_TRY(launch_split_b(a, p.nb, false, s, oio));
     }
     if (do_par)
       HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, B,
@@ -1585,34 +1589,68 @@ int smx_block_forward(const float* x, const float* ln_w, const float* ln_b, floa
                                    stream);
 }
 
+// The fused block with 2-byte x / y / g / grad_x exists where k_fused_blk does -- the decimated single-launch plan --
+// and where the row kernels move 2-byte chunks (ln_io_supported: D % 4 == 0).
+static bool block_fused_plan(const Plan& p) {
+  return p.path == SMX_PATH_DECIMATED && p.nsplit == 1 && p.groups == 1 && !p.fs && !p.full8;
+}
+static bool block_io_native(const Plan& p, int D) { return block_fused_plan(p) && io_native(p) && ln_io_supported(D); }
+static const char* const BLOCK_IO_PLANS = "no 2-byte block rows on this plan (smx_block_io_supported: the decimated "
+                                          "single-launch plan, D %% 4 == 0): widen the input and call the f32 entry";
+
+static int block_forward_impl(const float* x, const float* ln_w, const float* ln_b, float eps,
+                              const float* w_re, const float* w_im, const float* bias, float* y,
+                              float* xk_save, float* ln_stats, void* workspace,
+                              size_t workspace_bytes, int B, int N, int D, int F, float dropout_p,
+                              const void* rng_state, float* filter_pack, void* stream, int io);
+
 int smx_block_forward_dropout(const float* x, const float* ln_w, const float* ln_b, float eps,
                               const float* w_re, const float* w_im, const float* bias, float* y,
                               float* xk_save, float* ln_stats, void* workspace,
                               size_t workspace_bytes, int B, int N, int D, int F, float dropout_p,
                               const void* rng_state, float* filter_pack, void* stream) {
+  return block_forward_impl(x, ln_w, ln_b, eps, w_re, w_im, bias, y, xk_save, ln_stats, workspace, workspace_bytes, B, N,
+                            D, F, dropout_p, rng_state, filter_pack, stream, SMX_IO_F32);
+}
+
+// io: element type of x and y (2-byte rows behind the float pointers, as in forward_impl)
+static int block_forward_impl(const float* x, const float* ln_w, const float* ln_b, float eps,
+                              const float* w_re, const float* w_im, const float* bias, float* y,
+                              float* xk_save, float* ln_stats, void* workspace,
+                              size_t workspace_bytes, int B, int N, int D, int F, float dropout_p,
+                              const void* rng_state, float* filter_pack, void* stream, int io) {
   if (int rc = check_shape(B, N, D, F)) return rc;
   DropCfg dc;
   if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
   if (!ln_supported(D)) return fail(SMX_ERR_UNSUPPORTED, "LayerNorm width D=%d is not supported", D);
+  if (io != SMX_IO_F32 && !block_io_native(make_plan(layer_shape(B, N, D, F)), D))
+    return fail(SMX_ERR_UNSUPPORTED, BLOCK_IO_PLANS);
   if (!x || !w_re || !w_im || !y || !ln_stats)
     return fail(SMX_ERR_INVALID, "x, w_re, w_im, y, ln_stats must be non-NULL");
   if (x == y) return fail(SMX_ERR_INVALID, "y must not alias x");
-  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)ln_stats) & 7)
-    return fail(SMX_ERR_INVALID, "x, y and ln_stats must be 8-byte aligned");
-  if (D % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)ln_w | (uintptr_t)ln_b) & 15))
-    return fail(SMX_ERR_INVALID, "x, y, ln_w, ln_b must be 16-byte aligned");
+  if (io != SMX_IO_F32) {
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)ln_stats) & 7)
+      return fail(SMX_ERR_INVALID, "2-byte x and y (D %% 4 == 0) and ln_stats must be 8-byte aligned");
+    if (((uintptr_t)ln_w | (uintptr_t)ln_b) & 15) return fail(SMX_ERR_INVALID, "ln_w, ln_b must be 16-byte aligned");
+  } else {
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)ln_stats) & 7)
+      return fail(SMX_ERR_INVALID, "x, y and ln_stats must be 8-byte aligned");
+    if (D % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)ln_w | (uintptr_t)ln_b) & 15))
+      return fail(SMX_ERR_INVALID, "x, y, ln_w, ln_b must be 16-byte aligned");
+  }
   if ((uintptr_t)xk_save & 15) return fail(SMX_ERR_INVALID, "xk_save must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const long long rows = (long long)B * N;
   const Shape h = layer_shape(B, N, D, F);
   const Plan p = make_plan(h);
   const bool by_groups = p.groups > 1 && !p.fs && !p.full8;
-  HIP_TRY(launch_ln_stats(x, (cf*)ln_stats, rows, D, eps, s));
-  if (p.path == SMX_PATH_DECIMATED && p.nsplit == 1 && p.groups == 1 && !p.fs && !p.full8) {
+  if (io != SMX_IO_F32) HIP_TRY(launch_ln_stats_io(x, (cf*)ln_stats, rows, D, eps, s, io));
+  else HIP_TRY(launch_ln_stats(x, (cf*)ln_stats, rows, D, eps, s));
+  if (block_fused_plan(p)) {
     TableRef t;
     if (int rc = get_tables(N, &t, s)) return rc;
     const Ws w = ws_layout(p, B, N, D);
-    DecimArgs a = decim_args(p, t, h, (char*)workspace, w);
+    DecimArgs a = decim_args(p, t, h, (char*)workspace, w, io != SMX_IO_F32 ? 2 : 4);
     a.in = x; a.out = y;
     a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.bias = bias; a.fa.conj_w = 0;
     a.fa.xk_out = xk_save;
@@ -1624,7 +1662,7 @@ int smx_block_forward_dropout(const float* x, const float* ln_w, const float* ln
     if (workspace && workspace_bytes >= w.total && !((uintptr_t)workspace & 255) &&
         sync_words(B, D) * sizeof(unsigned) <= SYNC_BYTES)
       a.sync = (unsigned*)((char*)workspace + w.sync);        // left zero for smx_block_backward (SYNC_CLEAN)
-    HIP_TRY(launch_fused_block(a, p.nb, s));
+    HIP_TRY(launch_fused_block(a, p.nb, s, io));
     return SMX_OK;
   }
   // other plans: normalise into y, transform y in place (every kernel reads its whole input column
@@ -2016,5 +2054,59 @@ int smx_conv_backward_io(const smx_shape* shape, const void* g, const float* x_s
                             grad_h_im, grad_row_scale, workspace, workspace_bytes, io, stream);
 }
 
-}  // extern "C"
+// ---- 2-byte activations of the fused block line (bf16 / fp16 x, y, g, grad_x) -----------------------------------------
+// Replaces: reference fft_tensor/spectral_layers.py:185 (x + spectral_mix(norm1(x)), with :154-158, :162) and its autograd
+// backward for half-precision activations -- there three torch ops with three roundings of the activation.  Same plan,
+// launches, work items and summation order as smx_block_forward_dropout / smx_block_backward_dropout; only the row I/O
+// of k_ln_stats, k_fused_blk, k_fused (mode 1: 2-byte g in, f32 grad_h out) and k_ln_bwd differs.
+int smx_block_io_supported(int B, int N, int D, int F, int io) {
+  if (io_check(io) || check_shape(B, N, D, F)) return 0;
+  if (io == SMX_IO_F32) return smx_block_supported(D);
+  return block_io_native(make_plan(layer_shape(B, N, D, F)), D) ? 1 : 0;
+}
 
+int smx_block_forward_io(const void* x, const float* ln_w, const float* ln_b, float eps, const float* w_re,
+                         const float* w_im, const float* bias, void* y, float* xk_save, float* ln_stats,
+                         void* workspace, size_t workspace_bytes, int B, int N, int D, int F, float dropout_p,
+                         const void* rng_state, float* filter_pack, void* stream, int io) {
+  if (int rc = io_check(io)) return rc;
+  return block_forward_impl((const float*)x, ln_w, ln_b, eps, w_re, w_im, bias, (float*)y, xk_save, ln_stats, workspace,
+                            workspace_bytes, B, N, D, F, dropout_p, rng_state, filter_pack, stream, io);
+}
+
+int smx_block_backward_io(const void* g, const void* x, const float* ln_stats, const float* ln_w, const float* xk,
+                          const float* w_re, const float* w_im, void* grad_x, float* g_ln_w, float* g_ln_b,
+                          float* gw_re, float* gw_im, float* gbias, float* grad_h, void* workspace,
+                          size_t workspace_bytes, int B, int N, int D, int F, int phases, float dropout_p,
+                          const void* rng_state, const float* filter_pack, void* stream, int io) {
+  if (int rc = io_check(io)) return rc;
+  if (io == SMX_IO_F32)
+    return smx_block_backward_dropout((const float*)g, (const float*)x, ln_stats, ln_w, xk, w_re, w_im, (float*)grad_x,
+                                      g_ln_w, g_ln_b, gw_re, gw_im, gbias, workspace, workspace_bytes, B, N, D, F,
+                                      phases, dropout_p, rng_state, filter_pack, stream);
+  if (int rc = check_shape(B, N, D, F)) return rc;
+  if (!ln_supported(D)) return fail(SMX_ERR_UNSUPPORTED, "LayerNorm width D=%d is not supported", D);
+  if ((phases & 7) < 1 || phases > 15) return fail(SMX_ERR_INVALID, "phases must be a combination of 1, 2, 4");
+  const Shape h = layer_shape(B, N, D, F);
+  if (!block_io_native(make_plan(h), D)) return fail(SMX_ERR_UNSUPPORTED, BLOCK_IO_PLANS);
+  if (!grad_h || ((uintptr_t)grad_h & 15))
+    return fail(SMX_ERR_INVALID, "grad_h, a (B, N, D) f32 scratch, must be non-NULL and 16-byte aligned");
+  if ((phases & SMX_PHASE_INVERSE) && (!x || !ln_stats || !grad_x))
+    return fail(SMX_ERR_INVALID, "x, ln_stats, grad_x must be non-NULL");
+  if (g == grad_x || x == grad_x) return fail(SMX_ERR_INVALID, "grad_x must not alias g or x");
+  if (((uintptr_t)x | (uintptr_t)g | (uintptr_t)grad_x) & 7)
+    return fail(SMX_ERR_INVALID, "2-byte x, g, grad_x (D %% 4 == 0) must be 8-byte aligned");
+  if ((uintptr_t)ln_w & 15) return fail(SMX_ERR_INVALID, "ln_w must be 16-byte aligned");
+
+  if (int rc = backward_impl(h, (const float*)g, xk, w_re, w_im, grad_h, gw_re, gw_im, gbias, workspace, workspace_bytes,
+                             phases, dropout_p, rng_state, filter_pack, stream, nullptr, nullptr, io, SMX_IO_F32))
+    return rc;
+  if (phases & SMX_PHASE_INVERSE) {
+    const Ws w = ws_layout(make_plan(h), B, N, D);
+    HIP_TRY(launch_ln_bwd_io(grad_h, x, g, grad_x, (const cf*)ln_stats, ln_w, (float*)((char*)workspace + w.lnp), g_ln_w,
+                             g_ln_b, (long long)B * N, D, (hipStream_t)stream, io));
+  }
+  return SMX_OK;
+}
+
+}  // extern "C"

@@ -7,6 +7,8 @@
 //                   statistics need all D channels, a workgroup of the transform owns 32;
 //   * k_ln_bwd      LayerNorm backward + residual: grad_x = g + LN'(grad_h), in place over grad_h, and
 //                   the per-block partial sums of grad_gamma / grad_beta;
+//                   (2-byte rows, IO != 0: grad_h stays f32 in a scratch of its own, x / g are read and grad_x is
+//                   written in the IO type -- not in place, the same arithmetic, one rounding at the store);
 //   * k_ln_colsum   fixed-order reduction of those partials (bitwise reproducible);
 //   * k_ln_apply, k_add_rows   unfused fallback used with the split / direct transform paths.
 // One wavefront per row, lane l holds elements (l + 64 c) VEC + [0, VEC), c < CH, in registers:
@@ -25,8 +27,9 @@ namespace {
 
 // stats[row] = (mean, 1/sqrt(var + eps)), biased variance, two passes over the registers
 // (torch.nn.LayerNorm, used by the reference at spectral_layers.py:162,185).
-template <int VEC, int CH>
-__global__ __launch_bounds__(64 * ROW_WAVES) void k_ln_stats(const float* __restrict__ x,
+// IO: element type of x (smx_rows.h io_elem); the statistics are f32 whatever it is.
+template <int VEC, int CH, int IO = 0>
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_ln_stats(const io_elem<IO>* __restrict__ x,
                                                              cf* __restrict__ stats, long long rows,
                                                              int D, float eps) {
   constexpr int R = CH <= 2 ? 2 : 1;          // rows in flight per wavefront (read-only kernel)
@@ -41,7 +44,7 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void k_ln_stats(const float* __rest
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
         const int e = (lane + 64 * c) * VEC;
-        if (e < D && row < rows) xv[q][c].load(x + (size_t)row * D + e);
+        if (e < D && row < rows) load_io<IO>(xv[q][c], x + (size_t)row * D + e);
         else
 #pragma unroll
           for (int i = 0; i < VEC; ++i) xv[q][c].v[i] = 0.f;
@@ -206,6 +209,100 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void k_ln_bwd(float* __restrict__ g
   }
 }
 
+// The same with 2-byte rows: grad_h is read from an f32 scratch of its own, x and g in the element type IO, and grad_x
+// is written in IO, rounded once -- not in place.  The arithmetic and its order are k_ln_bwd's, so grad_x is its
+// grad_x rounded and the partials are its partials.  A copy, not a shared body: with one, k_ln_bwd<4, .> compiled to
+// other machine code (tools/kdiff.py), as with every helper spelling before.
+template <int VEC, int CH, int IO>
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_ln_bwd_io(const float* __restrict__ gh,
+                                                              const io_elem<IO>* __restrict__ x,
+                                                              const io_elem<IO>* __restrict__ g,
+                                                              io_elem<IO>* __restrict__ dx,
+                                                              const cf* __restrict__ stats,
+                                                              const float* __restrict__ gamma,
+                                                              float* __restrict__ part, long long rows,
+                                                              int D) {
+  __shared__ float red[ROW_WAVES][2][64 * VEC];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float inv_d = 1.f / (float)D;
+  Vec<VEC> gm[CH], ag[CH], ab[CH];
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    const int e = (lane + 64 * c) * VEC;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) { gm[c].v[i] = 1.f; ag[c].v[i] = 0.f; ab[c].v[i] = 0.f; }
+    if (e < D && gamma) gm[c].load_cached(gamma + e);
+  }
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows;
+       row += (long long)gridDim.x * ROW_WAVES) {
+    const size_t o = (size_t)row * D;
+    Vec<VEC> hv[CH], xv[CH], gv[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int e = (lane + 64 * c) * VEC;
+      if (e < D) {
+        hv[c].load_cached(gh + o + e);
+        load_io<IO>(xv[c], x + o + e);
+        load_io<IO>(gv[c], g + o + e);
+      } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) { hv[c].v[i] = 0.f; xv[c].v[i] = 0.f; gv[c].v[i] = 0.f; }
+      }
+    }
+    const cf st = stats[row];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int e = (lane + 64 * c) * VEC;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        const float xh = e < D ? (xv[c].v[i] - st.x) * st.y : 0.f;
+        const float gmv = gm[c].v[i];           // read before hv: the operand order of gamma * grad_h
+        hv[c].v[i] = ln_bwd_acc(hv[c].v[i], xh, gmv, ag[c].v[i], ab[c].v[i], s1, s2);
+        xv[c].v[i] = xh;
+      }
+    }
+    const float m1 = wave_sum(s1) * inv_d, m2 = wave_sum(s2) * inv_d;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int e = (lane + 64 * c) * VEC;
+      if (e < D) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i)
+          gv[c].v[i] = fmaf(st.y, hv[c].v[i] - m1 - xv[c].v[i] * m2, gv[c].v[i]);
+        store_io<IO>(gv[c], dx + o + e);
+      }
+    }
+  }
+  // block partials: waves are added in index order
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      red[wv][0][lane * VEC + i] = ag[c].v[i];
+      red[wv][1][lane * VEC + i] = ab[c].v[i];
+    }
+    __syncthreads();
+    if (wv == 0) {
+      const int e = (lane + 64 * c) * VEC;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        if (e + i < D) {
+          float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+          for (int w2 = 0; w2 < ROW_WAVES; ++w2) {
+            a0 += red[w2][0][lane * VEC + i];
+            a1 += red[w2][1][lane * VEC + i];
+          }
+          part[((size_t)blockIdx.x * 2 + 0) * D + e + i] = a0;
+          part[((size_t)blockIdx.x * 2 + 1) * D + e + i] = a1;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // out[which][d] = sum_blk part[blk][which][d]; 16 channels x 64 block groups per workgroup, groups
 // added in index order (bitwise reproducible).  2 D/16 workgroups: 32 at D = 256.
 __global__ __launch_bounds__(1024) void k_ln_colsum(const float* __restrict__ part, int nblk, int D,
@@ -306,6 +403,23 @@ hipError_t launch_ln_stats(const float* x, cf* stats, long long rows, int D, flo
   return hipGetLastError();
 }
 
+// 2-byte rows: Vec<4> chunks only, 8 bytes per lane.  (D % 4 != 0 stays on the up-cast route: the f32 kernels walk such
+// a row one element per lane, and any wider 2-byte chunk would add the row sums in another order.)
+bool ln_io_supported(int D) { return D % 4 == 0 && ln_supported(D); }
+
+template <int IO>
+static void launch_ln_stats_t(const void* x, cf* stats, long long rows, int D, float eps, hipStream_t s) {
+  row_dispatch<4, 16>(D, [&](auto vec, auto ch) {
+    row_launch(k_ln_stats<decltype(vec)::value, decltype(ch)::value, IO>, rows, s, (const io_elem<IO>*)x, stats, rows,
+               D, eps);
+  });
+}
+hipError_t launch_ln_stats_io(const void* x, cf* stats, long long rows, int D, float eps, hipStream_t s, int io) {
+  if (!ln_io_supported(D) || (io != 1 && io != 2)) return hipErrorInvalidValue;
+  if (io == 1) launch_ln_stats_t<1>(x, stats, rows, D, eps, s); else launch_ln_stats_t<2>(x, stats, rows, D, eps, s);
+  return hipGetLastError();
+}
+
 hipError_t launch_ln_apply(const float* x, const cf* stats, const float* gamma, const float* beta,
                            float* h, long long rows, int D, hipStream_t s) {
   ln_dispatch(D, [&](auto vec, auto ch) {
@@ -336,6 +450,24 @@ hipError_t launch_ln_bwd(float* gh_dx, const float* x, const float* g, const cf*
     row_launch(k_ln_bwd<decltype(vec)::value, decltype(ch)::value>, rows, s, gh_dx, x, g, stats, gamma,
                part, rows, D);
   });
+  if (hipError_t e = hipGetLastError()) return e;
+  return launch_ln_colsum(part, ln_num_blocks(rows), D, g_gamma, g_beta, s);
+}
+
+template <int IO>
+static void launch_ln_bwd_t(const float* gh, const void* x, const void* g, void* dx, const cf* stats,
+                            const float* gamma, float* part, long long rows, int D, hipStream_t s) {
+  row_dispatch<4, 16>(D, [&](auto vec, auto ch) {
+    row_launch(k_ln_bwd_io<decltype(vec)::value, decltype(ch)::value, IO>, rows, s, gh, (const io_elem<IO>*)x,
+               (const io_elem<IO>*)g, (io_elem<IO>*)dx, stats, gamma, part, rows, D);
+  });
+}
+hipError_t launch_ln_bwd_io(const float* gh, const void* x, const void* g, void* dx, const cf* stats,
+                            const float* gamma, float* part, float* g_gamma, float* g_beta, long long rows, int D,
+                            hipStream_t s, int io) {
+  if (!ln_io_supported(D) || (io != 1 && io != 2)) return hipErrorInvalidValue;
+  if (io == 1) launch_ln_bwd_t<1>(gh, x, g, dx, stats, gamma, part, rows, D, s);
+  else launch_ln_bwd_t<2>(gh, x, g, dx, stats, gamma, part, rows, D, s);
   if (hipError_t e = hipGetLastError()) return e;
   return launch_ln_colsum(part, ln_num_blocks(rows), D, g_gamma, g_beta, s);
 }

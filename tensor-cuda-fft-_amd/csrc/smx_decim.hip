@@ -347,7 +347,9 @@ __device__ __forceinline__ void gradw_tail(const DecimArgs& a, cf* lds, int cb) 
 // the widened input, rounded once at the store.  IO != 0 never holds the folded
 // parameter-gradient reduction (no gradw_tail, no __builtin_trap, no extra registers: the half backward reduces in
 // k_gradw, bitwise the same sums), and only the configurations smx_api routes there are instantiated (launch_fused).
-template <int NB, int MODE, bool DROP = false, bool ACC = false, bool PAD = false, int IO = 0>
+// OIO: element type of a.out where it is not a.in's.  One pairing exists: 2-byte g in, f32 rows out (MODE 1), the
+// transform of the 2-byte block backward -- its output is grad_h, which the LayerNorm backward reads unrounded.
+template <int NB, int MODE, bool DROP = false, bool ACC = false, bool PAD = false, int IO = 0, int OIO = IO>
 __global__ __launch_bounds__(TPB, 2) void k_fused(const DecimArgs a) {
   SMX_LDS_DECL;
   const Geom& g = a.g;
@@ -403,9 +405,9 @@ __global__ __launch_bounds__(TPB, 2) void k_fused(const DecimArgs a) {
     return;
   }
   __syncthreads();
-  RowBufT<IO> yb;   // (ACC: also read back)
-  if constexpr (IO == 0) yb = row_buf(a.out + (size_t)b * g.R * g.D, g, t, d, valid);
-  else yb = row_buf<IO>(a.out, b, g, t, d, valid);
+  RowBufT<OIO> yb;   // (ACC: also read back)
+  if constexpr (OIO == 0) yb = row_buf(a.out + (size_t)b * g.R * g.D, g, t, d, valid);
+  else yb = row_buf<OIO>(a.out, b, g, t, d, valid);
   inverse_loop<NB, ACC, DROP && MODE == 0, PAD>(st, lds, yb, a, t, j, 0, g.L, rot, yb, dr, pj);
   if constexpr (NB == 1) store_io<NB, MODE>(st, g, a.fa, b, d, valid, t);     // saved spectrum / grad slab
   if constexpr (FOLD_GRADW) {
@@ -681,7 +683,9 @@ __global__ __launch_bounds__(TPB, 1) void k_synth8(const DecimArgs a) {
 // Same structure as k_fused<NB, 0>; x is read a second time at the store for the residual.
 // (four bands: 256 VGPRs are not enough for the extra row statistics and residual rows -- 57 spills
 // inside the loops cost more than the second workgroup per CU gains: 784 vs 688 us at (32,4096,1024))
-template <int NB, bool DROP = false>
+// IO: element type of x and y as in k_fused -- the LayerNorm-on-load rows, the residual re-read and the store; the
+// statistics, gamma / beta and the spectrum stay f32, so y is the f32 kernel's y on the widened x, rounded once.
+template <int NB, bool DROP = false, int IO = 0>
 __global__ __launch_bounds__(TPB, NB > 2 ? 1 : 2) void k_fused_blk(const DecimArgs a) {
   SMX_LDS_DECL;
   const Geom& g = a.g;
@@ -691,7 +695,9 @@ __global__ __launch_bounds__(TPB, NB > 2 ? 1 : 2) void k_fused_blk(const DecimAr
   const int b = w.b, d = w.dt * DT + 2 * j, rot = w.rot;
   const bool valid = d < g.D;
   const int dc = valid ? d : g.D - 2;
-  const RowBuf xb = row_buf(a.in + (size_t)b * g.R * g.D, g, t, dc);
+  RowBufT<IO> xb;
+  if constexpr (IO == 0) xb = row_buf(a.in + (size_t)b * g.R * g.D, g, t, dc);
+  else xb = row_buf<IO>(a.in, b, g, t, dc);
   LnLoad ln;
   ln.sb = a.ln_stats + (size_t)b * g.N;
   ln.g0 = a.ln_w ? a.ln_w[dc] : 1.f; ln.g1 = a.ln_w ? a.ln_w[dc + 1] : 1.f;
@@ -706,7 +712,9 @@ __global__ __launch_bounds__(TPB, NB > 2 ? 1 : 2) void k_fused_blk(const DecimAr
   forward_loop<NB, true>(st, lds, xb, a, t, j, 0, g.L, rot, &ln);
   unpack_filter<NB, 0, false>(st, lds, g, a.fa, b, d, valid, t, j, NB == 1 ? &wp : nullptr);
   __syncthreads();
-  const RowBuf yb = row_buf(a.out + (size_t)b * g.R * g.D, g, t, d, valid);
+  RowBufT<IO> yb;
+  if constexpr (IO == 0) yb = row_buf(a.out + (size_t)b * g.R * g.D, g, t, d, valid);
+  else yb = row_buf<IO>(a.out, b, g, t, d, valid);
   Drop dr{};
   if constexpr (DROP) dr = make_drop(a, b);
   inverse_loop<NB, true, DROP>(st, lds, yb, a, t, j, 0, g.L, rot, xb, dr, (unsigned)(dc >> 1));
@@ -898,17 +906,34 @@ static void launch_fused_nb(const DecimArgs& a, int nb, int mode, dim3 grid, hip
   else launch_fused_t<1, IO>(a, mode, grid, s);
 }
 
+// 2-byte g in, f32 rows out: mode 1 only (see k_fused, OIO)
+template <int IO>
+static void launch_fused_mixed(const DecimArgs& a, int nb, dim3 grid, hipStream_t s) {
+  const dim3 block(TPB);
+  if (a.drop_thr != 0) {
+    if (nb == 4) hipLaunchKernelGGL((k_fused<4, 1, true, false, false, IO, 0>), grid, block, 0, s, a);
+    else if (nb == 2) hipLaunchKernelGGL((k_fused<2, 1, true, false, false, IO, 0>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_fused<1, 1, true, false, false, IO, 0>), grid, block, 0, s, a);
+  } else if (nb == 4) hipLaunchKernelGGL((k_fused<4, 1, false, false, false, IO, 0>), grid, block, 0, s, a);
+  else if (nb == 2) hipLaunchKernelGGL((k_fused<2, 1, false, false, false, IO, 0>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((k_fused<1, 1, false, false, false, IO, 0>), grid, block, 0, s, a);
+}
+
 int gradw_tail_blocks(int D, int F, bool bias) {
   return ((D + DT - 1) / DT) * ((F + GWT_BINS - 1) / GWT_BINS + (bias ? 1 : 0));
 }
 
-hipError_t launch_fused(const DecimArgs& a, int nb, int mode, hipStream_t s, int io) {
+hipError_t launch_fused(const DecimArgs& a, int nb, int mode, hipStream_t s, int io, int oio) {
   if (!io_instance(a, io) || (io != 0 && ((mode != 0 && mode != 1) || a.n_cons > 0))) return hipErrorInvalidValue;
+  const bool mixed = oio >= 0 && oio != io;
+  if (mixed && (io == 0 || oio != 0 || mode != 1)) return hipErrorInvalidValue;
   const int total = n_wg(a);
   return for_rounds(a, total, [&](const DecimArgs& r, dim3 grid) {
     // the reduction workgroups ride behind the LAST round's transform workgroups
     if (r.n_cons > 0 && r.bid0 + (int)grid.x >= total) grid.x += r.n_cons;
     if (r.accumulate && r.out != nullptr) launch_fused_acc(r, mode, grid, s);
+    else if (mixed && io == 1) launch_fused_mixed<1>(r, nb, grid, s);
+    else if (mixed) launch_fused_mixed<2>(r, nb, grid, s);
     else if (io == 1) launch_fused_nb<1>(r, nb, mode, grid, s);
     else if (io == 2) launch_fused_nb<2>(r, nb, mode, grid, s);
     else launch_fused_nb<0>(r, nb, mode, grid, s);
@@ -1001,16 +1026,23 @@ hipError_t launch_full8(const DecimArgs& a, int mode, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_fused_block(const DecimArgs& a, int nb, hipStream_t s) {
+template <int IO>
+static void launch_fused_block_t(const DecimArgs& r, int nb, dim3 grid, hipStream_t s) {
+  const dim3 block(TPB);
+  if (r.drop_thr != 0) {
+    if (nb == 4) hipLaunchKernelGGL((k_fused_blk<4, true, IO>), grid, block, 0, s, r);
+    else if (nb == 2) hipLaunchKernelGGL((k_fused_blk<2, true, IO>), grid, block, 0, s, r);
+    else hipLaunchKernelGGL((k_fused_blk<1, true, IO>), grid, block, 0, s, r);
+  } else if (nb == 4) hipLaunchKernelGGL((k_fused_blk<4, false, IO>), grid, block, 0, s, r);
+  else if (nb == 2) hipLaunchKernelGGL((k_fused_blk<2, false, IO>), grid, block, 0, s, r);
+  else hipLaunchKernelGGL((k_fused_blk<1, false, IO>), grid, block, 0, s, r);
+}
+hipError_t launch_fused_block(const DecimArgs& a, int nb, hipStream_t s, int io) {
+  if (!io_instance(a, io)) return hipErrorInvalidValue;
   return for_rounds(a, n_wg(a), [&](const DecimArgs& r, dim3 grid) {
-    const dim3 block(TPB);
-    if (r.drop_thr != 0) {
-      if (nb == 4) hipLaunchKernelGGL((k_fused_blk<4, true>), grid, block, 0, s, r);
-      else if (nb == 2) hipLaunchKernelGGL((k_fused_blk<2, true>), grid, block, 0, s, r);
-      else hipLaunchKernelGGL((k_fused_blk<1, true>), grid, block, 0, s, r);
-    } else if (nb == 4) hipLaunchKernelGGL((k_fused_blk<4>), grid, block, 0, s, r);
-    else if (nb == 2) hipLaunchKernelGGL((k_fused_blk<2>), grid, block, 0, s, r);
-    else hipLaunchKernelGGL((k_fused_blk<1>), grid, block, 0, s, r);
+    if (io == 1) launch_fused_block_t<1>(r, nb, grid, s);
+    else if (io == 2) launch_fused_block_t<2>(r, nb, grid, s);
+    else launch_fused_block_t<0>(r, nb, grid, s);
   }, nb == 4);
 }
 

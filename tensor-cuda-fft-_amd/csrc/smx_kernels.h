@@ -70,7 +70,9 @@ hipError_t launch_split16_b(const DecimArgs& a, int nb, bool drop_out, hipStream
 // io (here and in launch_split_a / launch_split_b): element type of the rows a.in / a.out point at (SMX_IO_*: 0 f32,
 // 1 bf16, 2 fp16 -- 2-byte rows, everything else f32).  io != 0 exists for modes 0 and 1 without zero-padded rows,
 // band groups (accumulate) or the folded parameter-gradient reduction (n_cons); anything else: hipErrorInvalidValue
-hipError_t launch_fused(const DecimArgs& a, int nb, int mode, hipStream_t s, int io = 0);
+// oio: element type of a.out where it differs from a.in's (-1 = io).  Only (io 2-byte, oio f32, mode 1) exists: the
+// block backward, whose grad_h stays f32 for the LayerNorm backward behind it
+hipError_t launch_fused(const DecimArgs& a, int nb, int mode, hipStream_t s, int io = 0, int oio = -1);
 // synthesis from a given one-sided spectrum (fa.xk_in, fa.sp_scale, fa.sp_herm): fused inverse, or the packed
 // spectrum parked for launch_split_b when out == NULL
 hipError_t launch_synth(const DecimArgs& a, int nb, hipStream_t s);
@@ -113,7 +115,7 @@ hipError_t launch_phase_filter(const float* m, const float* ph, int D, int k, in
 hipError_t launch_phase_filter_bwd(const float* m, const float* ph, const float* gw_re, const float* gw_im, int D, int k,
                                    int n_fft, int ld, float* g_m, float* g_p, hipStream_t s);
 // forward of y = x + mix(LayerNorm(x)) in one launch (nsplit == 1 only)
-hipError_t launch_fused_block(const DecimArgs& a, int nb, hipStream_t s);
+hipError_t launch_fused_block(const DecimArgs& a, int nb, hipStream_t s, int io = 0);
 // three-launch path: partial forward / combine+filter / inverse
 hipError_t launch_split_a(const DecimArgs& a, int nb, bool drop_in, hipStream_t s, int io = 0);
 hipError_t launch_split_f(const DecimArgs& a, int nb, int mode, hipStream_t s);
@@ -233,6 +235,12 @@ hipError_t launch_ln_bwd(float* gh_dx, const float* x, const float* g, const cf*
                          const float* gamma, float* part, float* g_gamma, float* g_beta,
                          long long rows, int D, hipStream_t s);
 // g_gamma[d] = sum_blk part[blk][0][d], g_beta[d] = sum_blk part[blk][1][d] (fixed order; either may be null)
+// 2-byte rows (io = SMX_IO_BF16 / SMX_IO_F16; D % 4 == 0): x, g, dx in the io type, gh (B, N, D) f32 read-only, dx != gh
+bool ln_io_supported(int D);
+hipError_t launch_ln_stats_io(const void* x, cf* stats, long long rows, int D, float eps, hipStream_t s, int io);
+hipError_t launch_ln_bwd_io(const float* gh, const void* x, const void* g, void* dx, const cf* stats,
+                            const float* gamma, float* part, float* g_gamma, float* g_beta, long long rows, int D,
+                            hipStream_t s, int io);
 hipError_t launch_ln_colsum(const float* part, int nblk, int D, float* g_gamma, float* g_beta, hipStream_t s);
 
 // ---- row kernels of EnhancedSpectralBlock (smx_enh.hip) --------------------------------------------

@@ -184,6 +184,8 @@ __device__ __forceinline__ void store_rows(const RowBufT<IO>& rb, int r, const c
 // host pass of hipcc: the kernels' bodies are parsed but never emitted -- declarations only
 template <int IO> struct RowBufT { unsigned vo, su, rowb; };
 using RowBuf = RowBufT<0>;
+template <int IO> __device__ cf widen2(unsigned w);
+template <int IO> __device__ unsigned narrow2(float fx, float fy);
 template <int IO = 0>
 __device__ RowBufT<IO> row_buf(const void* row0, const Geom& g, int t, int d, bool in_range = true);
 template <int IO>

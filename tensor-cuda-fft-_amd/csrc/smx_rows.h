@@ -4,12 +4,17 @@
 // Vec<VEC>[CH] rows (load, store, LayerNorm statistics, the LayerNorm-backward step, the block partials of the parameter
 // gradients), the dropout factors, and the host side: the (VEC, CH) dispatch on the row width and the launch of the
 // kernels that walk rows ROW_WAVES at a time.
+// 2-byte rows (IO = SMX_IO_BF16 / SMX_IO_F16): load_io / store_io move a chunk as 8 bytes per lane, widened
+// exactly on load and rounded once at the store by widen2 / narrow2 of smx_launch.h -- the conversions of the
+// streaming kernels, the fp16 guard against a multiply fused into the conversion included.  IO = 0 is load / store.
 #pragma once
 #include <type_traits>
 
-#include "smx_kernels.h"
+#include "smx_launch.h"
 
 namespace smx {
+
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));      // (as smx_launch.h's, which only the device pass sees)
 
 namespace {
 
@@ -29,6 +34,9 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += dpp_f<0x143, 0xc, false>(v);     // row_bcast:31 into rows 2 and 3 -> lane 63 holds the total
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+
+// element of a row in memory: float, or the 16 bits of a bf16 / fp16
+template <int IO> using io_elem = std::conditional_t<IO == 0, float, unsigned short>;
 
 template <int VEC> struct Vec;
 template <> struct Vec<4> {
@@ -69,6 +77,31 @@ template <> struct Vec<2> {
     __builtin_nontemporal_store(w, reinterpret_cast<f32x2*>(p));
   }
 };
+
+// A chunk in the element type IO.  2-byte chunks exist for Vec<4> (8 bytes per lane); IO = 0 is load / store itself.
+template <int IO, int VEC>
+__device__ __forceinline__ void load_io(Vec<VEC>& r, const io_elem<IO>* p) {
+  if constexpr (IO == 0) {
+    r.load(p);
+  } else {
+    static_assert(VEC == 4, "2-byte rows move as Vec<4> chunks");
+    const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+    const unsigned w0 = w.x, w1 = w.y;      // (see load_rows, smx_launch.h)
+    const cf a = widen2<IO>(w0), b = widen2<IO>(w1);
+    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = b.x; r.v[3] = b.y;
+  }
+}
+template <int IO, int VEC>
+__device__ __forceinline__ void store_io(const Vec<VEC>& r, io_elem<IO>* p) {
+  if constexpr (IO == 0) {
+    r.store(p);
+  } else {
+    static_assert(VEC == 4, "2-byte rows move as Vec<4> chunks");
+    u32x2 w;
+    w.x = narrow2<IO>(r.v[0], r.v[1]); w.y = narrow2<IO>(r.v[2], r.v[3]);
+    __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(p));
+  }
+}
 
 template <int VEC, int CH>
 __device__ __forceinline__ void zero(Vec<VEC> (&r)[CH]) {

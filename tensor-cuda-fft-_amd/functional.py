@@ -487,8 +487,10 @@ def _spectral_mix_half(x, w_re, w_im, bias, sync, dropout_p, drop_state):
 
 
 def block_forward_raw(x, ln_w, ln_b, eps, w_re, w_im, bias, *, save=True, dropout_p=0.0, rng=None,
-                      pack=None, ws=None):
-    """y, xk, stats = smx_block_forward(...): y = x + mix(LayerNorm(x)); stats (B,N,2) = (mean, rstd)."""
+                      pack=None, ws=None, io=0):
+    """y, xk, stats = smx_block_forward(...): y = x + mix(LayerNorm(x)); stats (B,N,2) = (mean, rstd).
+    io: element type of x and y (SMX_IO_BF16 / SMX_IO_F16: bf16 / fp16 x, 8-byte aligned, on a shape with
+    _lib.block_io_supported; y comes back in x's dtype, xk and stats stay fp32)."""
     B, N, D = x.shape
     F = w_re.shape[1]
     k = num_bins(N, F)
@@ -499,18 +501,24 @@ def block_forward_raw(x, ln_w, ln_b, eps, w_re, w_im, bias, *, save=True, dropou
     if ws is None:
         ws = _workspace(x.device, _ws_bytes(B, N, D, F))
     with _on_device(x.device):
-        _lib.check(_lib.lib().smx_block_forward_dropout(
-            x.data_ptr(), _ptr(ln_w), _ptr(ln_b), float(eps), w_re.data_ptr(), w_im.data_ptr(),
-            _ptr(bias), y.data_ptr(), _ptr(xk), stats.data_ptr(), _ptr(ws),
-            0 if ws is None else ws.numel(), B, N, D, F, float(dropout_p), _ptr(rng), _ptr(pack),
-            _stream(x.device)))
+        args = (x.data_ptr(), _ptr(ln_w), _ptr(ln_b), float(eps), w_re.data_ptr(), w_im.data_ptr(),
+                _ptr(bias), y.data_ptr(), _ptr(xk), stats.data_ptr(), _ptr(ws),
+                0 if ws is None else ws.numel(), B, N, D, F, float(dropout_p), _ptr(rng), _ptr(pack),
+                _stream(x.device))
+        # (as forward_raw: 2-byte rows through the _io entry, f32 through the f32 entry)
+        _lib.check(_lib.lib().smx_block_forward_io(*args, int(io)) if io
+                   else _lib.lib().smx_block_forward_dropout(*args))
     return y, xk, stats
 
 
 def block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, *, phases=PHASE_ALL, grad_x=None,
-                       flat=None, ln_flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, sync_clean=False):
+                       flat=None, ln_flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, sync_clean=False,
+                       io=0, grad_h=None):
     """Runs smx_block_backward.  Returns (grad_x, flat, ln_flat): flat = [gw_re | gw_im | gbias],
-    ln_flat = [g_ln_w | g_ln_b]."""
+    ln_flat = [g_ln_w | g_ln_b].
+    io: element type of g, x and grad_x, as in block_forward_raw (every parameter gradient stays fp32).  A 2-byte io
+    needs grad_h, a (B, N, D) fp32 scratch -- the same one for every phase of a phase-split backward; without one it
+    comes from torch's allocator for this call."""
     B, N, D = g.shape
     F = w_re.shape[1]
     if grad_x is None:
@@ -519,18 +527,21 @@ def block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, *, phases=PHASE_ALL, g
         flat = torch.empty(2 * D * F + D, dtype=torch.float32, device=g.device)
     if ln_flat is None:
         ln_flat = torch.empty(2 * D, dtype=torch.float32, device=g.device)
+    if io and grad_h is None:
+        grad_h = torch.empty((B, N, D), dtype=torch.float32, device=g.device)
     if ws is None:
         ws = _workspace(g.device, _ws_bytes(B, N, D, F))
     if sync_clean:
         phases |= PHASE_SYNC_CLEAN
     _prepare(g.device, N)
     with _on_device(g.device):
-        _lib.check(_lib.lib().smx_block_backward_dropout(
-            g.data_ptr(), x.data_ptr(), stats.data_ptr(), _ptr(ln_w), _ptr(xk), w_re.data_ptr(),
-            w_im.data_ptr(), grad_x.data_ptr(), ln_flat[:D].data_ptr(), ln_flat[D:].data_ptr(),
-            flat[:D * F].data_ptr(), flat[D * F:2 * D * F].data_ptr(), flat[2 * D * F:].data_ptr(),
-            _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F, phases, float(dropout_p),
-            _ptr(rng), _ptr(pack), _stream(g.device)))
+        head = (g.data_ptr(), x.data_ptr(), stats.data_ptr(), _ptr(ln_w), _ptr(xk), w_re.data_ptr(),
+                w_im.data_ptr(), grad_x.data_ptr(), ln_flat[:D].data_ptr(), ln_flat[D:].data_ptr(),
+                flat[:D * F].data_ptr(), flat[D * F:2 * D * F].data_ptr(), flat[2 * D * F:].data_ptr())
+        tail = (_ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F, phases, float(dropout_p),
+                _ptr(rng), _ptr(pack), _stream(g.device))
+        _lib.check(_lib.lib().smx_block_backward_io(*head, grad_h.data_ptr(), *tail, int(io)) if io
+                   else _lib.lib().smx_block_backward_dropout(*head, *tail))
     return grad_x, flat, ln_flat
 
 
@@ -548,8 +559,11 @@ class _SpectralBlockMix(torch.autograd.Function):
         pack = _new_pack(x, w_re) if needs else None
         B, N, D = x.shape
         ws = _workspace(x.device, _ws_bytes(B, N, D, w_re.shape[1]))     # shared with backward, see _SpectralMix
+        io = _IO[x.dtype]                                    # bf16 / fp16 x: shapes with native 2-byte block rows only
         y, xk, stats = block_forward_raw(x, ln_w, ln_b, eps, w_re, w_im, bias, save=needs,
-                                         dropout_p=dropout_p, rng=rng, pack=pack, ws=ws)
+                                         dropout_p=dropout_p, rng=rng, pack=pack, ws=ws, io=io)
+        ctx.io = io
+        ctx.io_dtype = x.dtype
         ctx.ws = ws if needs else None
         ctx.sync = sync
         ctx.drop = (dropout_p, rng)
@@ -568,12 +582,14 @@ class _SpectralBlockMix(torch.autograd.Function):
         has_w, has_b, has_bias = ctx.flags
         if not has_w:
             ln_w = None
-        if g.dtype != torch.float32:
-            g = g.float()
+        if g.dtype != ctx.io_dtype:
+            g = g.to(ctx.io_dtype)
         g = _dense(g)
         D, F = w_re.shape
         sync = ctx.sync if (ctx.sync is not None and ctx.sync.active()) else None
-        dkw = dict(dropout_p=ctx.drop[0], rng=ctx.drop[1], pack=ctx.pack)
+        dkw = dict(dropout_p=ctx.drop[0], rng=ctx.drop[1], pack=ctx.pack, io=ctx.io)
+        if ctx.io and sync is not None:                      # one fp32 grad_h for every phase
+            dkw["grad_h"] = torch.empty(g.shape, dtype=torch.float32, device=g.device)
         if sync is None:
             gx, flat, lnf = block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, ws=ctx.ws,
                                                sync_clean=ctx.ws is not None, **dkw)
@@ -599,6 +615,9 @@ class _SpectralBlockMix(torch.autograd.Function):
                 flat[2 * D * F:2 * D * F + D] if has_bias else None, None, None, None, None)
 
 
+_block_io_cache = _Memo()
+
+
 def block_supported(D: int) -> bool:
     return bool(_lib.lib().smx_block_supported(int(D)))
 
@@ -609,12 +628,36 @@ def spectral_block_mix(x: torch.Tensor, ln_weight: Optional[torch.Tensor],
                        sync=None, dropout_p: float = 0.0,
                        drop_state: Optional[DropoutState] = None) -> torch.Tensor:
     """x + dropout(spectral_mix(layer_norm(x, (D,), ln_weight, ln_bias, eps), weight_real, weight_imag,
-    bias), dropout_p)."""
-    _require_gpu_f32("x", x)
-    for name, t in (("ln_weight", ln_weight), ("ln_bias", ln_bias), ("weight_real", weight_real),
-                    ("weight_imag", weight_imag), ("bias", bias)):
-        if t is not None:
-            _require_gpu_f32(name, t)
+    bias), dropout_p).
+
+    x may be fp32, bf16 or fp16; y and grad_x come back in x's dtype.  The parameters are fp32 or x's dtype and are read
+    as fp32 (`.float()`, so autograd returns their gradients in their own dtype).  All arithmetic is fp32: the result is
+    the fp32 op's on x.float(), rounded once to x's dtype -- by the kernels' stores where the shape has native 2-byte
+    block rows (_lib.block_io_supported), by `.to(dtype)` after the fp32 op everywhere else."""
+    _require_gpu_io("x", x)
+    params = (("ln_weight", ln_weight), ("ln_bias", ln_bias), ("weight_real", weight_real),
+              ("weight_imag", weight_imag), ("bias", bias))
+    if x.dtype != torch.float32:
+        for name, t in params:
+            if t is not None:
+                _require_gpu_io(name, t)
+                if t.dtype not in (torch.float32, x.dtype):
+                    raise TypeError(f"{name} must be float32 or {x.dtype} like x, got {t.dtype}")
+        ln_weight, ln_bias, weight_real, weight_imag, bias = (None if t is None else t.float() for _, t in params)
+        if x.dim() == 3 and weight_real.dim() == 2 and x.numel() > 0:
+            B, N, D = x.shape
+            F = weight_real.shape[1]
+            native = _block_io_cache.get((B, N, D, F, x.dtype),
+                                         lambda: _lib.block_io_supported(B, N, D, F, _IO[x.dtype]))
+        else:
+            native = False                                   # (the fp32 call below raises what there is to raise)
+        if not native:
+            return spectral_block_mix(x.float(), ln_weight, ln_bias, eps, weight_real, weight_imag, bias, sync,
+                                      dropout_p, drop_state).to(x.dtype)
+    else:
+        for name, t in params:
+            if t is not None:
+                _require_gpu_f32(name, t)
     if x.dim() != 3:
         raise ValueError(f"expected x of shape (B, T, D), got {tuple(x.shape)}")
     D = x.shape[2]

@@ -16,7 +16,9 @@ Documented deviations from the reference:
   * training-mode dropout (p > 0) is drawn inside the transform's launches from the library's
     counter-based generator (keyed per call from torch's device generator): same distribution and
     scaling as nn.Dropout, different random bits, p quantised to 1/65536.  `layer.fuse_dropout = False` puts
-    nn.Dropout back as a separate pass.
+    nn.Dropout back as a separate pass;
+  * a bf16 / fp16 `SpectralMLPBlock` returns the once-rounded fp32 result of its first line, not the thrice-rounded
+    composition of three half-precision ops (see the class; `fuse_norm=False` keeps the composition).
 """
 from __future__ import annotations
 
@@ -107,7 +109,13 @@ class SpectralMLPBlock(nn.Module):
     (LayerNorm inside the transform's load, dropout and residual inside its store, smx_block_forward);
     norm2 and the MLP stay on torch/hipBLASLt.  Attribute
     names match the reference so `spectral_mix.weight_real`, `norm1.weight` etc. load from
-    reference checkpoints.  `fuse_norm=False` keeps the three ops separate."""
+    reference checkpoints.  `fuse_norm=False` keeps the three ops separate.
+
+    A bf16 / fp16 block takes the fused op as well (functional.spectral_block_mix): the first line is computed in fp32
+    from the 2-byte x and rounded ONCE -- bit for bit the fp32 module holding the same (rounded) weights, cast to the
+    dtype -- where the composition rounds the activation three times (after norm1, after the mix, after the add).  That
+    is a visible change of a half-precision block's output, towards the fp32 result; `fuse_norm=False` keeps the
+    composition.  No fp32 result changes."""
 
     def __init__(self, embed_dim: int, mlp_ratio: int = 4, dropout: float = 0.1):
         super().__init__()
@@ -124,7 +132,8 @@ class SpectralMLPBlock(nn.Module):
         sm = self.spectral_mix
         active = self.training and sm.dropout.p > 0.0          # a dropout the native op cannot take over
         return (self.fuse_norm and sm.learnable and x.dim() == 3 and x.shape[-1] == sm.embed_dim
-                and x.is_cuda and x.dtype == torch.float32 and not sm._eight_band_split(x.shape[0], x.shape[1])
+                and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16, torch.float16)
+                and not sm._eight_band_split(x.shape[0], x.shape[1])
                 and not (active and sm._fused_dropout_p() == 0.0)
                 and block_supported(sm.embed_dim))
 
