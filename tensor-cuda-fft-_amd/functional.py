@@ -672,9 +672,12 @@ def spectral_block_mix(x: torch.Tensor, ln_weight: Optional[torch.Tensor],
     if dropout_p > 0.0 and drop_state is None:
         raise ValueError("dropout_p > 0 needs a DropoutState")
     N = x.shape[1]
-    if x.numel() >= _ODD_D_PAD_MIN and ((D % 2 == 1 and N % 8 == 0) or (D % 2 == 0 and N % 16 == 8)):
-        # shapes that only stream through spectral_mix's own routes (one zero channel more; the even bins of twice
-        # the length): the block line as the composition it is -- the native block call would run DFT products
+    if not block_supported(D) or (x.numel() >= _ODD_D_PAD_MIN and
+                                  ((D % 2 == 1 and N % 8 == 0) or (D % 2 == 0 and N % 16 == 8))):
+        # rows wider than a wavefront's registers hold (no LayerNorm row kernel takes them), and shapes that only
+        # stream through spectral_mix's own routes (one zero channel more; the even bins of twice the length): the
+        # block line as the composition it is -- the native block call would refuse the one and run DFT products
+        # for the other
         h = torch.nn.functional.layer_norm(x, (D,), ln_weight, ln_bias, eps)
         return x + spectral_mix(h, weight_real, weight_imag, bias, sync, dropout_p, drop_state)
     return _SpectralBlockMix.apply(_dense(x), _dense(ln_weight), _dense(ln_bias), float(eps),

@@ -138,6 +138,7 @@ def test_block_entry_points_validate_without_touching_the_gpu(L):
     err = lambda: lib.smx_last_error().decode()
     assert [lib.smx_block_supported(d) for d in (1, 256, 4096, 4100, 8192, 1023, 1025)] == \
         [1, 1, 1, 0, 0, 1, 0]
+    assert [lib.smx_block_supported(d) for d in (1022, 1026)] == [1, 0]        # the widest scalar row (D % 4 != 0)
     n = lambda k: [None] * k
     assert lib.smx_block_forward(*n(3), 1e-5, *n(6), None, 0, 1, 256, 8192, 4, None) == -2
     assert "LayerNorm width" in err()

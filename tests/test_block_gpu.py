@@ -80,11 +80,24 @@ SHAPES = [  # (B, N, D, F, offset)
     (2, 300, 24, 12, 0.0),          # direct plan
     (5, 512, 6, 3, 10.0),           # scalar rows (D % 4 != 0), mean >> std
     (64, 256, 32, 16, 0.0),
+    # every (VEC, CH) instance of ln_dispatch the shapes above leave out, each at a width that fills it (or nearly) and
+    # at one a single chunk past the instance below, where the last chunk is almost all padding lanes
+    (2, 256, 2048, 16, 0.0),        # <4, 8> full
+    (2, 256, 1028, 16, 2.0),        # <4, 8>, one chunk past <4, 4>
+    (2, 256, 4096, 16, -3.0),       # <4, 16> full: the widest row
+    (2, 256, 2052, 16, 0.0),        # <4, 16>, one chunk past <4, 8>
+    (2, 256, 70, 16, 0.5),          # <1, 4> (D % 4 != 0), just past <1, 1>
+    (2, 256, 254, 16, 10.0),        # <1, 4> nearly full, mean >> std
+    (2, 256, 258, 16, 0.0),         # <1, 16>, two elements past <1, 4>
+    (2, 256, 1022, 16, -3.0),       # <1, 16> nearly full
+    # more than LN_MAX_BLOCKS * ROW_WAVES = 8192 rows and no multiple of it: the last pass of the row walk is ragged
+    (33, 256, 8, 4, 0.0),           # 8448 rows: the first 256 waves take a second row
+    (79, 256, 12, 6, 2.0),          # 20224 rows: two or three rows per wave
+    (40, 208, 8, 4, 0.5),           # 8320 rows on the sixteen-row plan (N = 16 * 13)
 ]
 
 
-@pytest.mark.parametrize("B,N,D,F,offset", SHAPES)
-def test_random_half_block_vs_oracle(gpu, B, N, D, F, offset):
+def _check_random_half_block(gpu, B, N, D, F, offset):
     _, _, fn = _mods()
     gen = torch.Generator().manual_seed(B * 1000 + N + D)
     r = lambda *s: torch.randn(*s, generator=gen)
@@ -97,6 +110,37 @@ def test_random_half_block_vs_oracle(gpu, B, N, D, F, offset):
     zz["eps"] = 1e-5
     zz.update({k: v.numpy() for k, v in zip(KEYS, ref)})
     _check(_run_half(fn, zz, gpu), zz)
+
+
+@pytest.mark.parametrize("B,N,D,F,offset", SHAPES)
+def test_random_half_block_vs_oracle(gpu, B, N, D, F, offset):
+    _, _, fn = _mods()
+    assert fn.block_supported(D)
+    _check_random_half_block(gpu, B, N, D, F, offset)
+
+
+@pytest.mark.parametrize("B,N,D,F,offset", [(2, 256, 2048, 16, 0.0), (2, 256, 4096, 16, -3.0), (2, 256, 2052, 16, 0.0),
+                                            (2, 256, 254, 16, 10.0), (2, 256, 1022, 16, -3.0), (33, 256, 8, 4, 0.0)])
+def test_random_half_block_vs_oracle_on_the_direct_plan(gpu, B, N, D, F, offset):
+    """The same under force_direct, where the LayerNorm is a pass of its own (k_ln_apply, then k_add_rows): its <4, 8>,
+    <4, 16>, <1, 4> and <1, 16> instances and its ragged second pass over 8448 rows."""
+    _, lib, _ = _mods()
+    lib.set_option("force_direct", 1)
+    try:
+        assert lib.plan(B, N, D, F).path == lib.SMX_PATH_DIRECT
+        _check_random_half_block(gpu, B, N, D, F, offset)
+    finally:
+        lib.set_option("force_direct", 0)
+
+
+@pytest.mark.parametrize("B,N,D,F,offset", [(2, 256, 4100, 16, 0.0), (2, 256, 1026, 16, 2.0)])
+def test_rows_past_the_kernel_limits_take_the_composition_route(gpu, B, N, D, F, offset):
+    """One chunk past the widest Vec<4> row and one pair past the widest scalar row: no LayerNorm row kernel holds such
+    a row (block_supported is false), and spectral_block_mix gives the oracle's numbers as
+    x + spectral_mix(layer_norm(x))."""
+    _, _, fn = _mods()
+    assert not fn.block_supported(D)
+    _check_random_half_block(gpu, B, N, D, F, offset)
 
 
 def test_block_module_uses_fused_op_and_matches_unfused(gpu):

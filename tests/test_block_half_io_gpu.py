@@ -114,6 +114,12 @@ NATIVE = [  # (B, N, D, F, offset), bands
     ((4, 256, 1024, 64, -3.0), 1),
     ((32, 1024, 128, 300, 10.0), 4),
     ((3, 768, 40, 20, 0.5), 1),           # ragged d-tile
+    # the eight- and sixteen-chunk instances of k_ln_stats / k_ln_bwd_io (tests/test_block_gpu.py ties the fp32 path to
+    # the oracle at the same widths).  B = 1 is the smallest batch with the single-launch plan at each of them.
+    ((1, 256, 1028, 16, 2.0), 1),         # <4, 8>, one chunk past <4, 4>: the last chunk is nearly all padding
+    ((1, 512, 2048, 16, 0.0), 1),         # <4, 8> full
+    ((1, 256, 4096, 16, -3.0), 1),        # <4, 16> full: the widest row
+    ((33, 256, 8, 4, 0.5), 1),            # 8448 rows: a ragged second pass of the row walk
 ]
 UPCAST = [  # (B, N, D, F, offset), why
     ((8, 4096, 128, 128, 0.0), "split"),

@@ -125,7 +125,9 @@ def test_eval_mode_and_p0_are_untouched_and_fuse_flag(gpu):
     assert not torch.equal(layer(x), ya)
 
 
-@pytest.mark.parametrize("B,N,D,F", [(4, 1024, 64, 32), (2, 4096, 8, 600), (2, 8704, 8, 600)])   # one launch; > 512 bins: four-step, band groups
+@pytest.mark.parametrize("B,N,D,F", [(4, 1024, 64, 32), (2, 4096, 8, 600), (2, 8704, 8, 600),   # one launch; > 512 bins: four-step, band groups
+                                     (33, 256, 8, 4),        # 8448 rows: the LayerNorm kernels walk a ragged second pass
+                                     (2, 256, 2048, 16)])    # eight Vec<4> chunks per row
 def test_block_training_path_is_fused_and_consistent(gpu, B, N, D, F):
     """SpectralMLPBlock(dropout=0.1).train(): the first residual line still runs as one native op;
     y - x is the dropped-out mix, and backward matches the eval composition fed with the same mask."""

@@ -107,12 +107,12 @@ def _randomized_block(pkg, D, gpu, seed=0):
     return blk.to(gpu).eval()
 
 
-@pytest.mark.parametrize("B,T_,D", [(4, 512, 256), (8, 1024, 256), (2, 256, 1024)])
-def test_fused_block_vs_float64_composition(gpu, B, T_, D):
+def _check_block_vs_float64(gpu, B, T_, D, fusable):
     import copy
     pkg, _ = _pkg()
     blk = _randomized_block(pkg, D, gpu)
     x = torch.randn(B, T_, D, device=gpu)
+    assert blk._fusable(x) == fusable
     g = torch.randn(B, T_, D, device=gpu)
     xx = x.clone().requires_grad_(True)
     y = blk(xx)
@@ -128,6 +128,21 @@ def test_fused_block_vs_float64_composition(gpu, B, T_, D):
     p64 = dict(b64.named_parameters())
     for name, p in blk.named_parameters():
         assert rel_err(c(p.grad), c(p64[name].grad)) <= TOL_PARAM, name
+
+
+@pytest.mark.parametrize("B,T_,D", [(4, 512, 256), (8, 1024, 256), (2, 256, 1024)])
+def test_fused_block_vs_float64_composition(gpu, B, T_, D):
+    _check_block_vs_float64(gpu, B, T_, D, True)
+
+
+def test_block_past_the_row_width_limit_vs_float64_composition(gpu):
+    """D = 1026 is one pair past ENH_MAX_D: enh_supported is false, the block runs the reference's op sequence around the
+    native transforms, and the numbers are still the float64 composition's.  (The other side of enh_supported, an odd
+    D such as 7, has no block to check: RotaryFrequencyEmbedding pairs the channels, so the reference and this package
+    both refuse an odd D before anything runs.)"""
+    _, fn = _pkg()
+    assert not fn.enh_supported(1026) and not fn.enh_supported(7)
+    _check_block_vs_float64(gpu, 2, 64, 1026, False)
 
 
 def test_misaligned_view_input(gpu):
@@ -179,9 +194,32 @@ def _compare(got, ref):
 
 
 LINE_SHAPES = [(3, 40, 6), (2, 100, 16), (4, 128, 256), (2, 64, 1024), (2, 33, 1022)]
+# One width per (VEC, CH) instance of enh_dispatch that LINE_SHAPES leaves out, the power-of-two widths 128 and 512, and the widths
+# one chunk past a ladder boundary, whose last chunk is nearly all padding lanes ("Which test
+# reaches which row-kernel instance").  74 and 111 rows: the last block of four waves is ragged.
+WIDTH_SHAPES = [(2, 37, 128),    # <4, 1>, lanes 0-31 only (the full tile of <2, 1>, which D % 4 == 0 never takes)
+                (2, 37, 130),    # <2, 2>, one pair past <2, 1>
+                (3, 37, 258),    # <2, 4>, one pair past <2, 2>
+                (2, 37, 260),    # <4, 2>, one chunk past <4, 1>
+                (2, 37, 384),    # <4, 2>
+                (3, 37, 510),    # <2, 4>, one pair short of full
+                (2, 37, 512),    # <4, 2> full
+                (2, 37, 514),    # <2, 8>, one pair past <2, 4>
+                (3, 37, 516)]    # <4, 4>, one chunk past <4, 2>
+# More than LN_MAX_BLOCKS * ROW_WAVES = 8192 rows, so a wave walks several rows (accumulating the parameter gradients
+# over them, with the dropout key of another batch row on a later pass), and the block counts that k_ln_colsum's three
+# tiers split differently.  D = 6 is Vec<2>, D = 8 Vec<4>.
+WALK_SHAPES = [(3, 2731, 8),     # 8193 rows: one wave takes a second row
+               (3, 2731, 6),
+               (4, 2047, 6),     # 8188 rows: 2047 blocks, just under the cap
+               (4, 2047, 8),
+               (2, 1200, 8),     # 2400 rows: 600 blocks = 512 + 64 + 24, the middle tier and the tail of the column sum
+               (2, 1200, 6),
+               (5, 4000, 6),     # 20000 rows: waves take two or three rows
+               (5, 4000, 8)]
 
 
-@pytest.mark.parametrize("B,T_,D", LINE_SHAPES)
+@pytest.mark.parametrize("B,T_,D", LINE_SHAPES + WIDTH_SHAPES + WALK_SHAPES)
 @pytest.mark.parametrize("p", [0.0, 0.3])
 def test_row_lines_vs_composition_with_the_library_mask(gpu, B, T_, D, p):
     """Each line's forward and backward against autograd of the reference's op sequence in float64, with the mask
@@ -196,7 +234,10 @@ def test_row_lines_vs_composition_with_the_library_mask(gpu, B, T_, D, p):
     with torch.no_grad():
         for m in (n1, n2, n3, ng):
             m.weight.normal_(1.0, 0.3); m.bias.normal_(0.0, 0.3)
-    rot = pkg.RotaryFrequencyEmbedding(D).rotation.to(gpu)
+    if (B, T_, D) in WALK_SHAPES:                            # a table of exactly T rows, every row its own angles
+        rot = torch.polar(torch.ones(T_, D // 2), 6.0 * torch.rand(T_, D // 2)).to(gpu)
+    else:
+        rot = pkg.RotaryFrequencyEmbedding(D).rotation.to(gpu)
     d = lambda t: t.detach().double().requires_grad_(True)
 
     # line 1: (x1, h2)
@@ -256,9 +297,8 @@ def test_drop_fraction_of_each_line(gpu):
     assert not torch.equal(x2 == x, x3 == x)                 # every line draws its own words
 
 
-def test_row_backward_is_bitwise_reproducible(gpu):
+def _check_row_backward_reproducible(gpu, B, T_, D):
     _, fn = _pkg()
-    B, T_, D = 16, 512, 256
     torch.manual_seed(5)
     x, pin = torch.randn(B, T_, D, device=gpu), torch.randn(B, T_, D, device=gpu)
     a = torch.randn(B, T_, 2 * D, device=gpu)
@@ -278,6 +318,15 @@ def test_row_backward_is_bitwise_reproducible(gpu):
     first, second = run(), run()
     for i, (u, v) in enumerate(zip(first, second)):
         assert torch.equal(u, v), i
+
+
+def test_row_backward_is_bitwise_reproducible(gpu):
+    _check_row_backward_reproducible(gpu, 16, 512, 256)
+
+
+def test_row_backward_is_bitwise_reproducible_on_the_row_walk(gpu):
+    """20000 rows: every wave adds two or three rows into its partial sums before the block reduction"""
+    _check_row_backward_reproducible(gpu, 5, 4000, 8)
 
 
 def test_fuse_dropout_off_matches_the_composition_with_torch_masks(gpu):

@@ -643,12 +643,11 @@ def test_time_path_conv_matches_the_reference_op_sequence(gpu, B, T, C, use_scal
         assert rel_err(a.cpu().numpy().reshape(r.shape), r.numpy()) <= (TOL_ACT if i < 2 else TOL_PARAM), i
 
 
-@pytest.mark.parametrize("B,Fq,C", [(2, 97, 16), (3, 33, 6), (1, 5, 70), (4, 129, 512), (2, 9, 1000), (5, 1, 130)])
-def test_spectral_layer_norm_matches_the_reference_op_sequence(gpu, B, Fq, C):
-    """SpectralLayerNorm (reference fft_lm/frequency_native.py:203-239: abs, mean, biased var, rsqrt, gamma / beta rows
-    of the bin, angle, exp(i angle)) as one native launch each way (smx_spectral_ln_*), against complex128 autograd of
-    exactly that op sequence: output, grad_z, grad_gamma, grad_beta; zeros of both signs keep the reference's phases
-    (angle(-0 + 0i) = pi) and get a zero gradient; the sums over the batch are bit-identical run to run."""
+SLN_SHAPES = [(2, 97, 16), (3, 33, 6), (1, 5, 70), (4, 129, 512), (2, 9, 1000), (5, 1, 130),      # CH 1, 1, 2, 8, 16, 4
+              (2, 3, 1024)]                                                                      # CH 16 full: the widest row
+
+
+def _check_spectral_layer_norm(gpu, B, Fq, C, planar):
     pkg, lib, fn = _pkg()
     rng = np.random.default_rng(7 * Fq + C)
     z = (rng.standard_normal((B, Fq, C)) + 1j * rng.standard_normal((B, Fq, C))).astype(np.complex64)
@@ -670,19 +669,114 @@ def test_spectral_layer_norm_matches_the_reference_op_sequence(gpu, B, Fq, C):
     zd = torch.tensor(z, device=gpu, requires_grad=True)
     gd, bd = (torch.tensor(a, device=gpu, requires_grad=True) for a in (gamma, beta))
     outs = []
+    g_gpu = torch.tensor(g, device=gpu)
+    if planar:                                               # the gradient arrives as planes too: (dL/dRe, dL/dIm)
+        g_gpu = torch.stack([g_gpu.real, g_gpu.imag]).contiguous()
     for _ in range(2):
         zd.grad = gd.grad = bd.grad = None
-        out = fn.spectral_layer_norm(zd, gd, bd, eps)
-        out.backward(torch.tensor(g, device=gpu))
+        out = fn.spectral_layer_norm(zd, gd, bd, eps, planar=planar)
+        out.backward(g_gpu)
         torch.cuda.synchronize()
         outs.append([out.detach().clone(), zd.grad.clone(), gd.grad.clone(), bd.grad.clone()])
     for a, b in zip(*outs):
         assert torch.equal(a, b)
+    if planar:
+        assert outs[0][0].shape == (2, B, Fq, C) and outs[0][0].dtype == torch.float32
+        outs[0][0] = torch.complex(outs[0][0][0], outs[0][0][1])
     c = lambda t: torch.view_as_real(t).cpu().numpy() if t.is_complex() else t.cpu().numpy()
     refs = [ref.detach(), zr.grad, gr.grad, br.grad]
     for i, (a, r) in enumerate(zip(outs[0], refs)):
         assert rel_err(c(a), c(r)) <= (TOL_ACT if i < 2 else TOL_PARAM), i
     assert float(outs[0][1][0, 0, :3].abs().max()) == 0.0                # zero gradient at the zeros
+
+
+@pytest.mark.parametrize("B,Fq,C", SLN_SHAPES)
+def test_spectral_layer_norm_matches_the_reference_op_sequence(gpu, B, Fq, C):
+    """SpectralLayerNorm (reference fft_lm/frequency_native.py:203-239: abs, mean, biased var, rsqrt, gamma / beta rows
+    of the bin, angle, exp(i angle)) as one native launch each way (smx_spectral_ln_*), against complex128 autograd of
+    exactly that op sequence: output, grad_z, grad_gamma, grad_beta; zeros of both signs keep the reference's phases
+    (angle(-0 + 0i) = pi) and get a zero gradient; the sums over the batch are bit-identical run to run."""
+    _check_spectral_layer_norm(gpu, B, Fq, C, False)
+
+
+@pytest.mark.parametrize("B,Fq,C", SLN_SHAPES)
+def test_planar_spectral_layer_norm_matches_the_reference_op_sequence(gpu, B, Fq, C):
+    """The same against the same reference on the route SpectralFFN.residual takes (spectral_layer_norm(planar=True),
+    k_sln_fwd / k_sln_bwd<CH, true>): the forward writes the (2, B, F, C) real and imaginary planes, the backward reads
+    a gradient that arrives as planes."""
+    _check_spectral_layer_norm(gpu, B, Fq, C, True)
+
+
+def _planes(t):
+    return torch.stack([t.real, t.imag]).contiguous()
+
+
+@pytest.mark.parametrize("B,Fq,C,misaligned", [(3, 33, 6, False), (2, 129, 130, False), (5, 9, 512, False),
+                                               (5, 9, 512, True), (3, 5, 1028, False)])
+def test_planar_cmul_matches_float64(gpu, B, Fq, C, misaligned):
+    """smx_planar_cmul_forward / _backward (PhaseShift between SpectralFFN's Linear layers, reference
+    fft_lm/frequency_native.py:62-77, :175) against fp64 h (f_re + i f_im) and its gradients, the filter gradients
+    summed over the batch: C % 4 != 0 (one channel per lane), C % 4 == 0 (four per lane; C = 1028 is a second
+    256-channel tile with one live lane), and C % 4 == 0 behind base pointers that are only 4-byte aligned, which the
+    library itself sends to the one-channel kernels (the Python wrapper would copy such a view, so the entry points are
+    called directly)."""
+    pkg, lib, fn = _pkg()
+    L = lib.lib()
+    torch.manual_seed(B * 100 + Fq + C)
+    h = torch.randn(B, Fq, C, dtype=torch.complex64)
+    g = torch.randn(B, Fq, C, dtype=torch.complex64)
+    f = torch.randn(Fq, C, dtype=torch.complex64)
+    h64, f64 = (t.to(torch.complex128).requires_grad_(True) for t in (h, f))
+    ref = h64 * f64
+    ref.backward(g.to(torch.complex128))
+    # torch's gradient of a complex leaf is dL/dRe + i dL/dIm: its real part is the gradient of the real plane
+    refs = [_planes(ref.detach()), _planes(h64.grad), f64.grad.real, f64.grad.imag]
+
+    def place(t):
+        """t on the device, 16-byte aligned, or one float past such an address"""
+        if not misaligned:
+            return t.to(gpu)
+        buf = torch.empty(t.numel() + 1, device=gpu)
+        v = buf[1:].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == 4
+        return v
+
+    hp, gp, fr, fi = place(_planes(h)), place(_planes(g)), place(f.real.contiguous()), place(f.imag.contiguous())
+    if misaligned:
+        out, gh, gfr, gfi = (place(torch.zeros_like(t)) for t in (hp, hp, fr, fi))
+        s = torch.cuda.current_stream().cuda_stream
+        lib.check(L.smx_planar_cmul_forward(hp.data_ptr(), fr.data_ptr(), fi.data_ptr(), out.data_ptr(), B, Fq, C, s))
+        lib.check(L.smx_planar_cmul_backward(gp.data_ptr(), hp.data_ptr(), fr.data_ptr(), fi.data_ptr(), gh.data_ptr(),
+                                             gfr.data_ptr(), gfi.data_ptr(), B, Fq, C, s))
+        torch.cuda.synchronize()
+        got = [out, gh, gfr, gfi]
+    else:
+        leaves = [t.requires_grad_(True) for t in (hp, fr, fi)]
+        out = fn.planar_cmul(*leaves)
+        out.backward(gp)
+        torch.cuda.synchronize()
+        got = [out.detach()] + [t.grad for t in leaves]
+    for i, (a, r) in enumerate(zip(got, refs)):
+        assert rel_err(a.cpu().numpy(), r.numpy()) <= (TOL_ACT if i < 2 else TOL_PARAM), i
+
+
+@pytest.mark.parametrize("n", [4, 1000, 2 ** 20 + 4])
+def test_planar_add_and_split_are_the_torch_expressions(gpu, n):
+    """smx_planar_add / smx_planar_split (the residual around SpectralFFN, reference fft_lm/frequency_native.py:355-356,
+    and its backward): y = a + (p[0] + i p[1]) with one rounding per component, the gradient of p the planes of the
+    gradient of y -- exactly, from one workgroup to more elements than the capped grid has threads."""
+    pkg, lib, fn = _pkg()
+    torch.manual_seed(n)
+    a = torch.randn(n, dtype=torch.complex64, device=gpu).requires_grad_(True)
+    p = torch.randn(2, n, device=gpu).requires_grad_(True)
+    g = torch.randn(n, dtype=torch.complex64, device=gpu)
+    y = fn.add_planar(a, p)
+    y.backward(g)
+    torch.cuda.synchronize()
+    assert torch.equal(torch.view_as_real(y.detach()), torch.view_as_real(a.detach() + torch.complex(p[0], p[1]).detach()))
+    assert torch.equal(torch.view_as_real(a.grad), torch.view_as_real(g))
+    assert torch.equal(p.grad, _planes(g))
 
 
 @pytest.mark.parametrize("B,Fq,C,p_drop", [(2, 65, 16, 0.0), (3, 33, 24, 0.0), (2, 129, 130, 0.0)])
