@@ -560,6 +560,46 @@ int smx_gate_blend_backward(const float* g3, const float* a, const float* v, con
                             void* workspace, size_t workspace_bytes, int B, int T, int D, float dropout_p,
                             const void* rng_state, void* stream);
 
+/* SpectralEMA, the frequency-domain state-space memory of fft_lm's chunk head, as one scan launch.
+ *   smx_ema_scan_*    replace the per-step op sequence fft_lm/spectral_ssm.py:71-105 (update) and the Python loop over
+ *                     the S chunks fft_lm/spectral_ssm.py:107-125 (scan): with rho = sigmoid(rho_logit[f]),
+ *                     theta = pi tanh(theta_raw[f]), u(X) = X / |X| (u = 1 at X == 0),
+ *                       SMX_EMA_ALIGNED:  H' = rho e^{i theta} |H| u(X) + (1 - rho) X
+ *                       SMX_EMA_POLAR:    H' = (rho |H| + (1 - rho) |X|) u(X)        (theta_raw unused, may be NULL)
+ *                     over t = 0 .. S-1 from H = init (B, F) (NULL: zeros); out (B, F) = the final state.  chunks (B, S, F),
+ *                     init, out, g, grad_chunks, grad_init: interleaved complex64, 8-byte aligned; rho_logit, theta_raw,
+ *                     their gradients: (F) float32 in DEVICE memory (read by the kernel: a captured graph sees updates).
+ *   smx_ema_tokens_*  the same scan behind fft_lm/chunk_head.py:56-65: chunk t of row b is the L-point real DFT
+ *                     (F = L / 2 + 1 bins, a direct sum) of tokens[b, t L : (t + 1) L] / 127.5 - 1, formed on the fly
+ *                     -- the (B, S, F) spectrum never exists in memory.  2 <= L <= 64, S = T / L (trailing tokens are
+ *                     ignored); token_bytes 1 (uint8) or 8 (int64); row_stride = elements between batch rows (>= T).
+ *                     The DC and Nyquist bins are exact integer sums, and a run of equal bytes gives exactly zero in
+ *                     every other bin; a bin that is exactly zero takes u = 1.
+ * Backward (g = gradient of the final state): each output may be NULL.  The launch reruns the forward chain into the
+ * workspace (smx_ema_workspace_bytes, 256-byte aligned: the (B, S, F) pre-step states and the per-chain parameter
+ * gradients) and walks it in reverse; a second small launch sums the parameter gradients over the batch in a fixed
+ * order -- bitwise reproducible.  The forward saves nothing and needs no workspace.  Where a state is exactly zero the
+ * aligned step hands conj(rho e^{i theta} u(X)) G to it, as the reference's autograd does (angle's gradient is 0
+ * there); SMX_EMA_POLAR writes zeros to grad_theta_raw.
+ * S == 0: out = init (or zeros), grad_init = g, zero parameter gradients.  S < 0, L outside 2..64, a mode other than the
+ * two, NULL required pointers: SMX_ERR_INVALID, nothing enqueued.  Nothing is allocated, the host is never synchronised. */
+#define SMX_EMA_ALIGNED 0
+#define SMX_EMA_POLAR 1
+int smx_ema_workspace_bytes(int B, int S, int F, size_t* out);
+int smx_ema_scan_forward(const float* chunks, const float* init, const float* rho_logit, const float* theta_raw,
+                         float* out, int mode, int B, int S, int F, void* stream);
+int smx_ema_scan_backward(const float* g, const float* chunks, const float* init, const float* rho_logit,
+                          const float* theta_raw, float* grad_chunks, float* grad_init, float* grad_rho_logit,
+                          float* grad_theta_raw, void* workspace, size_t workspace_bytes, int mode, int B, int S, int F,
+                          void* stream);
+int smx_ema_tokens_forward(const void* tokens, int token_bytes, long long row_stride, const float* init,
+                           const float* rho_logit, const float* theta_raw, float* out, int mode, int B, int T, int L,
+                           void* stream);
+int smx_ema_tokens_backward(const float* g, const void* tokens, int token_bytes, long long row_stride, const float* init,
+                            const float* rho_logit, const float* theta_raw, float* grad_init, float* grad_rho_logit,
+                            float* grad_theta_raw, void* workspace, size_t workspace_bytes, int mode, int B, int T, int L,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,13 +8,15 @@ from .spectral_layers import HybridSpectralAttention, SpectralMixingLayer, Spect
 from .wirtinger_ops import (ComplexParameter, WirtingerGradient, WirtingerSpectralFilter,
                             spectral_mix_with_filter)
 from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft, rfft_bins, seq_fft,
-                         spectral_block_mix, spectral_filter, spectral_mix)
+                         spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens)
 from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
 from .frequency_ops import FrequencyAttention
 from .fixed_spectral import FixedSpectralBlock, FrequencyConvFunc, causal_spectral_conv
 from .frequency_native import BicameralBlock, FrequencyNativeBlock, PhaseShift, SpectralFFN, SpectralLayerNorm
+from .spectral_ssm import EMAConfig, SpectralEMA
+from .chunk_head import ChunkLM, vectorized_windows
 from .distributed import GradSync, attach_grad_sync, all_reduce_grads, shard_batch
 
 __all__ = [
@@ -25,7 +27,7 @@ __all__ = [
     "CausalFrequencyMask", "EnhancedSpectralBlock", "ComplexRoPE", "GatedLinearUnit",
     "ComplexRoPESpectralLayer", "FrequencyAttention", "FixedSpectralBlock", "FrequencyConvFunc",
     "causal_spectral_conv", "rfft", "irfft", "FrequencyNativeBlock", "BicameralBlock", "PhaseShift", "SpectralFFN",
-    "SpectralLayerNorm",
+    "SpectralLayerNorm", "EMAConfig", "SpectralEMA", "ChunkLM", "vectorized_windows", "ema_scan", "ema_scan_tokens",
     "GradSync", "attach_grad_sync", "all_reduce_grads", "shard_batch",
 ]
 __version__ = "0.2.0"

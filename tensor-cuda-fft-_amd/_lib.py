@@ -132,6 +132,11 @@ _SIGS = {
     "smx_block_forward_io": (_I, [_P, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _SZ,
                                   _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I]),
     "smx_block_backward_io": (_I, [_P] * 15 + [_SZ, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I]),
+    "smx_ema_workspace_bytes": (_I, [_I, _I, _I, ctypes.POINTER(_SZ)]),
+    "smx_ema_scan_forward": (_I, [_P] * 5 + [_I] * 4 + [_P]),
+    "smx_ema_scan_backward": (_I, [_P] * 10 + [_SZ] + [_I] * 4 + [_P]),
+    "smx_ema_tokens_forward": (_I, [_P, _I, _LL] + [_P] * 4 + [_I] * 4 + [_P]),
+    "smx_ema_tokens_backward": (_I, [_P, _P, _I, _LL] + [_P] * 7 + [_SZ] + [_I] * 4 + [_P]),
 }
 
 

@@ -2109,4 +2109,92 @@ int smx_block_backward_io(const void* g, const void* x, const float* ln_stats, c
   return SMX_OK;
 }
 
+// ---- SpectralEMA scan (smx_ema.hip) ---------------------------------------------------------------------------------------
+static int ema_check(int mode, int B, int S, int F) {
+  if (mode != SMX_EMA_ALIGNED && mode != SMX_EMA_POLAR)
+    return fail(SMX_ERR_INVALID, "mode must be SMX_EMA_ALIGNED (0) or SMX_EMA_POLAR (1), got %d", mode);
+  if (B <= 0 || F <= 0) return fail(SMX_ERR_INVALID, "B and F must be positive: B=%d F=%d", B, F);
+  if (S < 0) return fail(SMX_ERR_INVALID, "the chunk count must not be negative, got %d", S);
+  if ((long long)B * F >= (1ll << 31)) return fail(SMX_ERR_UNSUPPORTED, "smx_ema_*: more than 2^31 chains");
+  return SMX_OK;
+}
+static int ema_tokens_src(const void* tokens, int token_bytes, long long row_stride, int B, int T, int L, EmaSrc* src) {
+  if (L < 2 || L > 64) return fail(SMX_ERR_INVALID, "chunk length L must be in 2..64, got %d", L);
+  if (T < 0) return fail(SMX_ERR_INVALID, "T must not be negative, got %d", T);
+  if (token_bytes != 1 && token_bytes != 8) return fail(SMX_ERR_INVALID, "token_bytes must be 1 (uint8) or 8 (int64)");
+  const int S = T / L;
+  if (S > 0 && !tokens) return fail(SMX_ERR_INVALID, "tokens must be non-NULL");
+  if (S > 0 && row_stride < T) return fail(SMX_ERR_INVALID, "row_stride must be at least T");
+  if (token_bytes == 8 && ((uintptr_t)tokens & 7)) return fail(SMX_ERR_INVALID, "int64 tokens must be 8-byte aligned");
+  *src = EmaSrc{tokens, token_bytes == 1 ? 1 : 2, row_stride, B, S, L / 2 + 1, L};
+  return SMX_OK;
+}
+static size_t ema_need(int B, int S, int F) { return SYNC_BYTES + al(ema_states_bytes(B, S, F)) + al(ema_part_bytes(B, F)); }
+static int ema_fwd(const EmaSrc& src, int mode, const float* init, const float* rho_logit, const float* theta_raw,
+                   float* out, void* stream) {
+  if (!rho_logit || !out || (mode == SMX_EMA_ALIGNED && !theta_raw))
+    return fail(SMX_ERR_INVALID, "rho_logit, theta_raw (aligned mode), out must be non-NULL");
+  if (((uintptr_t)init | (uintptr_t)out) & 7) return fail(SMX_ERR_INVALID, "init and out must be 8-byte aligned");
+  HIP_TRY(launch_ema(src, mode == SMX_EMA_POLAR, (const cf*)init, rho_logit, theta_raw, (cf*)out, (hipStream_t)stream));
+  return SMX_OK;
+}
+static int ema_bwd(const EmaSrc& src, int mode, const float* g, const float* init, const float* rho_logit,
+                   const float* theta_raw, float* grad_chunks, float* grad_init, float* grad_rho_logit,
+                   float* grad_theta_raw, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!g || !rho_logit || (mode == SMX_EMA_ALIGNED && !theta_raw))
+    return fail(SMX_ERR_INVALID, "g, rho_logit, theta_raw (aligned mode) must be non-NULL");
+  if (((uintptr_t)g | (uintptr_t)init | (uintptr_t)grad_chunks | (uintptr_t)grad_init) & 7)
+    return fail(SMX_ERR_INVALID, "g, init, grad_chunks, grad_init must be 8-byte aligned");
+  if (grad_chunks && grad_chunks == src.ptr) return fail(SMX_ERR_INVALID, "grad_chunks must not alias chunks");
+  const size_t need = ema_need(src.B, src.S, src.F);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
+    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes (smx_ema_workspace_bytes)", need);
+  char* states = (char*)workspace + SYNC_BYTES;
+  HIP_TRY(launch_ema_bwd(src, mode == SMX_EMA_POLAR, (const cf*)g, (const cf*)init, rho_logit, theta_raw, (cf*)grad_chunks,
+                         (cf*)grad_init, grad_rho_logit, grad_theta_raw, (cf*)states,
+                         (float*)(states + al(ema_states_bytes(src.B, src.S, src.F))), (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_ema_workspace_bytes(int B, int S, int F, size_t* out) {
+  if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
+  if (int rc = ema_check(SMX_EMA_ALIGNED, B, S, F)) return rc;
+  *out = ema_need(B, S, F);                                         // behind the sync area, as every layout (ws_layout)
+  return SMX_OK;
+}
+int smx_ema_scan_forward(const float* chunks, const float* init, const float* rho_logit, const float* theta_raw,
+                         float* out, int mode, int B, int S, int F, void* stream) {
+  if (int rc = ema_check(mode, B, S, F)) return rc;
+  if ((S > 0 && !chunks) || ((uintptr_t)chunks & 7))
+    return fail(SMX_ERR_INVALID, "chunks must be non-NULL and 8-byte aligned");
+  return ema_fwd(EmaSrc{chunks, 0, 0, B, S, F, 0}, mode, init, rho_logit, theta_raw, out, stream);
+}
+int smx_ema_scan_backward(const float* g, const float* chunks, const float* init, const float* rho_logit,
+                          const float* theta_raw, float* grad_chunks, float* grad_init, float* grad_rho_logit,
+                          float* grad_theta_raw, void* workspace, size_t workspace_bytes, int mode, int B, int S, int F,
+                          void* stream) {
+  if (int rc = ema_check(mode, B, S, F)) return rc;
+  if ((S > 0 && !chunks) || ((uintptr_t)chunks & 7))
+    return fail(SMX_ERR_INVALID, "chunks must be non-NULL and 8-byte aligned");
+  return ema_bwd(EmaSrc{chunks, 0, 0, B, S, F, 0}, mode, g, init, rho_logit, theta_raw, grad_chunks, grad_init,
+                 grad_rho_logit, grad_theta_raw, workspace, workspace_bytes, stream);
+}
+int smx_ema_tokens_forward(const void* tokens, int token_bytes, long long row_stride, const float* init,
+                           const float* rho_logit, const float* theta_raw, float* out, int mode, int B, int T, int L,
+                           void* stream) {
+  EmaSrc src;
+  if (int rc = ema_tokens_src(tokens, token_bytes, row_stride, B, T, L, &src)) return rc;
+  if (int rc = ema_check(mode, B, src.S, src.F)) return rc;
+  return ema_fwd(src, mode, init, rho_logit, theta_raw, out, stream);
+}
+int smx_ema_tokens_backward(const float* g, const void* tokens, int token_bytes, long long row_stride, const float* init,
+                            const float* rho_logit, const float* theta_raw, float* grad_init, float* grad_rho_logit,
+                            float* grad_theta_raw, void* workspace, size_t workspace_bytes, int mode, int B, int T, int L,
+                            void* stream) {
+  EmaSrc src;
+  if (int rc = ema_tokens_src(tokens, token_bytes, row_stride, B, T, L, &src)) return rc;
+  if (int rc = ema_check(mode, B, src.S, src.F)) return rc;
+  return ema_bwd(src, mode, g, init, rho_logit, theta_raw, nullptr, grad_init, grad_rho_logit, grad_theta_raw, workspace,
+                 workspace_bytes, stream);
+}
+
 }  // extern "C"

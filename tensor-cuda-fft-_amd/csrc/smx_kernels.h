@@ -218,6 +218,18 @@ hipError_t launch_gate_bwd(const cf* g, const cf* x, const cf* a, const float* u
                            const float* m, cf* gx, cf* s1, float* rc, float* rp, cf* part, int B, int F, int C,
                            hipStream_t s);
 
+// ---- SpectralEMA scan, one lane per chain (b, f) (smx_ema.hip) -------------------------------------------------------
+// kind 0: ptr = complex chunks (B, S, F); kind 1 / 2: ptr = uint8 / int64 tokens, rows row_stride elements apart,
+// chunk t of row b = the L-point real DFT of tokens[b, t L : (t + 1) L] / 127.5 - 1, F = L / 2 + 1
+struct EmaSrc { const void* ptr; int kind; long long row_stride; int B, S, F, L; };
+size_t ema_states_bytes(int B, int S, int F);      // backward scratch: the pre-step states
+size_t ema_part_bytes(int B, int F);               // backward scratch: per-chain parameter gradients
+hipError_t launch_ema(const EmaSrc& src, bool polar, const cf* init, const float* rho_logit, const float* theta_raw,
+                      cf* out, hipStream_t s);
+hipError_t launch_ema_bwd(const EmaSrc& src, bool polar, const cf* g, const cf* init, const float* rho_logit,
+                          const float* theta_raw, cf* gx, cf* ginit, float* g_rho, float* g_th, cf* states, float* part,
+                          hipStream_t s);
+
 // ---- LayerNorm row kernels of the fused block (smx_block.hip) -------------------------------------
 constexpr int ROW_WAVES = 4;             // wavefronts (rows in flight) per block of the kernels sized by ln_num_blocks
 constexpr int LN_MAX_BLOCKS = 2048;      // most rows of the grad_gamma / grad_beta partial buffer

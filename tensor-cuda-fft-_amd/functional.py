@@ -1808,3 +1808,135 @@ def gate_blend(a: torch.Tensor, v: torch.Tensor, x2: Optional[torch.Tensor], wg,
     p = _check_p(dropout_p)
     return _GateBlend.apply(_dense(a), _dense(v), _dense(x2), _dense(wg), _dense(bg), float(eps), p,
                             drop_state if p > 0.0 else None)
+
+
+# ---- SpectralEMA: the chunk head's state-space memory as one scan launch (csrc/smx_ema.hip) ---------------------------
+EMA_MODES = {"aligned": 0, "polar": 1}                      # include/smx.h SMX_EMA_*
+
+
+def _ema_mode(mode: str) -> int:
+    if mode not in EMA_MODES:
+        raise ValueError(f"unknown SpectralEMA mode {mode!r} (expected 'aligned' or 'polar')")
+    return EMA_MODES[mode]
+
+
+def _ema_ws(dev: torch.device, B: int, S: int, F: int):
+    import ctypes
+    nb = ctypes.c_size_t()
+    _lib.check(_lib.lib().smx_ema_workspace_bytes(B, S, F, ctypes.byref(nb)))
+    return _workspace(dev, int(nb.value))
+
+
+class _EmaScan(torch.autograd.Function):
+    """Final state of the scan over (B, S, F) complex64 chunks (reference fft_lm/spectral_ssm.py:107-125) through
+    smx_ema_scan_forward / _backward.  The forward saves its inputs only: the backward launch reruns the chain."""
+
+    @staticmethod
+    def forward(ctx, chunks, rho_logit, theta_raw, init, mode):
+        B, S, F = chunks.shape
+        out = torch.empty((B, F), dtype=torch.complex64, device=chunks.device)
+        with _on_device(chunks.device):
+            _lib.check(_lib.lib().smx_ema_scan_forward(chunks.data_ptr(), _ptr(init), rho_logit.data_ptr(),
+                                                       theta_raw.data_ptr(), out.data_ptr(), mode, B, S, F,
+                                                       _stream(chunks.device)))
+        ctx.mode, ctx.has_init = mode, init is not None
+        ctx.save_for_backward(chunks, rho_logit, theta_raw, init if init is not None else chunks.new_empty(0))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        chunks, rho_logit, theta_raw, init = ctx.saved_tensors
+        init = init if ctx.has_init else None
+        B, S, F = chunks.shape
+        g = _dense(g.to(torch.complex64))
+        need = ctx.needs_input_grad
+        gx = torch.empty_like(chunks) if need[0] else None
+        gr = torch.empty_like(rho_logit) if need[1] else None
+        gt = torch.empty_like(theta_raw) if need[2] and ctx.mode == 0 else None
+        gi = torch.empty_like(g) if ctx.has_init and need[3] else None
+        ws = _ema_ws(g.device, B, S, F)
+        with _on_device(g.device):
+            _lib.check(_lib.lib().smx_ema_scan_backward(g.data_ptr(), chunks.data_ptr(), _ptr(init), rho_logit.data_ptr(),
+                                                        theta_raw.data_ptr(), _ptr(gx), _ptr(gi), _ptr(gr), _ptr(gt),
+                                                        ws.data_ptr(), ws.numel(), ctx.mode, B, S, F, _stream(g.device)))
+        return gx, gr, gt, gi, None
+
+
+class _EmaScanTokens(torch.autograd.Function):
+    """The same scan with chunk t of row b formed in the kernel from byte tokens (reference fft_lm/chunk_head.py:56-65)
+    through smx_ema_tokens_forward / _backward: the (B, S, F) spectrum is never written."""
+
+    @staticmethod
+    def forward(ctx, tokens, L, rho_logit, theta_raw, mode):
+        B, T = tokens.shape
+        out = torch.empty((B, L // 2 + 1), dtype=torch.complex64, device=tokens.device)
+        ctx.args = (tokens.data_ptr(), tokens.element_size(), tokens.stride(0))
+        with _on_device(tokens.device):
+            _lib.check(_lib.lib().smx_ema_tokens_forward(*ctx.args, None, rho_logit.data_ptr(), theta_raw.data_ptr(),
+                                                         out.data_ptr(), mode, B, T, L, _stream(tokens.device)))
+        ctx.mode, ctx.L = mode, L
+        ctx.save_for_backward(tokens, rho_logit, theta_raw)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        tokens, rho_logit, theta_raw = ctx.saved_tensors
+        B, T = tokens.shape
+        L = ctx.L
+        g = _dense(g.to(torch.complex64))
+        gr = torch.empty_like(rho_logit) if ctx.needs_input_grad[2] else None
+        gt = torch.empty_like(theta_raw) if ctx.needs_input_grad[3] and ctx.mode == 0 else None
+        ws = _ema_ws(g.device, B, T // L, L // 2 + 1)
+        with _on_device(g.device):
+            _lib.check(_lib.lib().smx_ema_tokens_backward(g.data_ptr(), *ctx.args, None, rho_logit.data_ptr(),
+                                                          theta_raw.data_ptr(), None, _ptr(gr), _ptr(gt), ws.data_ptr(),
+                                                          ws.numel(), ctx.mode, B, T, L, _stream(g.device)))
+        return None, None, gr, gt, None
+
+
+def _ema_params(F: int, rho_logit: torch.Tensor, theta_raw: torch.Tensor):
+    for name, p in (("rho_logit", rho_logit), ("theta_raw", theta_raw)):
+        _require_gpu_f32(name, p)
+        if tuple(p.shape) != (F,):
+            raise ValueError(f"{name} must be (F,) = ({F},), got {tuple(p.shape)}")
+    return _dense(rho_logit), _dense(theta_raw)
+
+
+def ema_scan(chunks: torch.Tensor, rho_logit: torch.Tensor, theta_raw: torch.Tensor, mode: str = "aligned",
+             init: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Final (B, F) complex64 state of fft_lm's SpectralEMA over `chunks` (B, S, F) complex64 from `init` (B, F)
+    (None: zeros): one launch forward, one scan launch and a small fixed-order sum backward; differentiable in chunks,
+    rho_logit, theta_raw (None in polar mode, where it takes no part) and init."""
+    m = _ema_mode(mode)
+    if not (isinstance(chunks, torch.Tensor) and chunks.is_cuda and chunks.dtype == torch.complex64 and chunks.dim() == 3):
+        raise TypeError("chunks must be a (B, S, F) complex64 tensor on a ROCm device")
+    B, S, F = chunks.shape
+    rho_logit, theta_raw = _ema_params(F, rho_logit, theta_raw)
+    if init is not None and not (init.is_cuda and init.dtype == torch.complex64 and tuple(init.shape) == (B, F)):
+        raise TypeError(f"init must be (B, F) = ({B}, {F}) complex64 on the device of chunks")
+    if B == 0:
+        return chunks.new_empty((0, F))
+    return _EmaScan.apply(_dense(chunks), rho_logit, theta_raw, _dense(init), m)
+
+
+def ema_scan_tokens(tokens: torch.Tensor, chunk_len: int, rho_logit: torch.Tensor, theta_raw: torch.Tensor,
+                    mode: str = "aligned") -> torch.Tensor:
+    """ema_scan over the chunk spectra of byte tokens (B, T), uint8 or int64: chunk t of row b is the
+    `chunk_len`-point real DFT of tokens[b, t L : (t + 1) L] / 127.5 - 1, formed inside the scan kernel (2 <= L <= 64;
+    bytes past (T // L) L are ignored).  Differentiable in rho_logit and theta_raw (None in polar mode)."""
+    m = _ema_mode(mode)
+    L = int(chunk_len)
+    if not 2 <= L <= 64:
+        raise ValueError(f"chunk_len must be in 2..64, got {L}")
+    if not (isinstance(tokens, torch.Tensor) and tokens.is_cuda and tokens.dim() == 2
+            and tokens.dtype in (torch.uint8, torch.int64)):
+        raise TypeError("tokens must be a (B, T) uint8 or int64 tensor on a ROCm device")
+    rho_logit, theta_raw = _ema_params(L // 2 + 1, rho_logit, theta_raw)
+    if tokens.shape[0] == 0:
+        return torch.empty((0, L // 2 + 1), dtype=torch.complex64, device=tokens.device)
+    if tokens.shape[1] > 1 and tokens.stride(1) != 1 or tokens.stride(0) < tokens.shape[1] \
+            or tokens.data_ptr() % tokens.element_size():
+        tokens = tokens.contiguous()
+    return _EmaScanTokens.apply(tokens, L, rho_logit, theta_raw, m)
