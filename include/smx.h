@@ -600,6 +600,44 @@ int smx_ema_tokens_backward(const float* g, const void* tokens, int token_bytes,
                             float* grad_theta_raw, void* workspace, size_t workspace_bytes, int mode, int B, int T, int L,
                             void* stream);
 
+/* Overlap-save chunk generation: one chunk step of a FixedSpectralBlock at inference as two row-kernel launches
+ * around the block's gate_ctx GEMV (which stays the caller's), replacing the per-chunk op sequence of
+ * scripts/generate_chunked_overlap_save.py:101-172 (LayerNorm of the chunk, a torch.cat of the whole (Bt, T, C) window,
+ * a full sum over it, an rfft and an irfft of n_fft points x C channels of which `chunk` rows are kept, and about a
+ * dozen pointwise launches).  At inference the filter spectrum k_freq sigmoid(gate_freq) (x cutoff mask) is a
+ * constant; h_eff = its n_fft-point inverse transform is a real constant too, and the kept rows of the reference's
+ * circular convolution are a (chunk x (K - 1 + chunk)) Toeplitz slice of h_eff -- negative lags (the circular wrap of
+ * the gated, non-compact h_eff) included -- applied to the last K - 1 + chunk rows of the window.
+ * State per layer, float32 (pos: int32) in DEVICE memory, owned by the caller:
+ *     ring (Bt, T, C)   the window of LayerNorm outputs, a ring buffer that is never copied
+ *     sum  (Bt, 2, C)   the window sum as a compensated pair (hi, lo)
+ *     pos  (Bt)         slot of the oldest row = the next write slot (read by the kernels: a captured graph replays
+ *                       correctly as the ring turns)
+ *   smx_stream_push   (:101-115) for n < chunk: slot = (pos[b] + n) % T, the evicted row is read, LayerNorm(h[b, n];
+ *                     ln_w, ln_b, eps) is written there and new - evicted accumulated; the sums of the block's
+ *                     wavefronts are added in wavefront order (bitwise reproducible) and folded into (hi, lo) by a
+ *                     two-sum; then pooled[b] = (hi + lo) / T and pos[b] = (pos[b] + chunk) % T.  One workgroup per
+ *                     batch row, the only reader and writer of that row's pos: no atomics.  h (Bt, chunk, C),
+ *                     pooled (Bt, C); ln_w / ln_b may be NULL.
+ *   smx_stream_conv   (:118-172 up to the FFN's linears) with pos already advanced, L = K - 1 + chunk,
+ *                     seg[j] = ring[b, (pos[b] - L + j) mod T]:
+ *                       y[n] = sum_{j < L} taps[n + L - 1 - j] seg[j]
+ *                       h_out[b, n] = h[b, n] + scale[b] * y[n]          scale (Bt, C) = gain * g_ctx
+ *                       ff_in[b, n] = LayerNorm(h_out[b, n]; ln_w, ln_b, eps)     (ff_in == NULL: skipped)
+ *                     taps: K + 2 chunk - 2 floats, taps[i] = h_eff[(i - (chunk - 1)) mod n_fft] -- the library never
+ *                     sees n_fft.  h_out may be h.
+ *   smx_stream_supported(T, K, C, chunk): 1 when C is a width of the LayerNorm row kernels (smx_block_supported),
+ *                     1 <= chunk <= 64, 1 <= K <= 4096 and K - 1 + chunk <= T.
+ * NULL required pointers, tensors that are not 16-byte aligned (pos and taps, which no vector load touches: 4-byte),
+ * Bt < 1 or an unsupported shape:
+ * SMX_ERR_INVALID, nothing enqueued.  Nothing is allocated, the host is never synchronised. */
+int smx_stream_supported(int T, int K, int C, int chunk);
+int smx_stream_push(const float* h, const float* ln_w, const float* ln_b, float eps, float* ring, float* sum, int* pos,
+                    float* pooled, int Bt, int T, int C, int chunk, void* stream);
+int smx_stream_conv(const float* h, const float* ring, const int* pos, const float* taps, const float* scale,
+                    const float* ln_w, const float* ln_b, float eps, float* h_out, float* ff_in, int Bt, int T, int K,
+                    int C, int chunk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

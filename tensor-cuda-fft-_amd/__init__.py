@@ -13,10 +13,12 @@ from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, 
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
 from .frequency_ops import FrequencyAttention
-from .fixed_spectral import FixedSpectralBlock, FrequencyConvFunc, causal_spectral_conv
+from .fixed_spectral import FixedSpectralBlock, FixedSpectralLM, FrequencyConvFunc, LMConfig, causal_spectral_conv
 from .frequency_native import BicameralBlock, FrequencyNativeBlock, PhaseShift, SpectralFFN, SpectralLayerNorm
 from .spectral_ssm import EMAConfig, SpectralEMA
 from .chunk_head import ChunkLM, vectorized_windows
+from .streaming import (LayerStream, StreamStates, generate_chunked, init_layer_states, stream_taps,
+                        update_backbone_chunk)
 from .distributed import GradSync, attach_grad_sync, all_reduce_grads, shard_batch
 
 __all__ = [
@@ -28,6 +30,7 @@ __all__ = [
     "ComplexRoPESpectralLayer", "FrequencyAttention", "FixedSpectralBlock", "FrequencyConvFunc",
     "causal_spectral_conv", "rfft", "irfft", "FrequencyNativeBlock", "BicameralBlock", "PhaseShift", "SpectralFFN",
     "SpectralLayerNorm", "EMAConfig", "SpectralEMA", "ChunkLM", "vectorized_windows", "ema_scan", "ema_scan_tokens",
-    "GradSync", "attach_grad_sync", "all_reduce_grads", "shard_batch",
+    "GradSync", "attach_grad_sync", "all_reduce_grads", "shard_batch", "FixedSpectralLM", "LMConfig", "StreamStates",
+    "LayerStream", "stream_taps", "init_layer_states", "update_backbone_chunk", "generate_chunked",
 ]
 __version__ = "0.2.0"

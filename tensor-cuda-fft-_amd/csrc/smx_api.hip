@@ -2197,4 +2197,38 @@ int smx_ema_tokens_backward(const float* g, const void* tokens, int token_bytes,
                  workspace_bytes, stream);
 }
 
+// ---- overlap-save chunk generation (smx_stream.hip) -----------------------------------------------------------------------
+static int stream_check(const char* fn, int Bt, int T, int K, int C, int chunk, std::initializer_list<const void*> ptrs) {
+  if (Bt < 1 || Bt > (1 << 24)) return fail(SMX_ERR_INVALID, "%s: Bt must be in 1..2^24, got %d", fn, Bt);
+  if (!stream_supported(T, K, C, chunk))
+    return fail(SMX_ERR_INVALID,
+                "%s: unsupported shape T=%d K=%d C=%d chunk=%d (smx_stream_supported: a LayerNorm row width, "
+                "1 <= chunk <= %d, 1 <= K <= %d, K - 1 + chunk <= T)", fn, T, K, C, chunk, STREAM_MAX_CHUNK, STREAM_MAX_K);
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 15) return fail(SMX_ERR_INVALID, "%s: tensors must be 16-byte aligned", fn);
+  return SMX_OK;
+}
+int smx_stream_supported(int T, int K, int C, int chunk) { return stream_supported(T, K, C, chunk) ? 1 : 0; }
+int smx_stream_push(const float* h, const float* ln_w, const float* ln_b, float eps, float* ring, float* sum, int* pos,
+                    float* pooled, int Bt, int T, int C, int chunk, void* stream) {
+  if (!h || !ring || !sum || !pos || !pooled)
+    return fail(SMX_ERR_INVALID, "smx_stream_push: h, ring, sum, pos, pooled must be non-NULL");
+  if ((uintptr_t)pos & 3) return fail(SMX_ERR_INVALID, "smx_stream_push: pos must be 4-byte aligned");
+  if (int rc = stream_check("smx_stream_push", Bt, T, 1, C, chunk, {h, ln_w, ln_b, ring, sum, pooled})) return rc;
+  HIP_TRY(launch_stream_push(h, ln_w, ln_b, eps, ring, sum, pos, pooled, Bt, T, C, chunk, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_stream_conv(const float* h, const float* ring, const int* pos, const float* taps, const float* scale,
+                    const float* ln_w, const float* ln_b, float eps, float* h_out, float* ff_in, int Bt, int T, int K,
+                    int C, int chunk, void* stream) {
+  if (!h || !ring || !pos || !taps || !scale || !h_out)
+    return fail(SMX_ERR_INVALID, "smx_stream_conv: h, ring, pos, taps, scale, h_out must be non-NULL");
+  if (((uintptr_t)pos | (uintptr_t)taps) & 3)
+    return fail(SMX_ERR_INVALID, "smx_stream_conv: pos and taps must be 4-byte aligned");
+  if (int rc = stream_check("smx_stream_conv", Bt, T, K, C, chunk, {h, ring, scale, ln_w, ln_b, h_out, ff_in})) return rc;
+  HIP_TRY(launch_stream_conv(h, ring, pos, taps, scale, ln_w, ln_b, eps, h_out, ff_in, Bt, T, K, C, chunk,
+                             (hipStream_t)stream));
+  return SMX_OK;
+}
+
 }  // extern "C"

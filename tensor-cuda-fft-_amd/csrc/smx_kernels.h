@@ -284,4 +284,16 @@ hipError_t launch_gate_blend_bwd(const float* g3, const float* a, const float* v
                                  int T, int D, unsigned thr, float scale, const unsigned long long* rng,
                                  hipStream_t s);
 
+// ---- overlap-save chunk generation: the window ring of a FixedSpectralBlock (smx_stream.hip) -----------------
+constexpr int STREAM_MAX_K = 4096;       // longest kernel, and with it the tap table held in LDS
+constexpr int STREAM_MAX_CHUNK = 64;
+bool stream_supported(int T, int K, int C, int chunk);
+// ring[b, (pos[b] + n) % T] = LN(h[b, n]), (hi, lo) += new - evicted, pooled = (hi + lo) / T, pos += chunk
+hipError_t launch_stream_push(const float* h, const float* ln_w, const float* ln_b, float eps, float* ring, float* sum,
+                              int* pos, float* pooled, int Bt, int T, int C, int chunk, hipStream_t s);
+// h_out = h + scale * (Toeplitz slice of taps) (last K - 1 + chunk ring rows), ff_in = LN(h_out) (nullable)
+hipError_t launch_stream_conv(const float* h, const float* ring, const int* pos, const float* taps, const float* scale,
+                              const float* ln_w, const float* ln_b, float eps, float* h_out, float* ff_in, int Bt, int T,
+                              int K, int C, int chunk, hipStream_t s);
+
 }  // namespace smx

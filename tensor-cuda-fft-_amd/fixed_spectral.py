@@ -15,6 +15,7 @@ cropped output.  Parameter gradients follow from the native grad_W through that 
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
@@ -138,8 +139,24 @@ def causal_spectral_conv(x: torch.Tensor, kernel: torch.Tensor, gain: torch.Tens
     return spectral_filter(x, w_re, w_im, None, n_fft=n_fft, k=fbins, row_scale=g_ctx)
 
 
+def _causal_conv_torch(x, kernel, gain, gate_freq_logits, g_ctx, cutoff, transition_bins):
+    """causal_spectral_conv's line through torch.fft, for CPU tensors only (as spectral_ssm.py's torch path: the
+    library has no CPU kernels, and on a ROCm device the native line is the only one)."""
+    B, T, C = x.shape
+    K = kernel.shape[0]
+    n_fft = next_pow2(T + K - 1)
+    fbins = n_fft // 2 + 1
+    h = torch.fft.rfft(kernel.to(x.dtype), n=n_fft) * torch.sigmoid(gate_freq_logits[:fbins]).to(x.dtype)
+    mask = cutoff_mask(cutoff, fbins, transition_bins, x.device)
+    if mask is not None:
+        h = h * mask.to(x.dtype)
+    y = torch.fft.irfft(torch.fft.rfft(x, n=n_fft, dim=1) * h.view(1, -1, 1), n=n_fft, dim=1)[:, :T]
+    return y * (gain.unsqueeze(0) * g_ctx).unsqueeze(1)
+
+
 class FixedSpectralBlock(nn.Module):
-    """Pre-norm causal spectral mixing + gated valve + FFN residual (reference :427-563)."""
+    """Pre-norm causal spectral mixing + gated valve + FFN residual (reference :427-563).  A CPU input takes the same
+    line through torch.fft (streaming.py's torch path and the CPU tests run on it)."""
 
     def __init__(self, d_model: int, seq_len: int, kernel_len: int, transition_bins: int, dropout: float = 0.1):
         super().__init__()
@@ -169,8 +186,12 @@ class FixedSpectralBlock(nn.Module):
         residual = x
         x = self.ln(x)
         g_ctx = torch.sigmoid(self.gate_ctx(x.mean(dim=1)))                # :532-533
-        y = causal_spectral_conv(x, self.kernel, self.gain, self.gate_freq_logits, g_ctx, cutoff,
-                                 self.transition_bins)
+        if x.is_cuda:
+            y = causal_spectral_conv(x, self.kernel, self.gain, self.gate_freq_logits, g_ctx, cutoff,
+                                     self.transition_bins)
+        else:
+            y = _causal_conv_torch(x, self.kernel, self.gain, self.gate_freq_logits, g_ctx, cutoff,
+                                   self.transition_bins)
         x = residual + self.drop(y)                                        # :557-558
         return x + self.drop(self.ffn(self.ffn_ln(x)))                     # :561-562
 
@@ -212,3 +233,49 @@ class FrequencyConvFunc(torch.autograd.Function):
         grad_kernel = (s_conj * gain.unsqueeze(0)).sum(dim=1)                                 # :114
         grad_gain = (s_plain * kernel_freq.unsqueeze(1)).real.sum(dim=0)                      # :117
         return grad_x, grad_kernel, grad_gain
+
+
+@dataclass
+class LMConfig:
+    """The fields of the reference's TrainConfig that FixedSpectralLM reads, with its defaults (reference :38-49, :63)."""
+    vocab_size: int = 256
+    d_model: int = 512
+    n_layers: int = 6
+    seq_len: int = 1024
+    kernel_len: int = 128
+    jpeg_transition: int = 32
+    bicameral: bool = False
+    frequency_native: bool = False
+
+
+class FixedSpectralLM(nn.Module):
+    """Byte embedding, n_layers spectral blocks, final LayerNorm, logits through the embedding matrix (weight tying):
+    reference :566-618, the backbone ChunkLM wraps.  `cfg` is an LMConfig, the reference's TrainConfig or any object
+    with LMConfig's fields; state_dict keys `embed.*`, `blocks.{i}.*`, `ln_f.*` as in the reference."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        self.embed = nn.Embedding(cfg.vocab_size, cfg.d_model)
+        if cfg.bicameral:                                                  # :573-583
+            from .frequency_native import BicameralBlock as block_class
+        elif cfg.frequency_native:
+            from .frequency_native import FrequencyNativeBlock as block_class
+        else:
+            block_class = FixedSpectralBlock
+        self.blocks = nn.ModuleList([
+            block_class(cfg.d_model, seq_len=cfg.seq_len, kernel_len=cfg.kernel_len,
+                        transition_bins=cfg.jpeg_transition, dropout=0.1)
+            for _ in range(cfg.n_layers)])
+        self.ln_f = nn.LayerNorm(cfg.d_model)
+
+    def forward(self, x: torch.Tensor, cutoff: "int | None" = None) -> torch.Tensor:
+        """x (B, T) long -> logits (B, T, vocab_size)."""
+        return torch.matmul(self.forward_hidden(x, cutoff=cutoff), self.embed.weight.t())
+
+    def forward_hidden(self, x: torch.Tensor, cutoff: "int | None" = None) -> torch.Tensor:
+        """x (B, T) long -> final hidden states (B, T, d_model)."""
+        h = self.embed(x)
+        for blk in self.blocks:
+            h = blk(h, cutoff=cutoff)
+        return self.ln_f(h)
