@@ -257,6 +257,16 @@ extern "C" int emu_fused16(int mode, const float* xin, const float* w_re, const 
   return 0;
 }
 
+// Every tile count the four-step plan accepts (fs_tiles_filter in smx_api.hip), as the kernels' SMX_FS_CASE lists:
+// L = 5 ... 32 with the column transform in one thread's registers (launch_fs_f), and L = L1 L2 on the two-level
+// columns with the smallest L2 in {4, 8, 16} that leaves L1 = 9 ... 16 (fs_two_level): 36 ... 64 step 4,
+// 72 ... 128 step 8, 144 ... 256 step 16.
+#define EMU_FS_ONE_LEVEL(X) \
+  X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) \
+  X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
+#define EMU_FS_L1(X, L2) X(L2, 9) X(L2, 10) X(L2, 11) X(L2, 12) X(L2, 13) X(L2, 14) X(L2, 15) X(L2, 16)
+#define EMU_FS_TWO_LEVEL(X) EMU_FS_L1(X, 4) EMU_FS_L1(X, 8) EMU_FS_L1(X, 16)
+
 // Four-step path (smx_core.h, end): (A) tile spectra -> workspace, (F) per-thread column pairs, (B) inverse.
 template <int L, int MODE>
 static void run_fourstep(const float* xin, const FilterArgs& fa, float* yout, const Geom& g) {
@@ -414,25 +424,18 @@ extern "C" int emu_fourstep_ex(int mode, const float* xin, const float* w_re, co
   fa.xk_in = mode == 1 ? xk : nullptr;
   fa.pslab = pslab; fa.gb_part = gb_part;
   fa.sc = sc; fa.gsc = gsc;
-  if (g.L == 8) { if (mode == 0) run_fourstep<8, 0>(xin, fa, yout, g); else run_fourstep<8, 1>(xin, fa, yout, g); }
-  else if (g.L == 16) { if (mode == 0) run_fourstep<16, 0>(xin, fa, yout, g); else run_fourstep<16, 1>(xin, fa, yout, g); }
-  else if (g.L == 32) { if (mode == 0) run_fourstep<32, 0>(xin, fa, yout, g); else run_fourstep<32, 1>(xin, fa, yout, g); }
-  else if (g.L == 5) { if (mode == 0) run_fourstep<5, 0>(xin, fa, yout, g); else run_fourstep<5, 1>(xin, fa, yout, g); }
-  else if (g.L == 12) { if (mode == 0) run_fourstep<12, 0>(xin, fa, yout, g); else run_fourstep<12, 1>(xin, fa, yout, g); }
-  else if (g.L == 24) { if (mode == 0) run_fourstep<24, 0>(xin, fa, yout, g); else run_fourstep<24, 1>(xin, fa, yout, g); }
-  else if (g.L == 26) { if (mode == 0) run_fourstep<26, 0>(xin, fa, yout, g); else run_fourstep<26, 1>(xin, fa, yout, g); }
-  else if (g.L == 17) { if (mode == 0) run_fourstep<17, 0>(xin, fa, yout, g); else run_fourstep<17, 1>(xin, fa, yout, g); }
-  else if (g.L == 25) { if (mode == 0) run_fourstep<25, 0>(xin, fa, yout, g); else run_fourstep<25, 1>(xin, fa, yout, g); }
-  else if (g.L == 64) { if (mode == 0) run_fourstep_big<4, 0>(xin, fa, yout, g); else run_fourstep_big<4, 1>(xin, fa, yout, g); }
-  else if (g.L == 128) { if (mode == 0) run_fourstep_big<8, 0>(xin, fa, yout, g); else run_fourstep_big<8, 1>(xin, fa, yout, g); }
-  else if (g.L == 256) { if (mode == 0) run_fourstep_big<16, 0>(xin, fa, yout, g); else run_fourstep_big<16, 1>(xin, fa, yout, g); }
-  // round 3: first-level lengths 9 ... 15 (a multiple of L2, one with a padded thread, one per L2)
-  else if (g.L == 48) { if (mode == 0) run_fourstep_big<4, 0, 12>(xin, fa, yout, g); else run_fourstep_big<4, 1, 12>(xin, fa, yout, g); }
-  else if (g.L == 36) { if (mode == 0) run_fourstep_big<4, 0, 9>(xin, fa, yout, g); else run_fourstep_big<4, 1, 9>(xin, fa, yout, g); }
-  else if (g.L == 52) { if (mode == 0) run_fourstep_big<4, 0, 13>(xin, fa, yout, g); else run_fourstep_big<4, 1, 13>(xin, fa, yout, g); }
-  else if (g.L == 80) { if (mode == 0) run_fourstep_big<8, 0, 10>(xin, fa, yout, g); else run_fourstep_big<8, 1, 10>(xin, fa, yout, g); }
-  else if (g.L == 144) { if (mode == 0) run_fourstep_big<16, 0, 9>(xin, fa, yout, g); else run_fourstep_big<16, 1, 9>(xin, fa, yout, g); }
-  else return -2;
+  switch (g.L) {
+#define EMU_FS_CASE(LL) \
+    case LL: if (mode == 0) run_fourstep<LL, 0>(xin, fa, yout, g); else run_fourstep<LL, 1>(xin, fa, yout, g); break;
+    EMU_FS_ONE_LEVEL(EMU_FS_CASE)
+#undef EMU_FS_CASE
+#define EMU_FS_CASE(L2, L1) \
+    case L1 * L2: if (mode == 0) run_fourstep_big<L2, 0, L1>(xin, fa, yout, g); \
+                  else run_fourstep_big<L2, 1, L1>(xin, fa, yout, g); break;
+    EMU_FS_TWO_LEVEL(EMU_FS_CASE)
+#undef EMU_FS_CASE
+    default: return -2;
+  }
   return 0;
 }
 
@@ -533,19 +536,12 @@ extern "C" int emu_synth(const float* spec, float* yout, int B, int R, int D, in
   }
   if (fourstep) {
     switch (g.L) {
-      case 5: run_fs_synth<5>(fa, yout, g); break;
-      case 8: run_fs_synth<8>(fa, yout, g); break;
-      case 12: run_fs_synth<12>(fa, yout, g); break;
-      case 16: run_fs_synth<16>(fa, yout, g); break;
-      case 32: run_fs_synth<32>(fa, yout, g); break;
-      case 24: run_fs_synth<24>(fa, yout, g); break;
-      case 17: run_fs_synth<17>(fa, yout, g); break;
-      case 64: run_fourstep_big<4, 4>(nullptr, fa, yout, g); break;
-      case 128: run_fourstep_big<8, 4>(nullptr, fa, yout, g); break;
-      case 256: run_fourstep_big<16, 4>(nullptr, fa, yout, g); break;
-      case 36: run_fourstep_big<4, 4, 9>(nullptr, fa, yout, g); break;
-      case 48: run_fourstep_big<4, 4, 12>(nullptr, fa, yout, g); break;
-      case 80: run_fourstep_big<8, 4, 10>(nullptr, fa, yout, g); break;
+#define EMU_FS_CASE(LL) case LL: run_fs_synth<LL>(fa, yout, g); break;
+      EMU_FS_ONE_LEVEL(EMU_FS_CASE)
+#undef EMU_FS_CASE
+#define EMU_FS_CASE(L2, L1) case L1 * L2: run_fourstep_big<L2, 4, L1>(nullptr, fa, yout, g); break;
+      EMU_FS_TWO_LEVEL(EMU_FS_CASE)
+#undef EMU_FS_CASE
       default: return -2;
     }
     return 0;

@@ -234,6 +234,13 @@ FS = [  # (B, rows, D, F, n_fft, k)
     (1, 20480, 2, 10241, 20480, 10241),  # L = 80 = 10 x 8: two q1 per thread, threads 5 ... 7 padding
     (1, 30000, 2, 18433, 36864, 18433),  # L = 144 = 9 x 16: one q1 per thread, seven threads padding; padded rows
 ]
+# The tile counts of the plan (fs_tiles_filter in csrc/smx_api.hip) that nothing above runs: one-level, with the odd
+# base lengths 9, 11, 13 and what the radix-2 step builds from them, and two-level L = L1 x L2.  Every other one with
+# zero-padded rows and pruned bins.
+FS_MORE = [6, 9, 10, 11, 13, 14, 18, 19, 20, 21, 22, 27, 28, 29,
+           40, 60, 72, 88, 96, 104, 112, 120, 160, 176, 192, 208, 224]
+FS += [(1, 256 * L, 2, 128 * L + 1, 256 * L, 128 * L + 1) if i % 2 == 0 else
+       (1, 256 * L - 100 - L, 2, 64 * L + 257, 256 * L, 64 * L + 257) for i, L in enumerate(FS_MORE)]
 
 
 @pytest.mark.parametrize("B,R,D,F,n_fft,k", FS)
@@ -417,7 +424,8 @@ def test_emulated_rank_one_conv_single_launch(emu, B, R, D, N, nj):
     (1, 9216, 2, 9216, 4609, 1),    # round 3: L = 36 = 9 x 4 (a padded thread per column pair)
     (1, 11000, 4, 12288, 6145, 1),  # L = 48 = 12 x 4, cropped rows
     (1, 20480, 2, 20480, 7000, 1),  # L = 80 = 10 x 8, pruned
-])
+] + [(1, 256 * L, 2, 256 * L, 128 * L + 1, 1) if i % 2 else (1, 256 * L - 100 - L, 2, 256 * L, 64 * L + 257, 1)
+     for i, L in enumerate(FS_MORE + [26])])    # the remaining tile counts; cropped / pruned the other way round
 @pytest.mark.parametrize("herm", [0, 1])
 def test_emulated_synthesis(emu, B, R, D, N, k, fs, herm):
     rng = np.random.default_rng(N + k + D)
@@ -433,9 +441,9 @@ def test_emulated_synthesis(emu, B, R, D, N, k, fs, herm):
     if herm:
         ref = np.fft.irfft(full, n=N, axis=1)[:, :R]                      # numpy ignores Im of DC / Nyquist too
     else:                                                                 # weight 1 on every bin: Re of the sum
-        n = np.arange(R)[:, None] * np.arange(k)[None, :]
-        E = np.exp(2j * np.pi * (n % N) / N)
-        ref = np.einsum("nf,bfd->bnd", E, S).real
+        zero = np.zeros((B, N, D), np.complex128)                         # sum_f S_f e^{+2 pi i f n / N}, S_f = 0
+        zero[:, :k] = S                                                   # for f >= k, is N ifft(S)
+        ref = N * np.fft.ifft(zero, axis=1).real[:, :R]
     assert rel_err(y, ref) <= TOL_ACT
 
 

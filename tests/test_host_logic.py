@@ -166,3 +166,25 @@ def test_slow_plans_warn_once_for_large_problems():
         Fn._note_plan(_lib.plan(64, 8704, 2048, 1024), 64, 8704, 2048, 8704)    # band groups (L = 34)
     assert len(w) == 2 and "not a multiple of 256" in str(w[0].message) and "band groups" in str(w[1].message)
     Fn._slow_plan_warned.clear()
+
+
+def test_four_step_chunked_walk_shapes_keep_several_tiles_per_workgroup():
+    """The shapes tests/test_fourstep_gpu.py runs for the streaming loop of k_fs_a / k_fs_b (prefetch, double buffer,
+    wrap, rotated start, ragged last chunk) only reach it while the plan gives a workgroup more than one tile: pin
+    what smx_plan_query_ex reports for them, so that a retuned 512 / nwg cannot turn those tests into one-tile runs
+    unnoticed.  The tile counts that file sweeps are pinned against the plan the same way."""
+    from tensor_cuda_fft_amd import _lib
+    from test_fourstep_gpu import TILE_COUNTS, WALK
+    assert len(WALK) == 8
+    for (B, R, D, n_fft), L, nwg, lc, chunks in WALK:
+        p = _lib.plan_ex(_lib.smx_shape(B, R, D, n_fft // 2 + 1, n_fft, n_fft // 2 + 1))
+        assert (p.path, p.bands, p.groups) == (_lib.SMX_PATH_DECIMATED, 0, 1), (B, R, D, n_fft)
+        assert (p.L, p.nsplit, p.workgroups) == (L, chunks, nwg * chunks), (B, R, D, n_fft)
+        assert nwg == B * math.ceil(D / 32) and math.ceil(p.L / p.nsplit) == lc and lc > 1, (B, R, D, n_fft)
+    assert len(TILE_COUNTS) == 52
+    taken = []
+    for L in range(1, 262):
+        p = _lib.plan_ex(_lib.smx_shape(1, 256 * L, 2, 128 * L + 1, 256 * L, 128 * L + 1))
+        if p.path == _lib.SMX_PATH_DECIMATED and p.bands == 0:
+            taken.append(L)
+    assert taken == TILE_COUNTS
