@@ -63,7 +63,13 @@ const char* smx_last_error(void);
  * 1 rotated residues, 2 XCD-aware = default, 3 | a << 8 | b << 16 = XCD-aware with the residue rotation
  * (a l2 + b d_tile) mod L, used by tools/rot_scan.py), "round" (workgroups per launch of the streaming
  * kernels, default 512 = one resident round; 0 = a single launch), "force_direct" (0/1), "full8", "fourstep",
- * "fs_bgroups", "fold_gradw", "tiled_dft", "decim16", "conv1", "st_plain" (A/B switches of DESIGN.md), "table_cache_entries" (twiddle-table cache bound). */
+ * "fs_bgroups", "fold_gradw", "tiled_dft", "decim16", "conv1", "st_plain" (A/B switches of DESIGN.md), "table_cache_entries" (twiddle-table cache bound).
+ * "st_layout_fwd" / "st_layout_bwd" ("st_layout" sets both): WHICH of a thread's 16 rows per tile are the st_plain
+ * write-back rows of the buffer-addressed streaming stores in the forward / backward launches: -2 (default) by the library's
+ * rule (4 on the single-launch plan up to 320 MiB of output, else -1: DESIGN.md section 4.6); -1 the first
+ * ones, one contiguous block per batch row; 0 every (16 / st_plain)-th row; 1 .. 4 the same rotated per tile by the
+ * residue r, by r >> 2, by the wave index, by wave index + r.  Process-wide only -- not a
+ * member of smx_options, which cannot grow -- and without effect on any result or workspace layout. */
 int smx_set_option(const char* name, int value);
 
 /* The same knobs as an argument of the calling context: every call THIS THREAD makes between

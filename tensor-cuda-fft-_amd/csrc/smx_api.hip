@@ -47,6 +47,11 @@ int fail(int code, const char* fmt, ...) {
 // g_opt_epoch changes with every change of a default.
 std::atomic<int> o_nsplit{0}, o_placement{2}, o_force_direct{0}, o_round{512}, o_full8{1}, o_fourstep{1};
 std::atomic<int> o_fs_bgroups{0}, o_fold_gradw{0}, o_decim16{1}, o_conv1{1}, o_st_plain{-1};
+// placement of the write-back rows (store_layout, smx_kernels.h), forward and backward launches apart.  Not a member of
+// smx_options (the struct has no size field to grow by): process-wide only.  The store policy never changes a result or
+// a workspace layout, so the two halves of a call pair need not agree on it.
+// -2 (default) = by the rule in decim_args.
+std::atomic<int> o_st_layout_fwd{-2}, o_st_layout_bwd{-2};
 std::atomic<unsigned long long> g_opt_epoch{1}, g_tab_epoch{1};
 constexpr int OPT_DEPTH = 8;
 thread_local smx_options t_opt_stack[OPT_DEPTH];
@@ -415,7 +420,8 @@ int need_ws(const Ws& w, void* ws, size_t bytes) {
 }
 
 // elem: bytes per element of the streamed x / y (4; 2 for the 2-byte activations of the _io entries)
-DecimArgs decim_args(const Plan& p, const Tables& t, const Shape& h, char* ws, const Ws& w, int elem = 4) {
+// dir: 0 = a forward entry point, 1 = a backward one (which "st_layout_*" option places the write-back rows)
+DecimArgs decim_args(const Plan& p, const Tables& t, const Shape& h, char* ws, const Ws& w, int elem = 4, int dir = 0) {
   const int B = h.B, N = h.N, D = h.D, F = h.F;
   DecimArgs a{};
   a.tw = t.tw; a.bt = t.bt; a.tq = t.tq;
@@ -437,6 +443,21 @@ DecimArgs decim_args(const Plan& p, const Tables& t, const Shape& h, char* ws, c
     const int aut = mib <= (p.nsplit > 1 ? 768 : 320) ? 4 : mib <= 768 ? 2 : mib <= 1536 ? 1 : 0;
     a.st_plain = opt.st_plain < 0 ? aut : (opt.st_plain >= 4 ? 4 : opt.st_plain == 3 ? 2 : opt.st_plain);
     a.g.st_plain = a.st_plain;            // (the pointer-addressed tile stores read it from the geometry)
+    // WHICH rows (buffer-addressed stores only: store_rows; layouts in smx_kernels.h store_layout).  Rule: the single-launch
+    // plan up to 320 MiB of output (C2) spreads them as single rows rotated by tile residue AND wave (layout 4);
+    // everything else keeps the thread's first rows (-1).  Why (profiles/store_layout_census.txt;
+    // C2 ms per step, 8 fresh processes per candidate and lease, rounds interleaved with the previous build):
+    //   previous build: two process modes, fast 0.2030-0.2066 (median F = 0.2049, max - min w = 0.0025 / 0.0033), slow
+    //   0.2161-0.2191, mean over all P = 0.2105 / 0.2112 -- in-step backward launch 99.9-100.3 us or 109.2-109.6 us
+    //   layout  -1: 0.2050-0.2204 (same two modes)     0: 0.2018-0.2134     2: 0.2087-0.2230 (every process slow)
+    //   layout   1: 0.2009-0.2060 / 0.2012-0.2040      3: 0.1996-0.2054 / 0.1990-0.2042
+    //   layout   4: 0.2005-0.2030 / 0.1998-0.2033, median 0.2022 / 0.2023: one mode (max - min <= 2 w on both
+    //               leases; 1 and 3 pass 2 w on one lease only), median below F; backward launch 99.3-100.0 us in 8 of 8
+    // C3 (residue-split plan) is slower with it (0.4413-0.4630 against 0.4349-0.4432), C5 (two rounds, two write-back rows)
+    // the same within noise (0.4830-0.4884 against 0.4840-0.4897): both keep -1.
+    int lay = (dir ? o_st_layout_bwd : o_st_layout_fwd).load();
+    if (lay < -1) lay = p.nsplit == 1 && mib <= 320 ? 4 : -1;
+    store_layout(a, lay);
   }
   a.nsplit = p.nsplit; a.lc = p.lc;
   a.sum_in_f = p.nb == 1 && p.nsplit <= 64;       // one band: k_split_f sums the chunk partials itself (no k_split_sum)
@@ -554,6 +575,9 @@ int smx_set_option(const char* name, int value) {
   else if (!strcmp(name, "decim16")) o = &o_decim16;
   else if (!strcmp(name, "conv1")) o = &o_conv1;
   else if (!strcmp(name, "st_plain")) o = &o_st_plain;
+  else if (!strcmp(name, "st_layout")) { o_st_layout_fwd = value; o = &o_st_layout_bwd; }
+  else if (!strcmp(name, "st_layout_fwd")) o = &o_st_layout_fwd;
+  else if (!strcmp(name, "st_layout_bwd")) o = &o_st_layout_bwd;
   else if (!strcmp(name, "tiled_dft")) { set_tiled_dft(value); g_opt_epoch++; return SMX_OK; }
   else if (!strcmp(name, "table_cache_entries")) { o_table_cap = value < 1 ? 1 : value; return SMX_OK; }
   else return fail(SMX_ERR_INVALID, "unknown option '%s'", name);
@@ -926,7 +950,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
     return SMX_OK;
   }
   if (p.path == SMX_PATH_DECIMATED) {
-    DecimArgs a = decim_args(p, t, h, ws, w, oio != SMX_IO_F32 ? 2 : 4);
+    DecimArgs a = decim_args(p, t, h, ws, w, oio != SMX_IO_F32 ? 2 : 4, 1);
     a.in = g; a.out = grad_x;
     a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.conj_w = 1;
     a.fa.xk_in = xk; a.fa.pslab = (float*)(ws + w.slab); a.fa.gb_part = (float*)(ws + w.gbp);

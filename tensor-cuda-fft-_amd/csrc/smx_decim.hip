@@ -168,7 +168,7 @@ template <int NB, bool RES, bool DROP, bool PAD, bool LAST, class YB, class RB>
 __device__ __forceinline__ void inverse_tile(TState<NB>& st, cf* E, const YB& yb, const DecimArgs& a,
                                              int t, int j, int r, int rn,
                                              const RB& res, cf (&rx)[RES ? 16 : 1], Drop dr,
-                                             unsigned pj) {
+                                             unsigned pj, int sw) {
   const Geom& g = a.g;
   inv_phase1<NB, true>(st, a.bt + (size_t)r * BT_STRIDE, E, t, j);
   __syncthreads();
@@ -193,7 +193,7 @@ __device__ __forceinline__ void inverse_tile(TState<NB>& st, cf* E, const YB& yb
     for (int u = 0; u < 16; ++u) st.v[u] = cadd(st.v[u], rx[u]);
     if constexpr (!LAST) load_rows<0, 16, PAD>(res, rn, rx);
   }
-  store_rows<PAD>(yb, r, st.v, a.st_plain);
+  store_rows<PAD>(yb, r, st.v, st_tile_mask(a, r, sw));
 }
 
 template <int NB, bool RES = false, bool DROP = false, bool PAD = false, class YB, class RB>
@@ -203,6 +203,8 @@ __device__ __forceinline__ void inverse_loop(TState<NB>& st, cf* lds, const YB& 
                                              unsigned pj = 0) {
   const Geom& g = a.g;
   int r = rbeg + rot;
+  // the wave's term of the store layout's rotation (st_tile_mask, smx_launch.h): scalar, formed once
+  const int sw = (__builtin_amdgcn_readfirstlane(t) >> 2) >> a.st_wsh;      // (the wave's first lane has t = 4 w)
   cf rx[RES ? 16 : 1];
   if constexpr (RES) load_rows<0, 16, PAD>(res, r, rx);
   load_cp(a.tq + ((size_t)t * g.L + r) * 16, st.cp);
@@ -215,10 +217,10 @@ __device__ __forceinline__ void inverse_loop(TState<NB>& st, cf* lds, const YB& 
   for (; i + 1 < cnt; ++i) {
     int rn = r + 1;
     if (rn == rbeg + cnt) rn = rbeg;
-    inverse_tile<NB, RES, DROP, PAD, false>(st, lds + (i & 1) * EX, yb, a, t, j, r, rn, res, rx, dr, pj);
+    inverse_tile<NB, RES, DROP, PAD, false>(st, lds + (i & 1) * EX, yb, a, t, j, r, rn, res, rx, dr, pj, sw);
     r = rn;
   }
-  inverse_tile<NB, RES, DROP, PAD, true>(st, lds + (i & 1) * EX, yb, a, t, j, r, r, res, rx, dr, pj);
+  inverse_tile<NB, RES, DROP, PAD, true>(st, lds + (i & 1) * EX, yb, a, t, j, r, r, res, rx, dr, pj, sw);
 }
 
 __device__ __forceinline__ Drop make_drop(const DecimArgs& a, int b) {

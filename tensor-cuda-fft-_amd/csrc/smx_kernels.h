@@ -19,8 +19,12 @@ struct DecimArgs {
   int placement;        // workgroup placement: 0 b-major, 1 + rotated residues, 2 XCD-aware (default)
   int accumulate;       // four-band kernels only: out += instead of out = (band groups after the first)
   int round;            // workgroups per launch of the streaming kernels (0 = all in one launch)
-  int st_plain;         // 0, 1, 2 or 4: a thread's first rows of every tile stored write-back, the others streaming
-  int bid0;             // first workgroup index of this launch (set by the launchers)
+  int st_plain;         // 0, 1, 2 or 4: rows of every tile (of a thread's 16) stored write-back, the others streaming
+  // which ones (store_rows, smx_launch.h): row u of tile r in wave w is write-back iff bit u of
+  // rot16(st_mask, (r >> st_rsh) + (w >> st_wsh)) is set; store_layout() below fills the three from the option
+  unsigned st_mask;
+  int st_rsh, st_wsh;
+  int bid0;            // first workgroup index of this launch (set by the launchers)
   // split path only
   int nsplit, lc;       // residues are cut into nsplit chunks of lc
   int sum_in_f;         // 1: k_split_f sums the chunk partials itself (no k_split_sum launch)
@@ -53,6 +57,25 @@ struct DecimArgs {
   const float* ln_w;    // (D) or null (= 1)
   const float* ln_b;    // (D) or null (= 0)
 };
+
+// Placement of the a.st_plain write-back rows of a tile (option "st_layout").  rot16(m, s): bit u
+// of the result = bit (u + s) mod 16 of m, so with the base mask of period 16 / count (0x1111, 0x0101, 0x0001) row u is
+// write-back iff (u + s) mod (16 / count) == 0.  s per layout (r = tile residue, w = wave of the workgroup = t >> 2):
+//   -1  the thread's FIRST rows u < count, no rotation: one contiguous count/16 of every batch row (1 MiB of 4 at C2)
+//    0  s = 0: rows u = 0 (mod 16 / count), count blocks of 1/16 of the batch row (256 KiB)
+//    1  s = r: pieces of one row (D elements, 1 KiB)        2  s = r >> 2: four rows (4 KiB)
+//    3  s = w: the 4 L rows of one wave (64 KiB), another u in every 16 L-row window
+//    4  s = w + r: single rows again, also rotated by wave
+// A shift of 30 switches a term off (r and w are small non-negative numbers).
+static inline void store_layout(DecimArgs& a, int layout) {
+  const int c = a.st_plain;
+  a.st_rsh = a.st_wsh = 30;
+  if (layout < 0 || layout > 4) { a.st_mask = (1u << c) - 1u; return; }
+  a.st_mask = c == 4 ? 0x1111u : c == 2 ? 0x0101u : c == 1 ? 0x0001u : 0u;
+  if (layout == 1 || layout == 4) a.st_rsh = 0;
+  if (layout == 2) a.st_rsh = 2;
+  if (layout == 3 || layout == 4) a.st_wsh = 0;
+}
 
 // one flag per transform workgroup + the count of finished reduction workgroups
 static inline size_t sync_words(int B, int D) { return (size_t)B * ((D + DT - 1) / DT) + 1; }

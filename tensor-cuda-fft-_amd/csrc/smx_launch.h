@@ -156,13 +156,24 @@ __device__ __forceinline__ void load_rows(const RowBufT<IO>& rb, int r, cf (&v)[
     v[u] = mk(fx, fy);
   }
 }
-// plain (wave-uniform: 0, 1, 2 or 4 -- DecimArgs::st_plain, chosen from the output's bytes in smx_api decim_args): the
-// thread's first `plain` rows go out with the default write-back policy, the others with the streaming hint.  About
-// 64 MiB of an output tensor written back through L2 / Infinity Cache costs nothing (it drains under the next
-// launch's reads); all 16 rows streaming were 9 % slower per C2 step, all 16 cached 13 %
-// (profiles/r04_store_policy.txt).  Four scalar branches per tile.
+// mask (wave-uniform, 16 bits; st_mask() below): row u goes out with the default write-back policy iff bit u is set, the
+// others with the streaming hint.  DecimArgs::st_plain of the 16 bits are set (0, 1, 2 or 4, chosen from the output's
+// bytes in smx_api decim_args); which ones is the store layout (store_layout(), smx_kernels.h).  About 64 MiB of an
+// output tensor written back through L2 / Infinity Cache costs nothing (it drains under the next launch's reads); all
+// 16 rows streaming were 9 % slower per C2 step, all 16 cached 13 % (profiles/r04_store_policy.txt).  The policy is an
+// immediate of the store, so every row is two store forms behind a scalar branch: sixteen s_bitcmp1 + branch per tile,
+// nothing per lane.
+__device__ __forceinline__ unsigned rot16(unsigned m, unsigned s) {
+  s &= 15u;
+  return ((m >> s) | (m << (16u - s))) & 0xffffu;
+}
+// sw = (wave of the workgroup) >> a.st_wsh, a scalar the caller forms once per launch (readfirstlane: the compiler
+// does not know that t >> 2 is wave-uniform, and a per-lane mask would turn the branches into exec masks)
+__device__ __forceinline__ unsigned st_tile_mask(const DecimArgs& a, int r, int sw) {
+  return rot16(a.st_mask, (unsigned)((r >> a.st_rsh) + sw));
+}
 template <bool PAD, int IO>
-__device__ __forceinline__ void store_rows(const RowBufT<IO>& rb, int r, const cf (&v)[16], int plain) {
+__device__ __forceinline__ void store_rows(const RowBufT<IO>& rb, int r, const cf (&v)[16], unsigned mask) {
   const unsigned vr = rb.vo + (unsigned)r * rb.rowb;
 #pragma unroll
   for (int u = 0; u < 16; ++u) {
@@ -172,10 +183,10 @@ __device__ __forceinline__ void store_rows(const RowBufT<IO>& rb, int r, const c
     else w = narrow2<IO>(fx, fy);
     const unsigned vo = PAD ? vr + (unsigned)u * rb.su : vr, so = PAD ? 0u : (unsigned)u * rb.su;
     if constexpr (IO == 0) {
-      if (u < 4 && u < plain) __builtin_amdgcn_raw_buffer_store_b64(w, rb.rs, vo, so, 0);
+      if (mask & (1u << u)) __builtin_amdgcn_raw_buffer_store_b64(w, rb.rs, vo, so, 0);
       else __builtin_amdgcn_raw_buffer_store_b64(w, rb.rs, vo, so, BUF_NT);
     } else {
-      if (u < 4 && u < plain) __builtin_amdgcn_raw_buffer_store_b32(w, rb.rs, vo, so, 0);
+      if (mask & (1u << u)) __builtin_amdgcn_raw_buffer_store_b32(w, rb.rs, vo, so, 0);
       else __builtin_amdgcn_raw_buffer_store_b32(w, rb.rs, vo, so, BUF_NT);
     }
   }
@@ -191,7 +202,8 @@ __device__ RowBufT<IO> row_buf(const void* row0, const Geom& g, int t, int d, bo
 template <int IO>
 __device__ RowBufT<IO> row_buf(const void* base, int b, const Geom& g, int t, int d, bool in_range = true);
 template <int U0, int CNT, bool PAD, int IO> __device__ void load_rows(const RowBufT<IO>& rb, int r, cf (&v)[16]);
-template <bool PAD, int IO> __device__ void store_rows(const RowBufT<IO>& rb, int r, const cf (&v)[16], int plain);
+__device__ unsigned st_tile_mask(const DecimArgs& a, int r, int sw);
+template <bool PAD, int IO> __device__ void store_rows(const RowBufT<IO>& rb, int r, const cf (&v)[16], unsigned mask);
 #endif
 
 // ---- launch helpers ----------------------------------------------------------------------------

@@ -1,13 +1,16 @@
 #!/bin/bash
 # The step-time "mode" of a process against its in-step kernel durations: N fresh processes of the bench under
 # rocprofv3 --kernel-trace --stats; prints step time and the average duration of every smx kernel of that process.
+# BENCH_ARGS='--opts st_layout=4' probes another option set, SMX_LIB another build.  A process that fails ends the probe.
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 N=${1:-6}
 cd /tmp && export TMPDIR=/tmp SMX_BENCH_NO_BOX=1
 for i in $(seq $N); do
   O=$R/gpurun_out/mode_probe/$i
   rm -rf "$O"; mkdir -p "$O"
-  timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > "$O/log.txt" 2>&1
+  timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs ${BENCH_ARGS:-} > "$O/log.txt" 2>&1
+  rc=$?
+  if [ $rc -ne 0 ]; then echo "process $i: exit $rc, stopping"; tail -5 "$O/log.txt"; exit $rc; fi
   python3 - "$O" <<'PY'
 import sys, json, glob, csv
 o = sys.argv[1]
