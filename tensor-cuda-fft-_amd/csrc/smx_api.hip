@@ -197,7 +197,7 @@ struct Plan {
   int path, k, L, nb, nsplit, lc, nwg;
   int groups;     // band groups of 512 bins (1 unless k > 512)
   int nedge;      // bins 512, 1024, ... < k: left to the edge kernels when groups > 1
-  bool fs;        // four-step path (k_fs_a / k_fs_f / k_fs_b): more than 512 bins at the tile counts of fs_tiles();
+  bool fs;        // four-step path (k_fs_a / k_fs_f / k_fs_b): more than 512 bins at the tile counts of fs_tiles_filter();
   int fs_nsplit, fs_lc;   // takes precedence over the band groups and over full8 (option "fourstep" = 0: off)
   bool conv1 = false;   // smx_conv_*: one launch per direction (k_conv1: n_fft <= 2048)
   int conv1_nj = 16;    // ... channel pairs per workgroup of that launch (16: 512 threads; 8: 256 threads)
@@ -234,17 +234,7 @@ int shape_from(const smx_shape* sh, Shape* out) {
   return check_shape(*out);
 }
 
-// tile counts the four-step path takes: the column transform in one thread's registers (5 ... 16; even 18 ... 32
-// by one radix-2 step over two half-length transforms) or shared by L / 16 threads (64, 128, 256)
-static bool fs_tiles(int L) {
-  return (L >= 5 && L <= 32) || L == 64 || L == 128 || L == 256;      // (odd 17 ... 31: round 3)
-}
-// ... plus every L = L1 L2 the two-level
-// columns take with a first-level length 9 ... 15: 36 ... 60 step 4, 72 ... 120 step 8, 144 ... 240 step 16
-static bool fs_tiles_filter(int L) {
-  int l1, l2;
-  return fs_tiles(L) || (L >= 33 && L <= 256 && fs_two_level(L, &l1, &l2));
-}
+// (the tile counts the four-step path takes: fs_tiles_filter / fs_tiles_cfft, smx_kernels.h)
 
 // residue (256-point plan) or tile (sixteen-row plan) chunks per (batch row, d-tile): L = items to cut
 static int choose_nsplit(int forced, int nwg, int L, double bytes) {
@@ -986,7 +976,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
       // wrote).  Measured at (64,1024,512), G = 8: k_gradw 71 -> 16 us, but k_fs_f<8,1> 215 -> 286 us -- one
       // thread walking 8 batch rows exposes the load latency 9216 independent workgroups hide.  Off by default.
       const int bgo = cur_opts().fs_bgroups;
-      const int bg = (bgo > 0 && p.L >= 5 && p.L <= 16 && B >= 2 * bgo) ? bgo : 0;
+      const int bg = (bgo > 0 && fs_grouped_tiles::has(p.L) && B >= 2 * bgo) ? bgo : 0;
       a.fs_bgroups = bg;
       if (do_spec) {
         HIP_TRY(launch_fs_a(a, s));
@@ -1108,7 +1098,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
 static bool cfft_plan(const Shape& h, Plan* p) {
   if (h.N % M != 0 || h.D % 2 != 0 || h.R > h.N) return false;
   const int L = h.N / M;
-  if (!(L == 2 || L == 4 || fs_tiles_filter(L))) return false;
+  if (!fs_tiles_cfft(L)) return false;
   *p = Plan{};
   p->path = SMX_PATH_DECIMATED; p->L = L; p->k = h.N / 2 + 1; p->nb = 4; p->groups = 1;
   p->nwg = h.B * ((h.D + DT - 1) / DT);
@@ -1166,7 +1156,7 @@ static bool conv_plan(const Shape& h, Plan* p) {
   // fit one thread's registers in backward up to L = 16; above that L / 16 threads share a column pair)
   if (h.N % M != 0 || h.D % 2 != 0 || h.R > h.N) return false;
   const int L = h.N / M;
-  if (!(L == 2 || L == 4 || L == 8 || L == 16 || L == 32 || L == 64 || L == 128 || L == 256)) return false;
+  if (!conv_tiles(L)) return false;
   *p = Plan{};
   p->path = SMX_PATH_DECIMATED; p->L = L; p->k = h.N / 2 + 1; p->nb = 4; p->groups = 1;
   p->nwg = h.B * ((h.D + DT - 1) / DT);

@@ -375,81 +375,54 @@ __global__ __launch_bounds__(256) void k_phase_filter_bwd(const float* __restric
 
 hipError_t launch_conv_response(const float* kernel, const float* logits, const float* mask, const cf* tw, int N,
                                 int K, float* h_re, float* h_im, hipStream_t s) {
-  hipLaunchKernelGGL(k_conv_response, dim3((N / 2 + 1 + 31) / 32), dim3(256), 0, s, kernel, logits, mask, tw, N, K,
+  SMX_LAUNCH(k_conv_response, dim3((N / 2 + 1 + 31) / 32), dim3(256), s, kernel, logits, mask, tw, N, K,
                      h_re, h_im);
-  return hipGetLastError();
+  return launch_status();
 }
 hipError_t launch_conv_response_bwd(const float* kernel, const float* logits, const float* mask, const cf* tw, int N,
                                     int K, int n_logits, const float* gh_re, const float* gh_im, float* grad_kernel,
                                     float* grad_logits, hipStream_t s) {
   const int lb = grad_logits ? (n_logits + 31) / 32 : 0;
-  hipLaunchKernelGGL(k_conv_response_bwd, dim3(K + lb), dim3(256), 0, s, kernel, logits, mask, tw, N, K, n_logits,
+  SMX_LAUNCH(k_conv_response_bwd, dim3(K + lb), dim3(256), s, kernel, logits, mask, tw, N, K, n_logits,
                      gh_re, gh_im, grad_kernel, grad_logits);
-  return hipGetLastError();
+  return launch_status();
 }
 
 hipError_t launch_phase_filter(const float* m, const float* ph, int D, int k, int n_fft, float* w_re, float* w_im,
                                hipStream_t s) {
   const long long total = (long long)D * k;
   const unsigned blocks = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(k_phase_filter, dim3(blocks ? blocks : 1), dim3(256), 0, s, m, ph, D, k, n_fft, w_re, w_im);
-  return hipGetLastError();
+  SMX_LAUNCH(k_phase_filter, dim3(blocks ? blocks : 1), dim3(256), s, m, ph, D, k, n_fft, w_re, w_im);
+  return launch_status();
 }
 hipError_t launch_phase_filter_bwd(const float* m, const float* ph, const float* gw_re, const float* gw_im, int D, int k,
                                    int n_fft, int ld, float* g_m, float* g_p, hipStream_t s) {
-  hipLaunchKernelGGL(k_phase_filter_bwd, dim3(D), dim3(256), 0, s, m, ph, gw_re, gw_im, D, k, n_fft, ld, g_m, g_p);
-  return hipGetLastError();
+  SMX_LAUNCH(k_phase_filter_bwd, dim3(D), dim3(256), s, m, ph, gw_re, gw_im, D, k, n_fft, ld, g_m, g_p);
+  return launch_status();
 }
-
-namespace {
-template <int LP, int NJ, bool FOLD, int IO>
-void launch_conv1_f(const DecimArgs& a, int dir, bool pad, dim3 grid, dim3 block, hipStream_t s) {
-  if (dir == 0 && pad) hipLaunchKernelGGL((k_conv1<LP, 0, true, NJ, FOLD, IO>), grid, block, 0, s, a);
-  else if (dir == 0) hipLaunchKernelGGL((k_conv1<LP, 0, false, NJ, FOLD, IO>), grid, block, 0, s, a);
-  else if (pad) hipLaunchKernelGGL((k_conv1<LP, 1, true, NJ, FOLD, IO>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((k_conv1<LP, 1, false, NJ, FOLD, IO>), grid, block, 0, s, a);
-}
-template <int LP, int NJ, int IO>
-void launch_conv1_t(const DecimArgs& a, int dir, hipStream_t s) {
-  const dim3 grid(conv1_workgroups(a.g.B, a.g.D, NJ)), block(c1_tpb<NJ>());
-  const bool fold = 2 * a.g.R > a.g.N;                    // rows beyond N / 2: folded onto the lower half
-  const bool pad = fold ? a.g.R < a.g.N : 2 * a.g.R < a.g.N;
-  if (fold) launch_conv1_f<LP, NJ, true, IO>(a, dir, pad, grid, block, s);
-  else launch_conv1_f<LP, NJ, false, IO>(a, dir, pad, grid, block, s);
-}
-template <int NJ, int IO>
-hipError_t launch_conv1_nj(const DecimArgs& a, int dir, hipStream_t s) {
-  switch (a.g.N) {
-    case 512: launch_conv1_t<1, NJ, IO>(a, dir, s); break;
-    case 1024: launch_conv1_t<2, NJ, IO>(a, dir, s); break;
-    case 2048: launch_conv1_t<4, NJ, IO>(a, dir, s); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-// both workgroup widths for every IO: the width sets which channel pairs one workgroup's partial sums of P / (R1, R2)
-// hold, and so the f32 summation order of the response's gradient -- a 2-byte launch must take the f32 plan's width
-template <int IO>
-hipError_t launch_conv1_io(const DecimArgs& a, int nj, int dir, hipStream_t s) {
-  return nj == 8 ? launch_conv1_nj<8, IO>(a, dir, s) : launch_conv1_nj<16, IO>(a, dir, s);
-}
-
-}  // namespace
-
-bool conv1_supported(int N, int R) { return (N == 512 || N == 1024 || N == 2048) && R >= 1 && R <= N; }
 
 int conv1_workgroups(int B, int D, int nj) { return B * ((D + 2 * nj - 1) / (2 * nj)); }
 
+// k_conv1<LP, DIR, PAD, NJ, FOLD, IO>: every combination of the lists below exists (lengths: conv1_lp, smx_kernels.h).
+// Both workgroup widths for every IO: the width sets which channel pairs one workgroup's partial sums of P / (R1, R2)
+// hold, and so the f32 summation order of the response's gradient -- a 2-byte launch must take the f32 plan's width.
 hipError_t launch_conv1(const DecimArgs& a0, int nj, int dir, float* gh_re, float* gh_im, float* grad_scale,
                         hipStream_t s, int io) {
   DecimArgs a = a0;
   a.bid0 = 0;
-  const hipError_t e = io == 1 ? launch_conv1_io<1>(a, nj, dir, s)
-                     : io == 2 ? launch_conv1_io<2>(a, nj, dir, s) : launch_conv1_io<0>(a, nj, dir, s);
-  if (e != hipSuccess) return e;
+  const bool fold = 2 * a.g.R > a.g.N;                    // rows beyond N / 2: folded onto the lower half
+  const bool pad = fold ? a.g.R < a.g.N : 2 * a.g.R < a.g.N;
+  const bool ok = conv1_length(a.g.N) && pick_key([&](auto LP, auto DIR, auto PAD, auto NJ, auto FOLD, auto IO) {
+    constexpr int J = SMX_KEY(NJ);
+    SMX_LAUNCH((k_conv1<SMX_KEY(LP), SMX_KEY(DIR), SMX_KEY(PAD), J, SMX_KEY(FOLD), SMX_KEY(IO)>),
+               dim3(conv1_workgroups(a.g.B, a.g.D, J)), dim3(c1_tpb<J>()), s, a);
+    return true;
+  }, conv1_lp{a.g.N / 512}, among<0, 1>{dir}, flag{pad}, among<8, 16>{nj}, flag{fold}, among<0, 1, 2>{io});
+  if (!ok) return hipErrorInvalidValue;
+  if (hipError_t e = launch_status()) return e;
   if (dir == 1)                                   // (R1, R2) arrive / N, one row of nj per workgroup
     return launch_conv_reduce(a, gh_re, gh_im, grad_scale, 1, 0.5f, s, conv1_workgroups(a.g.B, a.g.D, nj), nj);
-  return hipGetLastError();
+  return hipSuccess;
 }
 
 }  // namespace smx

@@ -351,6 +351,16 @@ __device__ __forceinline__ void gradw_tail(const DecimArgs& a, cf* lds, int cb) 
 // k_gradw, bitwise the same sums), and only the configurations smx_api routes there are instantiated (launch_fused).
 // OIO: element type of a.out where it is not a.in's.  One pairing exists: 2-byte g in, f32 rows out (MODE 1), the
 // transform of the 2-byte block backward -- its output is grad_h, which the LayerNorm backward reads unrounded.
+// The instances of k_fused that exist (launch_fused asks this before it launches, and instantiates nothing else).
+// 2-byte rows (io = SMX_IO_BF16 / SMX_IO_F16): only what smx_api routes to them -- modes 0 and 1 with and without dropout,
+// no zero-padded rows, no accumulating band groups; f32 rows out of 2-byte g (oio 0) in mode 1 only, the block backward.
+// An f32 instance must never read 2-byte rows.
+constexpr bool fused_instance(int nb, int mode, bool drop, bool acc, bool pad, int io, int oio) {
+  if (!among<1, 2, 4>::has(nb) || !among<0, 1, 2>::has(mode)) return false;
+  if (acc) return nb == 4 && mode != 2 && !drop && io == 0 && oio == 0;   // band groups after the first: four bands
+  if (io == 0) return oio == 0 && !(drop && (pad || mode == 2));          // (dropout never with zero-padded rows)
+  return among<1, 2>::has(io) && mode != 2 && !pad && (oio == io || (oio == 0 && mode == 1));
+}
 template <int NB, int MODE, bool DROP = false, bool ACC = false, bool PAD = false, int IO = 0, int OIO = IO>
 __global__ __launch_bounds__(TPB, 2) void k_fused(const DecimArgs a) {
   SMX_LDS_DECL;
@@ -487,6 +497,9 @@ __device__ __forceinline__ void inverse16_loop(TState<NB>& st, cf* lds, float* _
 
 // One launch per direction like k_fused<NB, MODE>.  NB = 1: k <= 128, the filter slice staged through LDS;
 // NB = 2: k <= 256, the filter from its packed copy (fa.wt) or gathered.
+constexpr bool fused16_instance(int nb, int mode, bool pad, bool drop) {
+  return among<1, 2>::has(nb) && among<0, 1, 2>::has(mode) && !(drop && (pad || mode == 2));
+}
 template <int NB, int MODE, bool PAD = false, bool DROP = false>
 __global__ __launch_bounds__(TPB, 2) void k_fused16(const DecimArgs a) {
   SMX_LDS_DECL;
@@ -527,6 +540,9 @@ __global__ __launch_bounds__(TPB, 2) void k_fused16(const DecimArgs a) {
 // Few (batch row, d-tile) pairs: the tiles are cut into nsplit chunks as on the 256-point split plan -- (A) partial
 // spectra per chunk, then the SAME k_split_sum / k_split_f (the accumulator layout is the same), then (B) the inverse
 // per chunk.  (B) with nsplit = 1 is also the inverse half of a phase-split backward.
+constexpr bool split16_instance(int nb, bool pad, bool drop) {      // k_split16_a and k_split16_b
+  return among<1, 2>::has(nb) && !(pad && drop);
+}
 template <int NB, bool PAD = false, bool DROP = false>
 __global__ __launch_bounds__(TPB, 2) void k_split16_a(const DecimArgs a) {
   SMX_LDS_DECL;
@@ -687,6 +703,7 @@ __global__ __launch_bounds__(TPB, 1) void k_synth8(const DecimArgs a) {
 // inside the loops cost more than the second workgroup per CU gains: 784 vs 688 us at (32,4096,1024))
 // IO: element type of x and y as in k_fused -- the LayerNorm-on-load rows, the residual re-read and the store; the
 // statistics, gamma / beta and the spectrum stay f32, so y is the f32 kernel's y on the widened x, rounded once.
+// k_fused_blk<NB, DROP, IO>: every combination of NB 1 2 4, DROP, IO 0 1 2 exists
 template <int NB, bool DROP = false, int IO = 0>
 __global__ __launch_bounds__(TPB, NB > 2 ? 1 : 2) void k_fused_blk(const DecimArgs a) {
   SMX_LDS_DECL;
@@ -724,6 +741,9 @@ __global__ __launch_bounds__(TPB, NB > 2 ? 1 : 2) void k_fused_blk(const DecimAr
 }
 
 // ---- split path: (A) partial forward over a chunk of residues ---------------------------------
+constexpr bool split_a_instance(int nb, bool drop, bool pad, int io) {
+  return among<1, 2, 4>::has(nb) && among<0, 1, 2>::has(io) && !(pad && (drop || io != 0));
+}
 template <int NB, bool DROP = false, bool PAD = false, int IO = 0>
 __global__ __launch_bounds__(TPB, 2) void k_split_a(const DecimArgs a) {
   SMX_LDS_DECL;
@@ -831,6 +851,11 @@ __global__ __launch_bounds__(TPB, NB > 1 ? 1 : 2) void k_split_f(const DecimArgs
 // (B) inverse over a chunk of residues, from the filtered spectrum parked by k_split_f / k_fused.
 // (Folding the unpack + filter into this launch was measured: every chunk workgroup repeating the
 // latency-bound prologue cost 33 us at C3, against 15 us for the separate B*ndt-block launch.)
+constexpr bool split_b_instance(int nb, bool drop, bool acc, bool pad, int io) {
+  if (!among<1, 2, 4>::has(nb) || !among<0, 1, 2>::has(io)) return false;
+  if (acc) return nb == 4 && !drop && io == 0;
+  return !(pad && (drop || io != 0));
+}
 template <int NB, bool DROP = false, bool ACC = false, bool PAD = false, int IO = 0>
 __global__ __launch_bounds__(TPB, 2) void k_split_b(const DecimArgs a) {
   SMX_LDS_DECL;
@@ -868,264 +893,145 @@ template __global__ void k_split_b<1>(const DecimArgs);
 template __global__ void k_split16_b<1>(const DecimArgs);
 template __global__ void k_fused16<1, 0>(const DecimArgs);
 #else
-// four bands, accumulating store (band groups after the first)
-static void launch_fused_acc(const DecimArgs& a, int mode, dim3 grid, hipStream_t s) {
-  const bool pad = a.g.R < a.g.N;
-  if (mode == 0 && pad) hipLaunchKernelGGL((k_fused<4, 0, false, true, true>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 0) hipLaunchKernelGGL((k_fused<4, 0, false, true>), grid, dim3(TPB), 0, s, a);
-  else if (pad) hipLaunchKernelGGL((k_fused<4, 1, false, true, true>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((k_fused<4, 1, false, true>), grid, dim3(TPB), 0, s, a);
-}
-
-// 2-byte rows (io = SMX_IO_BF16 / SMX_IO_F16): only the instances smx_api routes to exist -- modes 0 and 1 with and
-// without dropout, no zero-padded rows, no accumulating band groups.  The launchers refuse everything else
-// (hipErrorInvalidValue) before the first launch: an f32 instance must never read 2-byte rows.
-static bool io_instance(const DecimArgs& a, int io) {
-  return io == 0 || ((io == 1 || io == 2) && !(a.g.R < a.g.N) && !a.accumulate);
-}
-
-template <int NB, int IO>
-static void launch_fused_t(const DecimArgs& a, int mode, dim3 grid, hipStream_t s) {
-  const bool drop = a.drop_thr != 0;     // mode 0: on the stored tile, mode 1: on the loaded tile
-  if constexpr (IO == 0) {
-    if (a.g.R < a.g.N) {                 // zero-padded rows (never together with dropout, smx_api)
-      if (mode == 0) hipLaunchKernelGGL((k_fused<NB, 0, false, false, true>), grid, dim3(TPB), 0, s, a);
-      else if (mode == 1) hipLaunchKernelGGL((k_fused<NB, 1, false, false, true>), grid, dim3(TPB), 0, s, a);
-      else hipLaunchKernelGGL((k_fused<NB, 2, false, false, true>), grid, dim3(TPB), 0, s, a);
-      return;
-    }
-    if (mode != 0 && mode != 1) { hipLaunchKernelGGL((k_fused<NB, 2>), grid, dim3(TPB), 0, s, a); return; }
-  }
-  if (mode == 0 && drop) hipLaunchKernelGGL((k_fused<NB, 0, true, false, false, IO>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 0) hipLaunchKernelGGL((k_fused<NB, 0, false, false, false, IO>), grid, dim3(TPB), 0, s, a);
-  else if (drop) hipLaunchKernelGGL((k_fused<NB, 1, true, false, false, IO>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((k_fused<NB, 1, false, false, false, IO>), grid, dim3(TPB), 0, s, a);
-}
-template <int IO>
-static void launch_fused_nb(const DecimArgs& a, int nb, int mode, dim3 grid, hipStream_t s) {
-  if (nb == 4) launch_fused_t<4, IO>(a, mode, grid, s);
-  else if (nb == 2) launch_fused_t<2, IO>(a, mode, grid, s);
-  else launch_fused_t<1, IO>(a, mode, grid, s);
-}
-
-// 2-byte g in, f32 rows out: mode 1 only (see k_fused, OIO)
-template <int IO>
-static void launch_fused_mixed(const DecimArgs& a, int nb, dim3 grid, hipStream_t s) {
-  const dim3 block(TPB);
-  if (a.drop_thr != 0) {
-    if (nb == 4) hipLaunchKernelGGL((k_fused<4, 1, true, false, false, IO, 0>), grid, block, 0, s, a);
-    else if (nb == 2) hipLaunchKernelGGL((k_fused<2, 1, true, false, false, IO, 0>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_fused<1, 1, true, false, false, IO, 0>), grid, block, 0, s, a);
-  } else if (nb == 4) hipLaunchKernelGGL((k_fused<4, 1, false, false, false, IO, 0>), grid, block, 0, s, a);
-  else if (nb == 2) hipLaunchKernelGGL((k_fused<2, 1, false, false, false, IO, 0>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((k_fused<1, 1, false, false, false, IO, 0>), grid, block, 0, s, a);
-}
+// Every launcher below: the template key from the arguments, the family's predicate (next to its kernel) asked once
+// at run time -- no instance, no launch: hipErrorInvalidValue -- then pick_key under the same predicate and ONE launch
+// statement.
+static constexpr dim3 block_tpb() { return dim3(TPB); }
 
 int gradw_tail_blocks(int D, int F, bool bias) {
   return ((D + DT - 1) / DT) * ((F + GWT_BINS - 1) / GWT_BINS + (bias ? 1 : 0));
 }
 
 hipError_t launch_fused(const DecimArgs& a, int nb, int mode, hipStream_t s, int io, int oio) {
-  if (!io_instance(a, io) || (io != 0 && ((mode != 0 && mode != 1) || a.n_cons > 0))) return hipErrorInvalidValue;
-  const bool mixed = oio >= 0 && oio != io;
-  if (mixed && (io == 0 || oio != 0 || mode != 1)) return hipErrorInvalidValue;
+  const bool pad = a.g.R < a.g.N, acc = a.accumulate && a.out != nullptr;
+  const bool drop = a.drop_thr != 0;     // mode 0: on the stored tile, mode 1: on the loaded tile
+  if (oio < 0) oio = io;
+  if (!fused_instance(nb, mode, drop, acc, pad, io, oio) || (io != 0 && (a.accumulate || a.n_cons > 0)))
+    return hipErrorInvalidValue;         // (2-byte rows: no band groups, no folded parameter-gradient reduction)
   const int total = n_wg(a);
   return for_rounds(a, total, [&](const DecimArgs& r, dim3 grid) {
     // the reduction workgroups ride behind the LAST round's transform workgroups
     if (r.n_cons > 0 && r.bid0 + (int)grid.x >= total) grid.x += r.n_cons;
-    if (r.accumulate && r.out != nullptr) launch_fused_acc(r, mode, grid, s);
-    else if (mixed && io == 1) launch_fused_mixed<1>(r, nb, grid, s);
-    else if (mixed) launch_fused_mixed<2>(r, nb, grid, s);
-    else if (io == 1) launch_fused_nb<1>(r, nb, mode, grid, s);
-    else if (io == 2) launch_fused_nb<2>(r, nb, mode, grid, s);
-    else launch_fused_nb<0>(r, nb, mode, grid, s);
+    pick_key([&](auto NB, auto MODE, auto DROP, auto ACC, auto PAD, auto IO, auto OIO) {
+      if constexpr (fused_instance(SMX_KEY(NB), SMX_KEY(MODE), SMX_KEY(DROP), SMX_KEY(ACC), SMX_KEY(PAD), SMX_KEY(IO), SMX_KEY(OIO)))
+        SMX_LAUNCH((k_fused<SMX_KEY(NB), SMX_KEY(MODE), SMX_KEY(DROP), SMX_KEY(ACC), SMX_KEY(PAD), SMX_KEY(IO), SMX_KEY(OIO)>), grid, block_tpb(), s, r);
+      return true;
+    }, among<1, 2, 4>{nb}, among<0, 1, 2>{mode}, flag{drop}, flag{acc}, flag{pad}, among<0, 1, 2>{io}, among<0, 1, 2>{oio});
   }, nb == 4);
 }
 
-template <int NB, bool PAD>
-static void launch_fused16_t(const DecimArgs& r, int mode, dim3 grid, hipStream_t s) {
-  const dim3 block(TPB);
-  if (mode == 0) hipLaunchKernelGGL((k_fused16<NB, 0, PAD>), grid, block, 0, s, r);
-  else if (mode == 1) hipLaunchKernelGGL((k_fused16<NB, 1, PAD>), grid, block, 0, s, r);
-  else hipLaunchKernelGGL((k_fused16<NB, 2, PAD>), grid, block, 0, s, r);
-}
-template <int NB>
-static void launch_fused16_drop(const DecimArgs& r, int mode, dim3 grid, hipStream_t s) {      // never with padded rows
-  const dim3 block(TPB);
-  if (mode == 0) hipLaunchKernelGGL((k_fused16<NB, 0, false, true>), grid, block, 0, s, r);
-  else hipLaunchKernelGGL((k_fused16<NB, 1, false, true>), grid, block, 0, s, r);
-}
 hipError_t launch_fused16(const DecimArgs& a, int nb, int mode, hipStream_t s) {
+  const bool pad = a.g.R < a.g.N, drop = a.drop_thr != 0 && mode != 2;      // (mode 2 stores and loads no rows to mask)
+  if (!fused16_instance(nb, mode, pad, drop)) return hipErrorInvalidValue;
   return for_rounds(a, n_wg(a), [&](const DecimArgs& r, dim3 grid) {
-    const bool pad = r.g.R < r.g.N;
-    if (r.drop_thr != 0 && mode != 2) {
-      if (nb == 2) launch_fused16_drop<2>(r, mode, grid, s); else launch_fused16_drop<1>(r, mode, grid, s);
-    } else if (nb == 2) { if (pad) launch_fused16_t<2, true>(r, mode, grid, s); else launch_fused16_t<2, false>(r, mode, grid, s); }
-    else if (pad) launch_fused16_t<1, true>(r, mode, grid, s);
-    else launch_fused16_t<1, false>(r, mode, grid, s);
+    pick_key([&](auto NB, auto MODE, auto PAD, auto DROP) {
+      if constexpr (fused16_instance(SMX_KEY(NB), SMX_KEY(MODE), SMX_KEY(PAD), SMX_KEY(DROP)))
+        SMX_LAUNCH((k_fused16<SMX_KEY(NB), SMX_KEY(MODE), SMX_KEY(PAD), SMX_KEY(DROP)>), grid, block_tpb(), s, r);
+      return true;
+    }, among<1, 2>{nb}, among<0, 1, 2>{mode}, flag{pad}, flag{drop});
   });
 }
 // the split launches: drop = apply the dropout mask (A: to the loaded tile, B: to the stored tile)
 hipError_t launch_split16_a(const DecimArgs& a, int nb, bool drop, hipStream_t s) {
+  const bool pad = a.g.R < a.g.N, dr = drop && a.drop_thr != 0;
+  if (!split16_instance(nb, pad, dr)) return hipErrorInvalidValue;
   return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
-    const dim3 block(TPB);
-    const bool pad = r.g.R < r.g.N, dr = drop && r.drop_thr != 0;
-    if (nb == 2) {
-      if (dr) hipLaunchKernelGGL((k_split16_a<2, false, true>), grid, block, 0, s, r);
-      else if (pad) hipLaunchKernelGGL((k_split16_a<2, true>), grid, block, 0, s, r);
-      else hipLaunchKernelGGL((k_split16_a<2>), grid, block, 0, s, r);
-    } else if (dr) hipLaunchKernelGGL((k_split16_a<1, false, true>), grid, block, 0, s, r);
-    else if (pad) hipLaunchKernelGGL((k_split16_a<1, true>), grid, block, 0, s, r);
-    else hipLaunchKernelGGL((k_split16_a<1>), grid, block, 0, s, r);
+    pick_key([&](auto NB, auto PAD, auto DROP) {
+      if constexpr (split16_instance(SMX_KEY(NB), SMX_KEY(PAD), SMX_KEY(DROP)))
+        SMX_LAUNCH((k_split16_a<SMX_KEY(NB), SMX_KEY(PAD), SMX_KEY(DROP)>), grid, block_tpb(), s, r);
+      return true;
+    }, among<1, 2>{nb}, flag{pad}, flag{dr});
   });
 }
 hipError_t launch_split16_b(const DecimArgs& a, int nb, bool drop, hipStream_t s) {
+  const bool pad = a.g.R < a.g.N, dr = drop && a.drop_thr != 0;
+  if (!split16_instance(nb, pad, dr)) return hipErrorInvalidValue;
   return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
-    const dim3 block(TPB);
-    const bool pad = r.g.R < r.g.N, dr = drop && r.drop_thr != 0;
-    if (nb == 2) {
-      if (dr) hipLaunchKernelGGL((k_split16_b<2, false, true>), grid, block, 0, s, r);
-      else if (pad) hipLaunchKernelGGL((k_split16_b<2, true>), grid, block, 0, s, r);
-      else hipLaunchKernelGGL((k_split16_b<2>), grid, block, 0, s, r);
-    } else if (dr) hipLaunchKernelGGL((k_split16_b<1, false, true>), grid, block, 0, s, r);
-    else if (pad) hipLaunchKernelGGL((k_split16_b<1, true>), grid, block, 0, s, r);
-    else hipLaunchKernelGGL((k_split16_b<1>), grid, block, 0, s, r);
+    pick_key([&](auto NB, auto PAD, auto DROP) {
+      if constexpr (split16_instance(SMX_KEY(NB), SMX_KEY(PAD), SMX_KEY(DROP)))
+        SMX_LAUNCH((k_split16_b<SMX_KEY(NB), SMX_KEY(PAD), SMX_KEY(DROP)>), grid, block_tpb(), s, r);
+      return true;
+    }, among<1, 2>{nb}, flag{pad}, flag{dr});
   });
 }
 
 hipError_t launch_synth(const DecimArgs& a, int nb, hipStream_t s) {
+  if (!among<1, 2, 4>::has(nb)) return hipErrorInvalidValue;
   return for_rounds(a, n_wg(a), [&](const DecimArgs& r, dim3 grid) {
-    const dim3 block(TPB);
-    const bool pad = r.g.R < r.g.N;
-    if (nb == 4 && pad) hipLaunchKernelGGL((k_synth<4, true>), grid, block, 0, s, r);
-    else if (nb == 4) hipLaunchKernelGGL((k_synth<4, false>), grid, block, 0, s, r);
-    else if (nb == 2 && pad) hipLaunchKernelGGL((k_synth<2, true>), grid, block, 0, s, r);
-    else if (nb == 2) hipLaunchKernelGGL((k_synth<2, false>), grid, block, 0, s, r);
-    else if (pad) hipLaunchKernelGGL((k_synth<1, true>), grid, block, 0, s, r);
-    else hipLaunchKernelGGL((k_synth<1, false>), grid, block, 0, s, r);
+    pick_key([&](auto NB, auto PAD) {
+      SMX_LAUNCH((k_synth<SMX_KEY(NB), SMX_KEY(PAD)>), grid, block_tpb(), s, r);
+      return true;
+    }, among<1, 2, 4>{nb}, flag{r.g.R < r.g.N});
   }, nb == 4);
 }
 
 hipError_t launch_synth8(const DecimArgs& a, hipStream_t s) {
   DecimArgs r = a;
   r.bid0 = 0;
-  if (a.g.R < a.g.N) hipLaunchKernelGGL((k_synth8<true>), dim3(n_wg(a)), dim3(TPB), 0, s, r);
-  else hipLaunchKernelGGL((k_synth8<false>), dim3(n_wg(a)), dim3(TPB), 0, s, r);
-  return hipGetLastError();
+  pick_bool(a.g.R < a.g.N, [&](auto PAD) {
+    SMX_LAUNCH((k_synth8<SMX_KEY(PAD)>), dim3(n_wg(a)), block_tpb(), s, r);
+    return true;
+  });
+  return launch_status();
 }
 
 hipError_t launch_full8(const DecimArgs& a, int mode, hipStream_t s) {
   DecimArgs r = a;
   r.bid0 = 0;
-  const dim3 grid(n_wg(a)), block(TPB);
-  const bool pad = a.g.R < a.g.N;
-  if (mode == 0 && pad) hipLaunchKernelGGL((k_full8<0, true>), grid, block, 0, s, r);
-  else if (mode == 0) hipLaunchKernelGGL((k_full8<0, false>), grid, block, 0, s, r);
-  else if (mode == 1 && pad) hipLaunchKernelGGL((k_full8<1, true>), grid, block, 0, s, r);
-  else if (mode == 1) hipLaunchKernelGGL((k_full8<1, false>), grid, block, 0, s, r);
-  else if (pad) hipLaunchKernelGGL((k_full8<2, true>), grid, block, 0, s, r);
-  else hipLaunchKernelGGL((k_full8<2, false>), grid, block, 0, s, r);
-  return hipGetLastError();
+  const bool ok = pick_key([&](auto MODE, auto PAD) {
+    SMX_LAUNCH((k_full8<SMX_KEY(MODE), SMX_KEY(PAD)>), dim3(n_wg(a)), block_tpb(), s, r);
+    return true;
+  }, among<0, 1, 2>{mode}, flag{a.g.R < a.g.N});
+  return ok ? launch_status() : hipErrorInvalidValue;
 }
 
-template <int IO>
-static void launch_fused_block_t(const DecimArgs& r, int nb, dim3 grid, hipStream_t s) {
-  const dim3 block(TPB);
-  if (r.drop_thr != 0) {
-    if (nb == 4) hipLaunchKernelGGL((k_fused_blk<4, true, IO>), grid, block, 0, s, r);
-    else if (nb == 2) hipLaunchKernelGGL((k_fused_blk<2, true, IO>), grid, block, 0, s, r);
-    else hipLaunchKernelGGL((k_fused_blk<1, true, IO>), grid, block, 0, s, r);
-  } else if (nb == 4) hipLaunchKernelGGL((k_fused_blk<4, false, IO>), grid, block, 0, s, r);
-  else if (nb == 2) hipLaunchKernelGGL((k_fused_blk<2, false, IO>), grid, block, 0, s, r);
-  else hipLaunchKernelGGL((k_fused_blk<1, false, IO>), grid, block, 0, s, r);
-}
 hipError_t launch_fused_block(const DecimArgs& a, int nb, hipStream_t s, int io) {
-  if (!io_instance(a, io)) return hipErrorInvalidValue;
+  const bool drop = a.drop_thr != 0;
+  // (the kernel serves neither zero-padded rows nor accumulating band groups; the block plan has neither)
+  if (a.g.R < a.g.N || a.accumulate || !among<1, 2, 4>::has(nb) || !among<0, 1, 2>::has(io)) return hipErrorInvalidValue;
   return for_rounds(a, n_wg(a), [&](const DecimArgs& r, dim3 grid) {
-    if (io == 1) launch_fused_block_t<1>(r, nb, grid, s);
-    else if (io == 2) launch_fused_block_t<2>(r, nb, grid, s);
-    else launch_fused_block_t<0>(r, nb, grid, s);
+    pick_key([&](auto NB, auto DROP, auto IO) {
+      SMX_LAUNCH((k_fused_blk<SMX_KEY(NB), SMX_KEY(DROP), SMX_KEY(IO)>), grid, block_tpb(), s, r);
+      return true;
+    }, among<1, 2, 4>{nb}, flag{drop}, among<0, 1, 2>{io});
   }, nb == 4);
 }
 
-template <int IO>
-static void launch_split_a_t(const DecimArgs& r, int nb, bool drop_in, dim3 grid, hipStream_t s) {
-  const dim3 block(TPB);
-  if constexpr (IO == 0) {
-    if (r.g.R < r.g.N) {
-      if (nb == 4) hipLaunchKernelGGL((k_split_a<4, false, true>), grid, block, 0, s, r);
-      else if (nb == 2) hipLaunchKernelGGL((k_split_a<2, false, true>), grid, block, 0, s, r);
-      else hipLaunchKernelGGL((k_split_a<1, false, true>), grid, block, 0, s, r);
-      return;
-    }
-  }
-  if (drop_in && r.drop_thr != 0) {
-    if (nb == 4) hipLaunchKernelGGL((k_split_a<4, true, false, IO>), grid, block, 0, s, r);
-    else if (nb == 2) hipLaunchKernelGGL((k_split_a<2, true, false, IO>), grid, block, 0, s, r);
-    else hipLaunchKernelGGL((k_split_a<1, true, false, IO>), grid, block, 0, s, r);
-  } else if (nb == 4) hipLaunchKernelGGL((k_split_a<4, false, false, IO>), grid, block, 0, s, r);
-  else if (nb == 2) hipLaunchKernelGGL((k_split_a<2, false, false, IO>), grid, block, 0, s, r);
-  else hipLaunchKernelGGL((k_split_a<1, false, false, IO>), grid, block, 0, s, r);
-}
 hipError_t launch_split_a(const DecimArgs& a, int nb, bool drop_in, hipStream_t s, int io) {
-  if (!io_instance(a, io)) return hipErrorInvalidValue;
+  const bool pad = a.g.R < a.g.N, drop = drop_in && a.drop_thr != 0;
+  if (!split_a_instance(nb, drop, pad, io) || (io != 0 && a.accumulate)) return hipErrorInvalidValue;
   return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
-    if (io == 1) launch_split_a_t<1>(r, nb, drop_in, grid, s);
-    else if (io == 2) launch_split_a_t<2>(r, nb, drop_in, grid, s);
-    else launch_split_a_t<0>(r, nb, drop_in, grid, s);
+    pick_key([&](auto NB, auto DROP, auto PAD, auto IO) {
+      if constexpr (split_a_instance(SMX_KEY(NB), SMX_KEY(DROP), SMX_KEY(PAD), SMX_KEY(IO)))
+        SMX_LAUNCH((k_split_a<SMX_KEY(NB), SMX_KEY(DROP), SMX_KEY(PAD), SMX_KEY(IO)>), grid, block_tpb(), s, r);
+      return true;
+    }, among<1, 2, 4>{nb}, flag{drop}, flag{pad}, among<0, 1, 2>{io});
   });
 }
 
 hipError_t launch_split_f(const DecimArgs& a, int nb, int mode, hipStream_t s) {
-  if (!a.sum_in_f) {
-    dim3 gs(n_wg(a) * 16 * nb);
-    if (nb == 1) hipLaunchKernelGGL((k_split_sum<1>), gs, dim3(TPB), 0, s, a);
-    else if (nb == 2) hipLaunchKernelGGL((k_split_sum<2>), gs, dim3(TPB), 0, s, a);
-    else hipLaunchKernelGGL((k_split_sum<4>), gs, dim3(TPB), 0, s, a);
-  }
-  dim3 grid(n_wg(a)), block(TPB);
-  if (nb == 4) {
-    if (mode == 0) hipLaunchKernelGGL((k_split_f<4, 0>), grid, block, 0, s, a);
-    else if (mode == 1) hipLaunchKernelGGL((k_split_f<4, 1>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_split_f<4, 2>), grid, block, 0, s, a);
-    return hipGetLastError();
-  }
-  if (nb == 1 && mode == 0) hipLaunchKernelGGL((k_split_f<1, 0>), grid, block, 0, s, a);
-  else if (nb == 1 && mode == 1) hipLaunchKernelGGL((k_split_f<1, 1>), grid, block, 0, s, a);
-  else if (nb == 1) hipLaunchKernelGGL((k_split_f<1, 2>), grid, block, 0, s, a);
-  else if (mode == 0) hipLaunchKernelGGL((k_split_f<2, 0>), grid, block, 0, s, a);
-  else if (mode == 1) hipLaunchKernelGGL((k_split_f<2, 1>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((k_split_f<2, 2>), grid, block, 0, s, a);
-  return hipGetLastError();
+  if (!among<1, 2, 4>::has(nb) || !among<0, 1, 2>::has(mode)) return hipErrorInvalidValue;
+  if (!a.sum_in_f)
+    pick<1, 2, 4>(nb, [&](auto NB) {
+      SMX_LAUNCH((k_split_sum<SMX_KEY(NB)>), dim3(n_wg(a) * 16 * nb), block_tpb(), s, a);
+      return true;
+    });
+  pick_key([&](auto NB, auto MODE) {
+    SMX_LAUNCH((k_split_f<SMX_KEY(NB), SMX_KEY(MODE)>), dim3(n_wg(a)), block_tpb(), s, a);
+    return true;
+  }, among<1, 2, 4>{nb}, among<0, 1, 2>{mode});
+  return launch_status();
 }
 
-template <int IO>
-static void launch_split_b_t(const DecimArgs& r, int nb, bool drop_out, dim3 grid, hipStream_t s) {
-  const dim3 block(TPB);
-  if constexpr (IO == 0) {
-    if (r.g.R < r.g.N) {
-      if (r.accumulate) hipLaunchKernelGGL((k_split_b<4, false, true, true>), grid, block, 0, s, r);
-      else if (nb == 1) hipLaunchKernelGGL((k_split_b<1, false, false, true>), grid, block, 0, s, r);
-      else if (nb == 2) hipLaunchKernelGGL((k_split_b<2, false, false, true>), grid, block, 0, s, r);
-      else hipLaunchKernelGGL((k_split_b<4, false, false, true>), grid, block, 0, s, r);
-      return;
-    }
-    if (r.accumulate) { hipLaunchKernelGGL((k_split_b<4, false, true>), grid, block, 0, s, r); return; }
-  }
-  if (drop_out && r.drop_thr != 0) {
-    if (nb == 1) hipLaunchKernelGGL((k_split_b<1, true, false, false, IO>), grid, block, 0, s, r);
-    else if (nb == 2) hipLaunchKernelGGL((k_split_b<2, true, false, false, IO>), grid, block, 0, s, r);
-    else hipLaunchKernelGGL((k_split_b<4, true, false, false, IO>), grid, block, 0, s, r);
-  } else if (nb == 1) hipLaunchKernelGGL((k_split_b<1, false, false, false, IO>), grid, block, 0, s, r);
-  else if (nb == 2) hipLaunchKernelGGL((k_split_b<2, false, false, false, IO>), grid, block, 0, s, r);
-  else hipLaunchKernelGGL((k_split_b<4, false, false, false, IO>), grid, block, 0, s, r);
-}
 hipError_t launch_split_b(const DecimArgs& a, int nb, bool drop_out, hipStream_t s, int io) {
-  if (!io_instance(a, io)) return hipErrorInvalidValue;
+  const bool pad = a.g.R < a.g.N, acc = a.accumulate != 0, drop = drop_out && a.drop_thr != 0;
+  if (!split_b_instance(nb, drop, acc, pad, io)) return hipErrorInvalidValue;
   return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
-    if (io == 1) launch_split_b_t<1>(r, nb, drop_out, grid, s);
-    else if (io == 2) launch_split_b_t<2>(r, nb, drop_out, grid, s);
-    else launch_split_b_t<0>(r, nb, drop_out, grid, s);
+    pick_key([&](auto NB, auto DROP, auto ACC, auto PAD, auto IO) {
+      if constexpr (split_b_instance(SMX_KEY(NB), SMX_KEY(DROP), SMX_KEY(ACC), SMX_KEY(PAD), SMX_KEY(IO)))
+        SMX_LAUNCH((k_split_b<SMX_KEY(NB), SMX_KEY(DROP), SMX_KEY(ACC), SMX_KEY(PAD), SMX_KEY(IO)>), grid, block_tpb(), s, r);
+      return true;
+    }, among<1, 2, 4>{nb}, flag{drop}, flag{acc}, flag{pad}, among<0, 1, 2>{io});
   });
 }
 

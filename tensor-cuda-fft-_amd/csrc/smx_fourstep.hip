@@ -90,6 +90,7 @@ __global__ __launch_bounds__(TPB) void k_fs_synth(const DecimArgs a) {
 // Backward with the slab summed over batch groups (option "fs_bgroups", off by default -- measured slower):
 // blockIdx.x = d-tile + ndt * batch group; one thread walks the group's batch rows and keeps the sums of its
 // slab rows in registers (4 L floats).  A kernel of its own so that k_fs_f<L, 1> stays lean.
+// (instances: fs_grouped_tiles, smx_kernels.h)
 template <int L>
 __global__ __launch_bounds__(TPB) void k_fs_f_grouped(const DecimArgs a) {
   __shared__ cf red[TPB];
@@ -283,17 +284,6 @@ __global__ __launch_bounds__(TPB) void k_fs_conv_big(const DecimArgs a) {
   }
 }
 
-template <int L>
-static void launch_fs_conv_t(const DecimArgs& a, int dir, dim3 grid, hipStream_t s) {
-  if (dir == 0) hipLaunchKernelGGL((k_fs_conv<L, 0>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((k_fs_conv<L, 1>), grid, dim3(TPB), 0, s, a);
-}
-template <int L2>
-static void launch_fs_conv_big_t(const DecimArgs& a, int dir, hipStream_t s) {
-  const dim3 grid(n_wg(a), (129 + 16 / L2 - 1) / (16 / L2));
-  if (dir == 0) hipLaunchKernelGGL((k_fs_conv_big<L2, 0>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((k_fs_conv_big<L2, 1>), grid, dim3(TPB), 0, s, a);
-}
 int conv_column_blocks(int L) { return L >= 32 ? (129 + 16 / (L / 16) - 1) / (16 / (L / 16)) : 9; }
 
 // Both reductions behind a backward column launch in ONE launch (round 3: three launches before -- two stages of the P
@@ -360,101 +350,80 @@ hipError_t launch_conv_reduce(const DecimArgs& a, float* gh_re, float* gh_im, fl
   const long long total = grad_scale ? (long long)nwg * nj : 0;
   const int nbr = (int)((total + 255) / 256);
   if (nbh + nbr == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_conv_grads, dim3(nbh + nbr), dim3(256), 0, s, a.ca.p_part, nwg, a.g.N, gh_re, gh_im, nbh,
+  SMX_LAUNCH(k_conv_grads, dim3(nbh + nbr), dim3(256), s, a.ca.p_part, nwg, a.g.N, gh_re, gh_im, nbh,
                      a.ca.r_part, grad_scale, a.g.B, a.g.D, rscale, ny, nj);
-  return hipGetLastError();
+  return launch_status();
 }
 
+// k_fs_conv<L, DIR> / k_fs_conv_big<L2, DIR>: every tile count of conv_one_level / conv_level2 (smx_kernels.h), both DIR
 hipError_t launch_fs_conv(const DecimArgs& a, int dir, float* gh_re, float* gh_im, float* grad_scale,
                           hipStream_t s) {
-  const dim3 grid(n_wg(a), 9);
-  switch (a.g.L) {
-    case 32: launch_fs_conv_big_t<2>(a, dir, s); break;
-    case 64: launch_fs_conv_big_t<4>(a, dir, s); break;
-    case 128: launch_fs_conv_big_t<8>(a, dir, s); break;
-    case 256: launch_fs_conv_big_t<16>(a, dir, s); break;
-#define SMX_FS_CASE(LL) case LL: launch_fs_conv_t<LL>(a, dir, grid, s); break;
-    SMX_FS_CASE(2) SMX_FS_CASE(4) SMX_FS_CASE(8) SMX_FS_CASE(16)     // (L = 32 was measured: 512 registers +
-#undef SMX_FS_CASE                                                     //  116 spills in backward, no faster than k_fs_f)
-    default: return hipErrorInvalidValue;
-  }
-  if (dir == 1) return launch_conv_reduce(a, gh_re, gh_im, grad_scale, conv_column_blocks(a.g.L), 0.5f * a.g.inv_n, s);
-  return hipGetLastError();
+  const int L = a.g.L;
+  if (!conv_tiles(L)) return hipErrorInvalidValue;
+  const dim3 grid(n_wg(a), conv_column_blocks(L));
+  const bool ok = conv_two_level(L)
+      ? pick_key([&](auto L2, auto DIR) {
+          SMX_LAUNCH((k_fs_conv_big<SMX_KEY(L2), SMX_KEY(DIR)>), grid, dim3(TPB), s, a);
+          return true;
+        }, conv_level2{L / 16}, among<0, 1>{dir})
+      : pick_key([&](auto LL, auto DIR) {
+          SMX_LAUNCH((k_fs_conv<SMX_KEY(LL), SMX_KEY(DIR)>), grid, dim3(TPB), s, a);
+          return true;
+        }, conv_one_level{L}, among<0, 1>{dir});
+  if (!ok) return hipErrorInvalidValue;
+  if (dir == 1) return launch_conv_reduce(a, gh_re, gh_im, grad_scale, conv_column_blocks(L), 0.5f * a.g.inv_n, s);
+  return launch_status();
 }
 
 hipError_t launch_fs_a(const DecimArgs& a, hipStream_t s) {
   return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
-    if (r.g.R < r.g.N) hipLaunchKernelGGL((k_fs_a<true>), grid, dim3(TPB), 0, s, r);
-    else hipLaunchKernelGGL((k_fs_a<false>), grid, dim3(TPB), 0, s, r);
+    pick_bool(r.g.R < r.g.N, [&](auto PAD) { SMX_LAUNCH((k_fs_a<SMX_KEY(PAD)>), grid, dim3(TPB), s, r); return true; });
   });
 }
 hipError_t launch_fs_b(const DecimArgs& a, hipStream_t s) {
   return for_rounds(a, n_wg(a) * a.nsplit, [&](const DecimArgs& r, dim3 grid) {
-    if (r.g.R < r.g.N) hipLaunchKernelGGL((k_fs_b<true>), grid, dim3(TPB), 0, s, r);
-    else hipLaunchKernelGGL((k_fs_b<false>), grid, dim3(TPB), 0, s, r);
+    pick_bool(r.g.R < r.g.N, [&](auto PAD) { SMX_LAUNCH((k_fs_b<SMX_KEY(PAD)>), grid, dim3(TPB), s, r); return true; });
   });
 }
-template <int L>
-static void launch_fs_f_t(const DecimArgs& a, int mode, dim3 grid, hipStream_t s) {
-  if (mode == 0) hipLaunchKernelGGL((k_fs_f<L, 0>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 1 && a.fs_bgroups > 0) {
-    if constexpr (L >= 5 && L <= 16) hipLaunchKernelGGL((k_fs_f_grouped<L>), grid, dim3(TPB), 0, s, a);
-  } else if (mode == 1) hipLaunchKernelGGL((k_fs_f<L, 1>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 2) hipLaunchKernelGGL((k_fs_f<L, 2>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 4) hipLaunchKernelGGL((k_fs_synth<L>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((k_fs_f<L, 3>), grid, dim3(TPB), 0, s, a);
-}
-// L = L1 L2 on the two-level columns: L2 threads per column pair (a divisor of 16), first-level length L1 <= 16.
-// 64 / 128 / 256 = 16 x 4 / 8 / 16 (round 2); round 3: L1 = 9 ... 15 with the smallest L2 in {4, 8, 16} that fits.
-bool fs_two_level(int L, int* L1, int* L2) {
-  for (int l2 = 4; l2 <= 16; l2 *= 2)
-    if (L % l2 == 0 && L / l2 >= 9 && L / l2 <= 16) { *L1 = L / l2; *L2 = l2; return true; }
-  return false;
-}
+
 int fs_column_blocks(int L) {
-  int l1, l2;
-  if (L >= 33 && fs_two_level(L, &l1, &l2)) return (129 + 16 / l2 - 1) / (16 / l2);
-  return 9;
+  int l1 = 0, l2 = 0;
+  return fs_two_level(L, &l1, &l2) ? (129 + 16 / l2 - 1) / (16 / l2) : 9;
 }
 
+// The column launch.  One thread per column (fs_one_level): k_fs_f<L, MODE> for modes 0 ... 3, k_fs_synth<L> for mode 4,
+// every L of the list; k_fs_f_grouped<L> (mode 1 with fs_bgroups) for fs_grouped_tiles.  L = L1 L2 on the two-level
+// columns (fs_two_level, smx_kernels.h): k_fs_big with L1 = 16 here (64 / 128 / 256 = 16 x 4 / 8 / 16, round 2), with
+// L1 = 9 ... 15 in smx_fourstep2.hip (round 3).  Three kernel templates, so three launch statements.
 hipError_t launch_fs_f(const DecimArgs& a, int mode, hipStream_t s) {
-  const int ndt = (a.g.D + DT - 1) / DT;
+  const int L = a.g.L, ndt = (a.g.D + DT - 1) / DT;
   int l1 = 0, l2 = 0;
-  if (a.g.L >= 33 && fs_two_level(a.g.L, &l1, &l2)) {
-    if (l1 == 16) {
-      if (l2 == 4) launch_fs_big_t<4>(a, mode, s);
-      else if (l2 == 8) launch_fs_big_t<8>(a, mode, s);
-      else launch_fs_big_t<16>(a, mode, s);
-    } else {
-      if (hipError_t e = launch_fs_big_general(a, mode, l1, l2, s)) return e;
-    }
-    if (mode == 1 && a.fa.gsc_part && a.fa.gsc) {
-      const long long total = (long long)n_wg(a) * 16;
-      hipLaunchKernelGGL(k_fs_gsc, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.fa.gsc_part, a.fa.gsc,
-                         a.g.B, a.g.D, fs_column_blocks(a.g.L));
-    }
-    return hipGetLastError();
-  }
-  const bool grouped = mode == 1 && a.fs_bgroups > 0 && a.g.L >= 5 && a.g.L <= 16;
-  const dim3 grid(grouped ? ndt * a.fs_bgroups : n_wg(a), 9);
-  switch (a.g.L) {
-#define SMX_FS_CASE(LL) case LL: launch_fs_f_t<LL>(a, mode, grid, s); break;
-    SMX_FS_CASE(2) SMX_FS_CASE(4)          // complex sequence FFT only (filter plans start at L = 5)
-    SMX_FS_CASE(5) SMX_FS_CASE(6) SMX_FS_CASE(7) SMX_FS_CASE(8) SMX_FS_CASE(9) SMX_FS_CASE(10) SMX_FS_CASE(11)
-    SMX_FS_CASE(12) SMX_FS_CASE(13) SMX_FS_CASE(14) SMX_FS_CASE(15) SMX_FS_CASE(16) SMX_FS_CASE(32)
-    SMX_FS_CASE(18) SMX_FS_CASE(20) SMX_FS_CASE(22) SMX_FS_CASE(24) SMX_FS_CASE(26) SMX_FS_CASE(28) SMX_FS_CASE(30)
-    // odd tile counts 17 ... 31 (round 3): the L x L product in one thread's registers, as for the odd L <= 15
-    SMX_FS_CASE(17) SMX_FS_CASE(19) SMX_FS_CASE(21) SMX_FS_CASE(23) SMX_FS_CASE(25) SMX_FS_CASE(27) SMX_FS_CASE(29)
-    SMX_FS_CASE(31)
-#undef SMX_FS_CASE
-    default: return hipErrorInvalidValue;
+  if (fs_two_level(L, &l1, &l2)) {
+    if (hipError_t e = l1 == 16 ? launch_fs_big<16>(a, mode, l1, l2, s) : launch_fs_big_general(a, mode, l1, l2, s))
+      return e;
+  } else {
+    const dim3 grid(n_wg(a), 9), block(TPB);
+    bool ok;
+    if (mode == 1 && a.fs_bgroups > 0)       // slab rows summed over fs_bgroups batch groups inside the launch
+      ok = pick_key([&](auto LL) {
+        SMX_LAUNCH((k_fs_f_grouped<SMX_KEY(LL)>), dim3(ndt * a.fs_bgroups, 9), block, s, a);
+        return true;
+      }, fs_grouped_tiles{L});
+    else if (mode == 4)
+      ok = pick_key([&](auto LL) { SMX_LAUNCH((k_fs_synth<SMX_KEY(LL)>), grid, block, s, a); return true; }, fs_one_level{L});
+    else
+      ok = pick_key([&](auto LL, auto MODE) {
+        SMX_LAUNCH((k_fs_f<SMX_KEY(LL), SMX_KEY(MODE)>), grid, block, s, a);
+        return true;
+      }, fs_one_level{L}, among<0, 1, 2, 3>{mode});
+    if (!ok) return hipErrorInvalidValue;
   }
   if (mode == 1 && a.fa.gsc_part && a.fa.gsc) {
     const long long total = (long long)n_wg(a) * 16;
-    hipLaunchKernelGGL(k_fs_gsc, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.fa.gsc_part, a.fa.gsc,
-                       a.g.B, a.g.D, 9);
+    SMX_LAUNCH(k_fs_gsc, dim3((unsigned)((total + 255) / 256)), dim3(256), s, a.fa.gsc_part, a.fa.gsc, a.g.B, a.g.D,
+               fs_column_blocks(L));
   }
-  return hipGetLastError();
+  return launch_status();
 }
 
 }  // namespace smx

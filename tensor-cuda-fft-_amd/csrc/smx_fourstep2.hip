@@ -11,24 +11,8 @@
 
 namespace smx {
 
-template <int L2>
-static hipError_t launch_general_l2(const DecimArgs& a, int mode, int l1, hipStream_t s) {
-  switch (l1) {
-#define SMX_FS2_CASE(LL) case LL: launch_fs_big_t<L2, LL>(a, mode, s); break;
-    SMX_FS2_CASE(9) SMX_FS2_CASE(10) SMX_FS2_CASE(11) SMX_FS2_CASE(12) SMX_FS2_CASE(13) SMX_FS2_CASE(14) SMX_FS2_CASE(15)
-#undef SMX_FS2_CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_fs_big_general(const DecimArgs& a, int mode, int l1, int l2, hipStream_t s) {
-  switch (l2) {
-    case 4: return launch_general_l2<4>(a, mode, l1, s);
-    case 8: return launch_general_l2<8>(a, mode, l1, s);
-    case 16: return launch_general_l2<16>(a, mode, l1, s);
-    default: return hipErrorInvalidValue;
-  }
+  return launch_fs_big<15, 14, 13, 12, 11, 10, 9>(a, mode, l1, l2, s);      // (last first: smx_fs_big.h)
 }
 
 }  // namespace smx

@@ -74,14 +74,20 @@ __global__ __launch_bounds__(TPB) void k_fs_big(const DecimArgs a) {
   }
 }
 
-template <int L2, int L1 = 16>
-static void launch_fs_big_t(const DecimArgs& a, int mode, hipStream_t s) {
-  const dim3 grid(n_wg(a), (129 + 16 / L2 - 1) / (16 / L2));
-  if (mode == 0) hipLaunchKernelGGL((k_fs_big<L2, 0, L1>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 1) hipLaunchKernelGGL((k_fs_big<L2, 1, L1>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 2) hipLaunchKernelGGL((k_fs_big<L2, 2, L1>), grid, dim3(TPB), 0, s, a);
-  else if (mode == 4) hipLaunchKernelGGL((k_fs_big<L2, 4, L1>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((k_fs_big<L2, 3, L1>), grid, dim3(TPB), 0, s, a);
+// k_fs_big<L2, MODE, L1> for the first-level lengths L1s of the including unit: every (L2, MODE, L1) exists.
+// Every list LAST VALUE FIRST (L2 = fs_level2, L1s likewise): the compiler instantiates what pick's fold names last
+// first, and so the kernels are emitted L2-major, then L1, then mode 0 1 2 4 3 -- the order they have always had in the
+// object.  Another order moves the zero bytes that pad a kernel to the next one's alignment, which a per-kernel
+// comparison of two objects (tools/kdiff.py) reports as a changed kernel.
+template <int... L1s>
+static hipError_t launch_fs_big(const DecimArgs& a, int mode, int l1, int l2, hipStream_t s) {
+  static_assert(fs_level2::has(16) && fs_level2::has(8) && fs_level2::has(4) && !fs_level2::has(2));
+  const bool ok = pick_key([&](auto L2, auto L1, auto MODE) {
+    constexpr int T2 = SMX_KEY(L2);
+    SMX_LAUNCH((k_fs_big<T2, SMX_KEY(MODE), SMX_KEY(L1)>), dim3(n_wg(a), (129 + 16 / T2 - 1) / (16 / T2)), dim3(TPB), s, a);
+    return true;
+  }, among<16, 8, 4>{l2}, among<L1s...>{l1}, among<3, 4, 2, 1, 0>{mode});
+  return ok ? launch_status() : hipErrorInvalidValue;
 }
 
 }  // namespace smx

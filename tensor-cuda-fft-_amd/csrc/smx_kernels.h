@@ -5,6 +5,42 @@
 
 namespace smx {
 
+// ---- supported-value sets, stated once: the plans (smx_api.hip) ask has(), the launchers pick from the same list --------
+// among<Vs...>{v}: a run-time value that selects a template argument from Vs (pick_key, smx_launch.h)
+template <int... Vs>
+struct among {
+  int v;
+  static constexpr bool has(int x) { return ((x == Vs) || ...); }
+};
+struct flag { bool v; };       // ... and one that selects a bool template argument
+// four-step tile counts L = n_fft / 256 whose column transform one thread holds in registers (k_fs_f<L, .>): 2 and 4
+// for the complex sequence FFT alone, the filter plans from FS_FILTER_MIN_L (below it their band kernels are faster)
+using fs_one_level = among<2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28,
+                           29, 30, 31, 32>;
+constexpr int FS_FILTER_MIN_L = 5;
+// ... of them, those whose mode-1 launch can sum the slab rows over batch groups (k_fs_f_grouped<L>, option fs_bgroups)
+using fs_grouped_tiles = among<5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>;
+// two-level columns (k_fs_big<L2, ., L1>): L = L1 L2 with L2 threads per column pair and a first-level length 9 ... 16,
+// the smallest such L2 -- 36 ... 64 step 4, 72 ... 128 step 8, 144 ... 256 step 16
+using fs_level2 = among<4, 8, 16>;
+using fs_level1 = among<9, 10, 11, 12, 13, 14, 15, 16>;
+constexpr bool fs_two_level(int L, int* L1, int* L2) {
+  for (int l2 = 4; l2 <= 16; l2 *= 2)
+    if (fs_level2::has(l2) && L % l2 == 0 && fs_level1::has(L / l2)) { *L1 = L / l2; *L2 = l2; return true; }
+  return false;
+}
+constexpr bool fs_tiles_cfft(int L) { int l1 = 0, l2 = 0; return fs_one_level::has(L) || fs_two_level(L, &l1, &l2); }
+constexpr bool fs_tiles_filter(int L) { return L >= FS_FILTER_MIN_L && fs_tiles_cfft(L); }
+// rank-one filter (launch_fs_conv): columns in one thread's registers (k_fs_conv<L, .>; L = 32 was measured: 512 registers
+// + 116 spills in backward, no faster than k_fs_f), above that L = 16 L2 on the two-level columns (k_fs_conv_big<L2, .>)
+using conv_one_level = among<2, 4, 8, 16>;
+using conv_level2 = among<2, 4, 8, 16>;
+constexpr bool conv_two_level(int L) { return L % 16 == 0 && conv_level2::has(L / 16); }
+constexpr bool conv_tiles(int L) { return conv_one_level::has(L) || conv_two_level(L); }
+// k_conv1<LP, ...>: n_fft = 512 LP
+using conv1_lp = among<1, 2, 4>;
+constexpr bool conv1_length(int N) { return N % 512 == 0 && conv1_lp::has(N / 512); }
+
 struct DecimArgs {
   const float* in;      // x (forward) or g (backward), (B,N,D) f32 -- or 2-byte rows behind the same pointer (io below)
   float* out;           // y or grad_x, (B,N,D) likewise; may be null (spectrum only)
@@ -102,14 +138,13 @@ hipError_t launch_synth(const DecimArgs& a, int nb, hipStream_t s);
 hipError_t launch_synth8(const DecimArgs& a, hipStream_t s);       // N = 2048, every bin: eight bands, one launch
 // full spectrum at N = 2048 (eight bands, L == 8): one launch per direction, no dropout / residue split
 hipError_t launch_full8(const DecimArgs& a, int mode, hipStream_t s);
-// four-step path (more than 512 bins, L in {5..16, 18..32 even, 64, 128, 256}): tile spectra -> workspace / column filter / inverse
+// four-step path (more than 512 bins at the tile counts of fs_tiles_filter above): tile spectra -> workspace / column
+// filter / inverse
 hipError_t launch_fs_a(const DecimArgs& a, hipStream_t s);
 hipError_t launch_fs_f(const DecimArgs& a, int mode, hipStream_t s);     // mode 4: columns from fa.xk_in (synthesis)
 hipError_t launch_fs_b(const DecimArgs& a, hipStream_t s);
 int conv_column_blocks(int L);      // the same for launch_fs_conv (ConvArgs::r_part)
 int fs_column_blocks(int L);        // grid.y of the column launch = rows of FilterArgs::gsc_part per workgroup
-// two-level columns: L = L1 L2, L2 in {4, 8, 16} threads per column pair, 9 <= L1 <= 16 (L >= 36)
-bool fs_two_level(int L, int* L1, int* L2);
 hipError_t launch_fs_big_general(const DecimArgs& a, int mode, int l1, int l2, hipStream_t s);   // L1 = 9 ... 15
 // rank-one filter (causal convolution of fft_lm) on the four-step path: column launch, dir 0 forward / 1 backward
 // (backward also reduces P -> dL/dH (gh_re, gh_im: N/2 + 1 each) and (R1, R2) -> grad_scale (B, D))
@@ -120,7 +155,7 @@ hipError_t launch_conv_reduce(const DecimArgs& a, float* gh_re, float* gh_im, fl
 // the same filter in ONE launch per direction (smx_conv1.hip): n_fft = 512, 1024, 2048 (rows above n_fft / 2 folded).
 // dir 0: a.ws_f = where the packed spectrum of x is kept for backward (or null); dir 1: a.ca.xs = that spectrum,
 // partial sums as launch_fs_conv with one row of (R1, R2) per workgroup
-bool conv1_supported(int N, int R);
+constexpr bool conv1_supported(int N, int R) { return conv1_length(N) && R >= 1 && R <= N; }
 // nj = channel pairs per workgroup: 16 (512 threads) or 8 (256 threads, two workgroups per CU)
 int conv1_workgroups(int B, int D, int nj);
 // io: element type of a.in / a.out (SMX_IO_*: 0 f32 rows, 1 bf16, 2 fp16 -- 2-byte rows, everything else f32)

@@ -2,6 +2,9 @@
 // the LDS declaration, the workgroup -> work item map and the launch-in-rounds helper.
 #pragma once
 #include <type_traits>
+#ifdef SMX_LAUNCH_TRACE
+#include <typeinfo>
+#endif
 #include "smx_kernels.h"
 
 namespace smx {
@@ -209,6 +212,56 @@ template <bool PAD, int IO> __device__ void store_rows(const RowBufT<IO>& rb, in
 // ---- launch helpers ----------------------------------------------------------------------------
 static inline int n_wg(const DecimArgs& a) { return a.g.B * ((a.g.D + DT - 1) / DT); }
 
+// Run-time values -> template arguments (the spelling of row_dispatch, smx_rows.h).  pick<Vs...>(v, f) calls
+// f(std::integral_constant<int, V>()) for the V == v and hands back what f returns; no such V: false.
+template <int... Vs, class F>
+bool pick(int v, F&& f) {
+  return ((v == Vs && f(std::integral_constant<int, Vs>())) || ...);
+}
+template <class F>
+bool pick_bool(bool v, F&& f) {
+  return v ? f(std::true_type()) : f(std::false_type());
+}
+// A whole template key at once: pick_key(f, among<1, 2, 4>{nb}, among<0, 1, 2>{mode}, flag{pad}) calls f(NB, MODE, PAD)
+// with the constants in that order and returns true; a value outside its list: f is not called, false.  f launches under
+// `if constexpr (<family>_instance(...))`, the constexpr predicate next to the kernel that states which instances exist
+// -- so of the cross product only those are emitted -- and returns true either way: the launcher has asked the same
+// predicate at run time before its first launch (a key without an instance is hipErrorInvalidValue, never a
+// neighbouring instance), so the empty branch is never reached.
+// SMX_KEY(NB) = the constant's value (a parameter of the generic lambda is not a constant expression itself).
+// (among<Vs...>, flag: smx_kernels.h)
+#define SMX_KEY(v) decltype(v)::value
+template <class F>
+bool pick_key(F&& f) { return f(); }
+template <class F, int... Vs, class... Ks>
+bool pick_key(F&& f, among<Vs...> k, Ks... rest);
+template <class F, class... Ks>
+bool pick_key(F&& f, flag k, Ks... rest) {
+  return pick_bool(k.v, [&](auto V) { return pick_key([&](auto... vs) { return f(V, vs...); }, rest...); });
+}
+template <class F, int... Vs, class... Ks>
+bool pick_key(F&& f, among<Vs...> k, Ks... rest) {
+  return pick<Vs...>(k.v, [&](auto V) { return pick_key([&](auto... vs) { return f(V, vs...); }, rest...); });
+}
+
+// The one launch statement of the transform families: SMX_LAUNCH((k_fused<NB, MODE>), grid, block, stream, args...).
+// With SMX_LAUNCH_TRACE defined (tests/launch_trace only, never in build.sh) nothing reaches the HIP runtime: the
+// instance's name, the grid and block, and bid0 of a DecimArgs argument go to trace_launch, which the test program defines.
+#ifdef SMX_LAUNCH_TRACE
+template <auto K> struct KTag {};          // typeid(KTag<K>).name() carries every template argument of K
+void trace_launch(const char* ktag, dim3 grid, dim3 block, const DecimArgs* a);
+template <class A0, class... A>
+const DecimArgs* trace_decim(const A0& a0, const A&...) {
+  if constexpr (std::is_same_v<A0, DecimArgs>) return &a0; else return nullptr;
+}
+#define SMX_LAUNCH(K, grid, block, s, ...) \
+  ::smx::trace_launch(typeid(::smx::KTag<(K)>).name(), grid, block, ::smx::trace_decim(__VA_ARGS__))
+static inline hipError_t launch_status() { return hipSuccess; }
+#else
+#define SMX_LAUNCH(K, grid, block, s, ...) hipLaunchKernelGGL(K, grid, block, 0, s, __VA_ARGS__)
+static inline hipError_t launch_status() { return hipGetLastError(); }
+#endif
+
 // The streaming kernels are launched in rounds of `a.round` workgroups (512 = 2 per CU, all resident):
 // the kernel boundary keeps every round's read phase and write phase chip-wide in step.  One launch of
 // 1024 workgroups lets the second round's reads run into the first round's writes, and mixed traffic is
@@ -222,7 +275,7 @@ static inline hipError_t for_rounds(const DecimArgs& a, int total, F launch, boo
     r.bid0 = b0;
     launch(r, dim3(total - b0 < round ? total - b0 : round));
   }
-  return hipGetLastError();
+  return launch_status();
 }
 
 }  // namespace smx
