@@ -193,18 +193,38 @@ int get_group_bt(int N, int group, cf** out, hipStream_t s) {
 }
 
 // ---- plan ----------------------------------------------------------------------------------------
+// What a shape runs on, resolved once by make_plan (tile_plan for smx_cfft_ex / smx_conv_*):
+enum class Kind {
+  Direct,     // DFT products
+  Sixteen,    // sixteen-row decimation (k_fused16), single launch or tile chunks (nsplit > 1)
+  Single,     // up to 512 bins, one fused launch per direction
+  Split,      // ... its residue-split form (nsplit > 1): three launches through the workspace
+  FourStep,   // k_fs_a / k_fs_f / k_fs_b: more than 512 bins at the tile counts of fs_tiles_filter(); takes precedence
+              // over the eight bands and the band groups (option "fourstep" = 0: off)
+  Full8,      // N = 2048 with k > 512: the eight-band kernel (k_full8) takes every call that runs forward half and
+              // inverse half together; the band groups remain the plan of the phase-split backward (and define the
+              // workspace layout, which must not depend on which of the two a call uses)
+  Groups,     // more than 512 bins elsewhere: one four-band launch per group of 512 bins + the edge kernels
+};
 struct Plan {
+  Kind kind;
   int path, k, L, nb, nsplit, lc, nwg;
   int groups;     // band groups of 512 bins (1 unless k > 512)
   int nedge;      // bins 512, 1024, ... < k: left to the edge kernels when groups > 1
-  bool fs;        // four-step path (k_fs_a / k_fs_f / k_fs_b): more than 512 bins at the tile counts of fs_tiles_filter();
-  int fs_nsplit, fs_lc;   // takes precedence over the band groups and over full8 (option "fourstep" = 0: off)
+  int fs_nsplit, fs_lc;   // four-step: tile chunks per (batch row, d-tile), tiles per chunk
+  bool pair8;     // N = 2048 with k > 512 and option "full8": smx_rfft_ex / smx_irfft_ex run their eight-band launches
   bool conv1 = false;   // smx_conv_*: one launch per direction (k_conv1: n_fft <= 2048)
   int conv1_nj = 16;    // ... channel pairs per workgroup of that launch (16: 512 threads; 8: 256 threads)
-  bool full8;     // N = 2048 with k > 512: the eight-band kernel (k_full8) takes every call that runs
-                  // forward half and inverse half together; the band groups remain the plan of the
-                  // phase-split backward (and define the workspace layout, which must not depend on
-                  // which of the two a call uses)
+  bool fs() const { return kind == Kind::FourStep; }
+  bool full8() const { return kind == Kind::Full8; }
+  bool io_native() const { return kind == Kind::Single || kind == Kind::Split; }       // kernels with 2-byte row I/O
+  bool block_fused() const { return kind == Kind::Single; }                            // k_fused_blk
+  // (row scale: not the eight-band kernel -- it only serves calls that run both halves of the backward together, and a
+  // caller must be able to rely on smx_row_scale_supported for every phase split).  The same kinds synthesise from a
+  // given spectrum (smx_irfft_ex).
+  bool row_scale() const { return io_native() || fs(); }
+  bool wide() const { return fs() || full8() || kind == Kind::Groups; }     // more than 512 bins: no fused dropout mask
+  bool groups_only() const { return kind == Kind::Groups; }                 // no call of this shape leaves the band groups
 };
 
 int check_shape(int B, int N, int D, int F) {
@@ -266,6 +286,27 @@ static int choose_nsplit(int forced, int nwg, int L, double bytes) {
   return ns;
 }
 
+// The four-step tile walk of a decimated plan: one resident round of tile workgroups, as on the split plan.  The
+// residue split is off (the band kernels of a phase-split call on this shape run one launch per group).
+void tile_plan(Plan& p) {
+  p.kind = Kind::FourStep;
+  int ns = 512 / p.nwg;
+  if (ns < 1) ns = 1;
+  if (ns > p.L) ns = p.L;
+  p.fs_lc = (p.L + ns - 1) / ns;
+  p.fs_nsplit = (p.L + p.fs_lc - 1) / p.fs_lc;
+  p.nsplit = 1; p.lc = p.L;
+}
+// ... as the whole plan of the entries that keep every bin of the packed spectrum (smx_cfft_ex, smx_conv_*), which
+// check the tile count themselves
+Plan tile_plan(const Shape& h) {
+  Plan p{};
+  p.path = SMX_PATH_DECIMATED; p.L = h.N / M; p.k = h.N / 2 + 1; p.nb = 4; p.groups = 1;
+  p.nwg = h.B * ((h.D + DT - 1) / DT);
+  tile_plan(p);
+  return p;
+}
+
 Plan make_plan(const Shape& h) {
   const int B = h.B, N = h.N, D = h.D;
   Plan p{};
@@ -281,7 +322,7 @@ Plan make_plan(const Shape& h) {
     // phase-split backward, synthesis alone) -- runs the DFT products of the direct plan on the same workspace
     if (!opt.force_direct && opt.decim16 != 0 && N % 16 == 0 && N % M != 0 && D % 2 == 0 && p.k >= 1 && p.k <= 256 &&
         p.k <= N / 2) {        // (not the Nyquist bin: its two slots +-N/2 would not cancel to an exact +0 imaginary part)
-      p.path = SMX_PATH_DECIM16;
+      p.path = SMX_PATH_DECIM16; p.kind = Kind::Sixteen;
       p.L = (N / 16 + 15) / 16;               // tiles of 16 residues
       p.nb = p.k > 128 ? 2 : 1;
       p.nwg = B * ((D + DT - 1) / DT);
@@ -291,7 +332,7 @@ Plan make_plan(const Shape& h) {
       p.nsplit = (p.L + p.lc - 1) / p.lc;
       return p;
     }
-    p.path = SMX_PATH_DIRECT; p.nsplit = 1; return p;
+    p.path = SMX_PATH_DIRECT; p.kind = Kind::Direct; p.nsplit = 1; return p;
   }
   p.path = SMX_PATH_DECIMATED;
   p.L = N / M;
@@ -302,17 +343,10 @@ Plan make_plan(const Shape& h) {
   p.nb = kb > 256 ? 4 : kb > 128 ? 2 : 1;
   p.nwg = B * ((D + DT - 1) / DT);
   if (kb > 512) {
-    p.full8 = p.L == 8 && opt.full8 != 0;
-    const int fsm = opt.fourstep;
-    p.fs = fsm != 0 && fs_tiles_filter(p.L);
-    if (p.fs) {
-      p.full8 = false;
-      int ns = 512 / p.nwg;                       // one resident round of tile workgroups, as on the split plan
-      if (ns < 1) ns = 1;
-      if (ns > p.L) ns = p.L;
-      p.fs_lc = (p.L + ns - 1) / ns;
-      p.fs_nsplit = (p.L + p.fs_lc - 1) / p.fs_lc;
-    }
+    p.pair8 = p.L == 8 && opt.full8 != 0;
+    p.kind = p.pair8 ? Kind::Full8 : Kind::Groups;
+    p.nsplit = 1; p.lc = p.L;
+    if (opt.fourstep != 0 && fs_tiles_filter(p.L)) tile_plan(p);
     // More than 512 bins: the four-band kernels run once per group of 512 bins (group g: |f| in
     // [512 g, 512 g + 512), its own residue-twiddle table, later groups add to y); the bins that are
     // multiples of 512 pair across groups and go through the literal-DFT kernels instead.  x is read
@@ -320,13 +354,13 @@ Plan make_plan(const Shape& h) {
     // for the direct path.  One fused launch per group (no residue split).
     p.groups = (kb + 511) / 512;
     p.nedge = (p.k - 1) / 512;
-    p.nsplit = 1; p.lc = p.L;
     return p;
   }
   int ns = choose_nsplit(opt.nsplit, p.nwg, p.L, 4.0 * B * (double)h.R * D);
   if (ns > p.L) ns = p.L;
   p.lc = (p.L + ns - 1) / ns;
   p.nsplit = (p.L + p.lc - 1) / p.lc;
+  p.kind = p.nsplit == 1 ? Kind::Single : Kind::Split;
   return p;
 }
 
@@ -376,12 +410,12 @@ Ws ws_layout(const Plan& p, int B, int N, int D) {
       w.edge1 = o; o += e;
       w.edgep = o;
       o += al((size_t)edge_chunks(B, N, D) * B * p.nedge * D * 2 * sizeof(double));
-      if (!p.fs && !p.full8) {   // the group launches re-read their input while the output accumulates: no in-place form
+      if (p.groups_only()) {     // the group launches re-read their input while the output accumulates: no in-place form
         w.rows = o; o += al((size_t)B * N * D * sizeof(float));
       }
     }
     w.wt = o; o += al((size_t)p.k * D * sizeof(cf));
-    if (p.fs) {
+    if (p.fs()) {
       w.fs = o; o += al((size_t)p.nwg * p.L * EX * sizeof(cf));
       w.gscp = o; o += al((size_t)p.nwg * fs_column_blocks(p.L) * 16 * sizeof(cf));
     }
@@ -400,14 +434,20 @@ Ws ws_layout(const Plan& p, int B, int N, int D) {
   return w;
 }
 
-int need_ws(const Ws& w, void* ws, size_t bytes) {
-  if (w.total == 0) return SMX_OK;
-  if (!ws) return fail(SMX_ERR_WORKSPACE, "workspace is NULL, %zu bytes required", w.total);
-  if (bytes < w.total)
-    return fail(SMX_ERR_WORKSPACE, "workspace has %zu bytes, %zu required", bytes, w.total);
-  if ((uintptr_t)ws & 255) return fail(SMX_ERR_INVALID, "workspace must be 256-byte aligned");
-  return SMX_OK;
+// THE workspace test: `need` bytes at a 256-byte aligned address
+bool ws_usable(const void* ws, size_t bytes, size_t need) { return ws && bytes >= need && !((uintptr_t)ws & 255); }
+// ... and its refusal.  query: the entry that tells the size ("" = none is named), or NULL for the three messages of
+// the transform entries
+int need_ws(const void* ws, size_t bytes, size_t need, const char* query) {
+  if (ws_usable(ws, bytes, need)) return SMX_OK;
+  if (query)
+    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes%s%s%s", need, *query ? " (" : "",
+                query, *query ? ")" : "");
+  if (!ws) return fail(SMX_ERR_WORKSPACE, "workspace is NULL, %zu bytes required", need);
+  if (bytes < need) return fail(SMX_ERR_WORKSPACE, "workspace has %zu bytes, %zu required", bytes, need);
+  return fail(SMX_ERR_INVALID, "workspace must be 256-byte aligned");
 }
+int need_ws(const Ws& w, const void* ws, size_t bytes) { return need_ws(ws, bytes, w.total, nullptr); }
 
 // elem: bytes per element of the streamed x / y (4; 2 for the 2-byte activations of the _io entries)
 // dir: 0 = a forward entry point, 1 = a backward one (which "st_layout_*" option places the write-back rows)
@@ -472,6 +512,31 @@ int drop_cfg(float p, const void* rng_state, DropCfg* out) {
   return SMX_OK;
 }
 void set_drop(DecimArgs& a, const DropCfg& dc) { a.drop_thr = dc.thr; a.drop_scale = dc.scale; a.rng = dc.rng; }
+hipError_t drop_rows(const float* in, float* out, const Shape& h, const DropCfg& dc, hipStream_t s) {
+  return launch_dropout_rows(in, out, h.B, (long long)h.N * h.D, dc.thr, dc.scale, dc.rng, s);
+}
+
+// ---- steps the entries share ---------------------------------------------------------------------------------------
+// the filter of a forward launch (xk_save: where the spectrum is kept for backward, or NULL) ...
+void filter_fwd(DecimArgs& a, const float* w_re, const float* w_im, const float* bias, int conj_w, float* xk_save) {
+  a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.bias = bias; a.fa.conj_w = conj_w;
+  a.fa.xk_out = xk_save;
+}
+// ... and of a backward launch: conj(W), the saved spectrum, the per-batch-row products and bias partials
+void filter_bwd(DecimArgs& a, const float* w_re, const float* w_im, const float* xk, char* ws, const Ws& w) {
+  a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.conj_w = 1;
+  a.fa.xk_in = xk; a.fa.pslab = (float*)(ws + w.slab); a.fa.gb_part = (float*)(ws + w.gbp);
+}
+// four-step launches: the tile spectra at `tiles`, walked in the plan's chunks
+void use_tiles(DecimArgs& a, const Plan& p, void* tiles) { a.ws_f = (cf*)tiles; a.nsplit = p.fs_nsplit; a.lc = p.fs_lc; }
+// the same launch without its inverse half: products out, spectrum parked
+DecimArgs no_out(DecimArgs a) { a.out = nullptr; return a; }
+// The fused forward launches leave the workspace's sync area zero when they are given one: a backward call on the same
+// workspace may then skip its own clearing (SMX_PHASE_SYNC_CLEAN).
+void use_sync(DecimArgs& a, const Ws& w, void* workspace, size_t workspace_bytes) {
+  if (ws_usable(workspace, workspace_bytes, w.total) && sync_words(a.g.B, a.g.D) * sizeof(unsigned) <= SYNC_BYTES)
+    a.sync = (unsigned*)((char*)workspace + w.sync);
+}
 
 // The filter in the layout of the unpack phase (FilterArgs::wt).  `ready`: a copy packed by an earlier
 // call with the same weights (backward reusing forward's) -- nothing is launched.  `keep`: caller buffer
@@ -493,7 +558,7 @@ int pack_filter(DecimArgs& a, const Plan& p, const Ws& w, void* workspace, size_
   if (ready) { a.fa.wt = ready; return SMX_OK; }
   cf* wt = (cf*)keep;
   if (!wt) {
-    if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return SMX_OK;
+    if (!ws_usable(workspace, workspace_bytes, w.total)) return SMX_OK;
     wt = (cf*)((char*)workspace + w.wt);
   }
   HIP_TRY(launch_pack_w(w_re, w_im, wt, D, F, p.k, s));
@@ -624,10 +689,10 @@ const char* smx_build_flags(void) {
 static int plan_query_impl(const Shape& h, smx_plan* out) {
   if (!out) return fail(SMX_ERR_INVALID, "out is NULL");
   Plan p = make_plan(h);
-  out->path = p.path; out->k = p.k; out->L = p.L; out->bands = p.full8 ? 8 : p.fs ? 0 : p.nb;
-  out->nsplit = p.fs ? p.fs_nsplit : p.nsplit;
+  out->path = p.path; out->k = p.k; out->L = p.L; out->bands = p.full8() ? 8 : p.fs() ? 0 : p.nb;
+  out->nsplit = p.fs() ? p.fs_nsplit : p.nsplit;
   out->workgroups = p.path != SMX_PATH_DIRECT ? p.nwg * out->nsplit : 0;
-  out->groups = (p.full8 || p.fs) ? 1 : p.groups;
+  out->groups = p.groups_only() ? p.groups : 1;
   return SMX_OK;
 }
 int smx_plan_query(int B, int N, int D, int F, smx_plan* out) {
@@ -661,56 +726,21 @@ int smx_prepare(int N) {
   return get_tables(N, &t, nullptr);
 }
 
-int smx_forward(const float* x, const float* w_re, const float* w_im, const float* bias, float* y,
-                float* xk_save, void* workspace, size_t workspace_bytes, int B, int N, int D, int F,
-                int conj_w, void* stream) {
-  return smx_forward_dropout(x, w_re, w_im, bias, y, xk_save, workspace, workspace_bytes, B, N, D, F,
-                             conj_w, 0.f, nullptr, nullptr, stream);
-}
-
-// io (forward_impl, backward_impl): element type of x / y / g / grad_x, SMX_IO_*.  2-byte rows travel behind the
-// float pointers and are only read by the IO instances of k_fused / k_split_a / k_split_b, on the plans of io_native.
-static bool io_native(const Plan& p) {
-  return p.path == SMX_PATH_DECIMATED && p.groups == 1 && !p.fs && !p.full8;
-}
 static int io_check(int io) {
   if (io != SMX_IO_F32 && io != SMX_IO_BF16 && io != SMX_IO_F16)
     return fail(SMX_ERR_INVALID, "io must be SMX_IO_F32, SMX_IO_BF16 or SMX_IO_F16, got %d", io);
   return SMX_OK;
 }
 
-static int forward_impl(const Shape& h, const float* x, const float* w_re, const float* w_im,
-                        const float* bias, float* y, float* xk_save, void* workspace,
-                        size_t workspace_bytes, int conj_w, float dropout_p, const void* rng_state,
-                        float* filter_pack, void* stream, const float* row_scale = nullptr, int io = SMX_IO_F32);
-
-int smx_forward_dropout(const float* x, const float* w_re, const float* w_im, const float* bias,
-                        float* y, float* xk_save, void* workspace, size_t workspace_bytes, int B,
-                        int N, int D, int F, int conj_w, float dropout_p, const void* rng_state,
-                        float* filter_pack, void* stream) {
-  if (int rc = check_shape(B, N, D, F)) return rc;
-  return forward_impl(layer_shape(B, N, D, F), x, w_re, w_im, bias, y, xk_save, workspace, workspace_bytes,
-                      conj_w, dropout_p, rng_state, filter_pack, stream);
-}
-
-int smx_forward_ex(const smx_shape* shape, const float* x, const float* w_re, const float* w_im,
-                   const float* bias, float* y, float* xk_save, void* workspace, size_t workspace_bytes,
-                   int conj_w, float* filter_pack, const float* row_scale, void* stream) {
-  Shape h;
-  if (int rc = shape_from(shape, &h)) return rc;
-  return forward_impl(h, x, w_re, w_im, bias, y, xk_save, workspace, workspace_bytes, conj_w, 0.f, nullptr,
-                      filter_pack, stream, row_scale);
-}
-
 int smx_row_scale_supported(const smx_shape* shape) {
   Shape h;
   if (shape_from(shape, &h)) return 0;
-  const Plan p = make_plan(h);
-  // (the eight-band kernel of option fourstep = 0 is left out: it only serves calls that run both halves of the
-  // backward together, and a caller must be able to rely on this answer for every phase split)
-  return p.path == SMX_PATH_DECIMATED && (p.groups == 1 || p.fs) ? 1 : 0;
+  return make_plan(h).row_scale() ? 1 : 0;
 }
 
+// io (forward_impl, backward_impl): element type of x / y / g / grad_x, SMX_IO_*.  2-byte rows travel behind the
+// float pointers and are only read by the IO instances of k_fused / k_split_a / k_split_b, on the plans of
+// Plan::io_native.
 static int forward_impl(const Shape& h, const float* x, const float* w_re, const float* w_im,
                         const float* bias, float* y, float* xk_save, void* workspace,
                         size_t workspace_bytes, int conj_w, float dropout_p, const void* rng_state,
@@ -728,7 +758,7 @@ static int forward_impl(const Shape& h, const float* x, const float* w_re, const
   if ((uintptr_t)xk_save & 15) return fail(SMX_ERR_INVALID, "xk_save must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const Plan p = make_plan(h);
-  if (io != SMX_IO_F32 && !io_native(p))
+  if (io != SMX_IO_F32 && !p.io_native())
     return fail(SMX_ERR_UNSUPPORTED, "no 2-byte I/O on this plan (smx_io_supported): widen the input and call "
                 "smx_forward_dropout");
   if (dc.thr && h.R < N) return fail(SMX_ERR_UNSUPPORTED, "fused dropout is not available with zero-padded rows");
@@ -738,57 +768,51 @@ static int forward_impl(const Shape& h, const float* x, const float* w_re, const
   TableRef t;
   if (int rc = get_tables(N, &t, s)) return rc;
   char* ws = (char*)workspace;
-  if (p.path == SMX_PATH_DECIM16 && !row_scale) {
-    DecimArgs a = decim_args(p, t, h, ws, w);
-    a.in = x; a.out = y;
-    a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.bias = bias; a.fa.conj_w = conj_w;
-    a.fa.xk_out = xk_save;
-    set_drop(a, dc);
-    if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F,
-                             pack_ready ? filter_pack : nullptr, pack_ready ? nullptr : filter_pack, s))
-      return rc;
-    if (p.nsplit == 1) {
-      HIP_TRY(launch_fused16(a, p.nb, 0, s));
-    } else {
-      if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
-      HIP_TRY(launch_split16_a(a, p.nb, false, s));
-      HIP_TRY(launch_split_f(a, p.nb, 0, s));
-      HIP_TRY(launch_split16_b(a, p.nb, true, s));
-    }
-    return SMX_OK;
-  }
-  if (p.path == SMX_PATH_DECIMATED) {
-    if (p.nsplit > 1) if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
+  // (the sixteen-row kernels take no row scale: such a call is left to the DFT products, which refuse it)
+  const bool direct = p.kind == Kind::Direct || (p.kind == Kind::Sixteen && row_scale);
+  // More than 512 bins (four-step, eight-band and band-group plans): their tile stores have no fused mask, nor has the
+  // direct plan; the same mask -- a pure function of (generator state, batch row, element) -- goes on y in one more pass.
+  const bool post_drop = dc.thr && (p.wide() || direct);
+  if (direct) {
+    if (row_scale) return fail(SMX_ERR_UNSUPPORTED, "row_scale is not available on the direct plan (smx_row_scale_supported)");
+    if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
+    DirectArgs d = direct_args(p, t, h);
+    cf* xk = xk_save ? (cf*)xk_save : (cf*)(ws + w.spec0);
+    cf* sk = (cf*)(ws + w.spec1);
+    HIP_TRY(launch_direct_spectrum(x, xk, d, s));
+    HIP_TRY(launch_direct_filter(xk, w_re, w_im, conj_w, sk, d, s));
+    HIP_TRY(launch_direct_synth(sk, bias, y, d, s));
+  } else {
+    if (p.kind == Kind::Split) if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
     DecimArgs a = decim_args(p, t, h, ws, w, io != SMX_IO_F32 ? 2 : 4);
     a.in = x; a.out = y;
-    a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.bias = bias; a.fa.conj_w = conj_w;
-    a.fa.xk_out = xk_save;
+    filter_fwd(a, w_re, w_im, bias, conj_w, xk_save);
     a.fa.sc = row_scale;
-    if (row_scale && !(p.groups == 1 || p.fs))
+    if (row_scale && !p.row_scale())
       return fail(SMX_ERR_UNSUPPORTED, "row_scale is not available on the band-group plan (smx_row_scale_supported)");
-    // More than 512 bins (four-step, eight-band and band-group plans): their tile stores have no fused mask; the same mask -- a pure
-    // function of (generator state, batch row, element) -- goes on y in one more pass (round 4; refused before).
-    const bool post_drop = dc.thr && (p.fs || p.full8 || p.groups > 1);
     set_drop(a, post_drop ? DropCfg{} : dc);
     if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F,
                              pack_ready ? filter_pack : nullptr, pack_ready ? nullptr : filter_pack, s))
       return rc;
-    if (p.fs) {
+    if (p.kind == Kind::Sixteen) {
+      if (p.nsplit == 1) {
+        HIP_TRY(launch_fused16(a, p.nb, 0, s));
+      } else {
+        if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
+        HIP_TRY(launch_split16_a(a, p.nb, false, s));
+        HIP_TRY(launch_split_f(a, p.nb, 0, s));
+        HIP_TRY(launch_split16_b(a, p.nb, true, s));
+      }
+    } else if (p.fs()) {
       if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
-      a.ws_f = (cf*)(ws + w.fs); a.nsplit = p.fs_nsplit; a.lc = p.fs_lc;
+      use_tiles(a, p, ws + w.fs);
       HIP_TRY(launch_fs_a(a, s));
       HIP_TRY(launch_fs_f(a, 0, s));
       HIP_TRY(launch_fs_b(a, s));
-      if (post_drop) HIP_TRY(launch_dropout_rows(y, y, B, (long long)N * D, dc.thr, dc.scale, dc.rng, s));
-      return SMX_OK;
-    }
-    if (p.full8) {
+    } else if (p.full8()) {
       if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
       HIP_TRY(launch_full8(a, 0, s));
-      if (post_drop) HIP_TRY(launch_dropout_rows(y, y, B, (long long)N * D, dc.thr, dc.scale, dc.rng, s));
-      return SMX_OK;
-    }
-    if (p.groups > 1) {
+    } else if (p.groups_only()) {
       if (x == y) return fail(SMX_ERR_INVALID, "the band-group plan cannot transform in place (y must not alias x)");
       if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
       for (int g = 0; g < p.groups; ++g) {
@@ -802,67 +826,40 @@ static int forward_impl(const Shape& h, const float* x, const float* w_re, const
       HIP_TRY(launch_direct_filter(xe, w_re, w_im, conj_w, (cf*)(ws + w.edge1), e, s));
       e.rows = 0;
       HIP_TRY(launch_edge_synth_acc((cf*)(ws + w.edge1), y, e, s));
-      if (post_drop) HIP_TRY(launch_dropout_rows(y, y, B, (long long)N * D, dc.thr, dc.scale, dc.rng, s));
-      return SMX_OK;
-    }
-    if (p.nsplit == 1) {
-      // the forward launch leaves the workspace's sync area zero: a backward call on the same workspace may then
-      // skip its own clearing (SMX_PHASE_SYNC_CLEAN)
-      if (workspace && workspace_bytes >= w.total && !((uintptr_t)workspace & 255) &&
-          sync_words(B, D) * sizeof(unsigned) <= SYNC_BYTES)
-        a.sync = (unsigned*)(ws + w.sync);
+    } else if (p.kind == Kind::Single) {
+      use_sync(a, w, workspace, workspace_bytes);
       HIP_TRY(launch_fused(a, p.nb, 0, s, io));
     } else {
       HIP_TRY(launch_split_a(a, p.nb, false, s, io));
       HIP_TRY(launch_split_f(a, p.nb, 0, s));
       HIP_TRY(launch_split_b(a, p.nb, true, s, io));
     }
-    return SMX_OK;
   }
-  if (row_scale) return fail(SMX_ERR_UNSUPPORTED, "row_scale is not available on the direct plan (smx_row_scale_supported)");
-  if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
-  DirectArgs d = direct_args(p, t, h);
-  cf* xk = xk_save ? (cf*)xk_save : (cf*)(ws + w.spec0);
-  cf* sk = (cf*)(ws + w.spec1);
-  HIP_TRY(launch_direct_spectrum(x, xk, d, s));
-  HIP_TRY(launch_direct_filter(xk, w_re, w_im, conj_w, sk, d, s));
-  HIP_TRY(launch_direct_synth(sk, bias, y, d, s));
-  if (dc.thr) HIP_TRY(launch_dropout_rows(y, y, B, (long long)N * D, dc.thr, dc.scale, dc.rng, s));
+  if (post_drop) HIP_TRY(drop_rows(y, y, h, dc, s));
   return SMX_OK;
 }
 
-int smx_backward(const float* g, const float* xk, const float* w_re, const float* w_im,
-                 float* grad_x, float* gw_re, float* gw_im, float* gbias, void* workspace,
-                 size_t workspace_bytes, int B, int N, int D, int F, int phases, void* stream) {
-  return smx_backward_dropout(g, xk, w_re, w_im, grad_x, gw_re, gw_im, gbias, workspace,
-                              workspace_bytes, B, N, D, F, phases, 0.f, nullptr, nullptr, stream);
-}
-
-static int backward_impl(const Shape& h, const float* g, const float* xk, const float* w_re,
-                         const float* w_im, float* grad_x, float* gw_re, float* gw_im, float* gbias,
-                         void* workspace, size_t workspace_bytes, int phases, float dropout_p,
-                         const void* rng_state, const float* filter_pack, void* stream,
-                         const float* row_scale = nullptr, float* grad_row_scale = nullptr, int io = SMX_IO_F32,
-                         int oio = -1);
-
-int smx_backward_dropout(const float* g, const float* xk, const float* w_re, const float* w_im,
-                         float* grad_x, float* gw_re, float* gw_im, float* gbias, void* workspace,
-                         size_t workspace_bytes, int B, int N, int D, int F, int phases,
-                         float dropout_p, const void* rng_state, const float* filter_pack,
-                         void* stream) {
+int smx_forward_dropout(const float* x, const float* w_re, const float* w_im, const float* bias,
+                        float* y, float* xk_save, void* workspace, size_t workspace_bytes, int B,
+                        int N, int D, int F, int conj_w, float dropout_p, const void* rng_state,
+                        float* filter_pack, void* stream) {
   if (int rc = check_shape(B, N, D, F)) return rc;
-  return backward_impl(layer_shape(B, N, D, F), g, xk, w_re, w_im, grad_x, gw_re, gw_im, gbias, workspace,
-                       workspace_bytes, phases, dropout_p, rng_state, filter_pack, stream);
+  return forward_impl(layer_shape(B, N, D, F), x, w_re, w_im, bias, y, xk_save, workspace, workspace_bytes,
+                      conj_w, dropout_p, rng_state, filter_pack, stream, nullptr, SMX_IO_F32);
 }
-
-int smx_backward_ex(const smx_shape* shape, const float* g, const float* xk, const float* w_re,
-                    const float* w_im, float* grad_x, float* gw_re, float* gw_im, float* gbias,
-                    void* workspace, size_t workspace_bytes, int phases, const float* filter_pack,
-                    const float* row_scale, float* grad_row_scale, void* stream) {
+int smx_forward(const float* x, const float* w_re, const float* w_im, const float* bias, float* y,
+                float* xk_save, void* workspace, size_t workspace_bytes, int B, int N, int D, int F,
+                int conj_w, void* stream) {
+  return smx_forward_dropout(x, w_re, w_im, bias, y, xk_save, workspace, workspace_bytes, B, N, D, F,
+                             conj_w, 0.f, nullptr, nullptr, stream);
+}
+int smx_forward_ex(const smx_shape* shape, const float* x, const float* w_re, const float* w_im,
+                   const float* bias, float* y, float* xk_save, void* workspace, size_t workspace_bytes,
+                   int conj_w, float* filter_pack, const float* row_scale, void* stream) {
   Shape h;
   if (int rc = shape_from(shape, &h)) return rc;
-  return backward_impl(h, g, xk, w_re, w_im, grad_x, gw_re, gw_im, gbias, workspace, workspace_bytes, phases,
-                       0.f, nullptr, filter_pack, stream, row_scale, grad_row_scale);
+  return forward_impl(h, x, w_re, w_im, bias, y, xk_save, workspace, workspace_bytes, conj_w, 0.f, nullptr,
+                      filter_pack, stream, row_scale, SMX_IO_F32);
 }
 
 static int backward_impl(const Shape& h, const float* g, const float* xk, const float* w_re,
@@ -892,14 +889,13 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
   if ((uintptr_t)xk & 15) return fail(SMX_ERR_INVALID, "xk must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const Plan p = make_plan(h);
-  if (io != SMX_IO_F32 && !io_native(p))
+  if (io != SMX_IO_F32 && !p.io_native())
     return fail(SMX_ERR_UNSUPPORTED, "no 2-byte I/O on this plan (smx_io_supported): widen g and call "
                 "smx_backward_dropout");
   if (dc.thr && h.R < N) return fail(SMX_ERR_UNSUPPORTED, "fused dropout is not available with zero-padded rows");
   if ((want_w || dc.thr || grad_row_scale || oio != io) && !xk && p.k > 0)
     return fail(SMX_ERR_INVALID, "xk (saved spectrum) is NULL");
-  if ((row_scale || grad_row_scale) &&
-      !(p.path == SMX_PATH_DECIMATED && (p.groups == 1 || p.fs)))
+  if ((row_scale || grad_row_scale) && !p.row_scale())
     return fail(SMX_ERR_UNSUPPORTED, "row_scale is not available on this plan (smx_row_scale_supported)");
   if (grad_row_scale && !row_scale) return fail(SMX_ERR_INVALID, "grad_row_scale without row_scale");
   const Ws w = ws_layout(p, B, N, D);
@@ -910,57 +906,28 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
   const bool do_spec = phases & SMX_PHASE_SPECTRUM, do_inv = phases & SMX_PHASE_INVERSE;
   const bool do_par = (phases & SMX_PHASE_PARAMS) && want_w;
 
-  if (p.path == SMX_PATH_DECIM16) {
-    if (row_scale || grad_row_scale)
-      return fail(SMX_ERR_UNSUPPORTED, "row_scale is not available on this plan (smx_row_scale_supported)");
-    DecimArgs a = decim_args(p, t, h, ws, w);
+  if (p.kind != Kind::Direct) {
+    // (the sixteen-row launches have always been placed by the forward launches' option, "st_layout_fwd")
+    DecimArgs a = decim_args(p, t, h, ws, w, oio != SMX_IO_F32 ? 2 : 4, p.kind == Kind::Sixteen ? 0 : 1);
     a.in = g; a.out = grad_x;
-    a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.conj_w = 1;
-    a.fa.xk_in = xk; a.fa.pslab = (float*)(ws + w.slab); a.fa.gb_part = (float*)(ws + w.gbp);
-    set_drop(a, dc);
-    const int mode = (want_w || dc.thr) ? 1 : 0;                  // (the mask is applied by the mode-1 load)
-    if (do_spec) {
-      if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F, filter_pack, nullptr, s)) return rc;
-      if (p.nsplit > 1) {
-        HIP_TRY(launch_split16_a(a, p.nb, true, s));
-        HIP_TRY(launch_split_f(a, p.nb, mode, s));
-        if (do_inv) HIP_TRY(launch_split16_b(a, p.nb, false, s));
-      } else if (do_inv) {
-        HIP_TRY(launch_fused16(a, p.nb, mode, s));
-      } else {                                                     // SPECTRUM alone: products out, spectrum parked
-        DecimArgs sp = a;
-        sp.out = nullptr;
-        HIP_TRY(launch_fused16(sp, p.nb, mode, s));
-      }
-    } else if (do_inv) {
-      HIP_TRY(launch_split16_b(a, p.nb, false, s));               // (nsplit == 1: one chunk = every tile)
-    }
-    if (do_par)
-      HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, B, D, F, p.k, s));
-    return SMX_OK;
-  }
-  if (p.path == SMX_PATH_DECIMATED) {
-    DecimArgs a = decim_args(p, t, h, ws, w, oio != SMX_IO_F32 ? 2 : 4, 1);
-    a.in = g; a.out = grad_x;
-    a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.conj_w = 1;
-    a.fa.xk_in = xk; a.fa.pslab = (float*)(ws + w.slab); a.fa.gb_part = (float*)(ws + w.gbp);
+    filter_bwd(a, w_re, w_im, xk, ws, w);
     // mode 0 with xk_out == NULL: input gradient only (with dropout the mask goes on the LOADED tile,
     // which only the mode-1 instantiation does: use it, the products land in the workspace unused)
-    const bool pre_drop = dc.thr && (p.fs || p.full8 || p.groups > 1);      // (see below)
+    const bool pre_drop = dc.thr && p.wide();      // (see below)
     const int mode = (want_w || (dc.thr && !pre_drop) || grad_row_scale || oio != io) ? 1 : 0;
     a.fa.sc = row_scale; a.fa.gsc = grad_row_scale;
-    if (p.fs && grad_row_scale) a.fa.gsc_part = (cf*)(ws + w.gscp);
+    if (p.fs() && grad_row_scale) a.fa.gsc_part = (cf*)(ws + w.gscp);
     // four-step / eight-band plans: the masked upstream gradient is staged in grad_x first (their kernels read the whole
     // input column before the first store to it, so transforming grad_x in place is safe)
     set_drop(a, pre_drop ? DropCfg{} : dc);
     if (pre_drop && do_spec) {
-      if (p.fs || p.full8) {
+      if (!p.groups_only()) {
         if (!grad_x) return fail(SMX_ERR_INVALID, "dropout with more than 512 bins needs grad_x as scratch");
-        if (p.full8 && !do_inv) return fail(SMX_ERR_UNSUPPORTED, "dropout on the eight-band plan needs the spectrum and inverse phases in one call");
-        HIP_TRY(launch_dropout_rows(g, grad_x, B, (long long)N * D, dc.thr, dc.scale, dc.rng, s));
+        if (p.full8() && !do_inv) return fail(SMX_ERR_UNSUPPORTED, "dropout on the eight-band plan needs the spectrum and inverse phases in one call");
+        HIP_TRY(drop_rows(g, grad_x, h, dc, s));
         a.in = grad_x;
       } else {             // band groups: the launches re-read g while grad_x accumulates -> the workspace's row copy
-        HIP_TRY(launch_dropout_rows(g, (float*)(ws + w.rows), B, (long long)N * D, dc.thr, dc.scale, dc.rng, s));
+        HIP_TRY(drop_rows(g, (float*)(ws + w.rows), h, dc, s));
         a.in = (const float*)(ws + w.rows);
         g = a.in;          // (the edge-bin spectrum below reads g as well)
       }
@@ -969,8 +936,22 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
       if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F, filter_pack,
                                nullptr, s))
         return rc;
-    if (p.fs) {
-      a.ws_f = (cf*)(ws + w.fs); a.nsplit = p.fs_nsplit; a.lc = p.fs_lc;
+    int slab_rows = B;          // rows of the gradient slab that launch_gradw_slab sums
+    bool reduce = do_par;       // ... in its own launch
+    if (p.kind == Kind::Sixteen) {
+      if (do_spec) {
+        if (p.nsplit > 1) {
+          HIP_TRY(launch_split16_a(a, p.nb, true, s));
+          HIP_TRY(launch_split_f(a, p.nb, mode, s));
+          if (do_inv) HIP_TRY(launch_split16_b(a, p.nb, false, s));
+        } else {                                                     // (SPECTRUM alone: products out, spectrum parked)
+          HIP_TRY(launch_fused16(do_inv ? a : no_out(a), p.nb, mode, s));
+        }
+      } else if (do_inv) {
+        HIP_TRY(launch_split16_b(a, p.nb, false, s));               // (nsplit == 1: one chunk = every tile)
+      }
+    } else if (p.fs()) {
+      use_tiles(a, p, ws + w.fs);
       // Option "fs_bgroups" = G > 0: slab rows summed over G batch groups inside k_fs_f (a rule of the shape
       // and the option only, so that a separate SMX_PHASE_PARAMS call reads the layout the SPECTRUM call
       // wrote).  Measured at (64,1024,512), G = 8: k_gradw 71 -> 16 us, but k_fs_f<8,1> 215 -> 286 us -- one
@@ -978,24 +959,15 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
       const int bgo = cur_opts().fs_bgroups;
       const int bg = (bgo > 0 && fs_grouped_tiles::has(p.L) && B >= 2 * bgo) ? bgo : 0;
       a.fs_bgroups = bg;
+      if (bg) slab_rows = (B + (B + bg - 1) / bg - 1) / ((B + bg - 1) / bg);
       if (do_spec) {
         HIP_TRY(launch_fs_a(a, s));
         HIP_TRY(launch_fs_f(a, mode, s));
       }
       if (do_inv) HIP_TRY(launch_fs_b(a, s));
-      if (do_par)
-        HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias,
-                                  bg ? (B + (B + bg - 1) / bg - 1) / ((B + bg - 1) / bg) : B, D, F, p.k, s));
-      return SMX_OK;
-    }
-    if (p.full8 && do_spec && do_inv) {
+    } else if (p.full8() && do_spec && do_inv) {
       HIP_TRY(launch_full8(a, mode, s));
-      if (do_par)
-        HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, B,
-                                  D, F, p.k, s));
-      return SMX_OK;
-    }
-    if (p.groups > 1) {
+    } else if (p.wide()) {             // band groups, also as the phase-split form of the eight-band plan
       DirectArgs e = edge_args(p, t, h);
       cf* ge = (cf*)(ws + w.edge0);
       cf* se = (cf*)(ws + w.edge1);
@@ -1006,23 +978,14 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
       }
       for (int gi = 0; gi < p.groups; ++gi) {
         if (int rc = set_group(a, p, t, w, ws, N, gi, nullptr, s)) return rc;
-        if (do_spec && do_inv) {
-          HIP_TRY(launch_fused(a, 4, mode, s));
-        } else if (do_spec) {
-          DecimArgs h = a;
-          h.out = nullptr;
-          HIP_TRY(launch_fused(h, 4, mode, s));
+        if (do_spec) {
+          HIP_TRY(launch_fused(do_inv ? a : no_out(a), 4, mode, s));
         } else if (do_inv) {
           HIP_TRY(launch_split_b(a, 4, false, s));
         }
       }
       if (do_inv) HIP_TRY(launch_edge_synth_acc(se, grad_x, e, s));
-      if (do_par)
-        HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, B,
-                                  D, F, p.k, s));
-      return SMX_OK;
-    }
-    if (do_spec && do_inv && p.nsplit == 1) {
+    } else if (do_spec && do_inv && p.kind == Kind::Single) {
       // Option fold_gradw = 1: one launch for everything -- the parameter-gradient reduction rides behind the
       // transform workgroups (gradw_tail in smx_decim.hip) instead of a separate k_gradw launch + two kernel
       // boundaries.  Bit-identical, wait-free for the producers, and MEASURED SLOWER (profiles/r03_fold_gradw_ab.txt:
@@ -1040,15 +1003,13 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
         a.gw_re = gw_re; a.gw_im = gw_im; a.gbias = gbias;
         a.fa.slab_agent = 1;
         if (!sync_clean) HIP_TRY(hipMemsetAsync(a.sync, 0, sync_words(B, D) * sizeof(unsigned), s));
+        reduce = false;
       }
       HIP_TRY(launch_fused(a, p.nb, mode, s, io, oio));
-      if (fold) return SMX_OK;
     } else {
       if (do_spec) {
-        if (p.nsplit == 1) {          // forward half + filter in one launch, S parked in the workspace
-          DecimArgs h = a;
-          h.out = nullptr;
-          HIP_TRY(launch_fused(h, p.nb, mode, s, io, oio));
+        if (p.kind == Kind::Single) {          // forward half + filter in one launch, S parked in the workspace
+          HIP_TRY(launch_fused(no_out(a), p.nb, mode, s, io, oio));
         } else {
           HIP_TRY(launch_split_a(a, p.nb, true, s, io));
           HIP_TRY(launch_split_f(a, p.nb, mode, s));
@@ -1056,9 +1017,8 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
       }
       if (do_inv) HIP_TRY(launch_split_b(a, p.nb, false, s, oio));
     }
-    if (do_par)
-      HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, B,
-                                D, F, p.k, s));
+    if (reduce)
+      HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, slab_rows, D, F, p.k, s));
     return SMX_OK;
   }
 
@@ -1071,7 +1031,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
     if (p.k == 0) dg.k = 1;
     if (dc.thr) {            // masked upstream gradient, staged in grad_x (overwritten by the synthesis)
       if (!grad_x) return fail(SMX_ERR_INVALID, "dropout on the direct plan needs grad_x as scratch");
-      HIP_TRY(launch_dropout_rows(g, grad_x, B, (long long)N * D, dc.thr, dc.scale, dc.rng, s));
+      HIP_TRY(drop_rows(g, grad_x, h, dc, s));
       g = grad_x;
     }
     HIP_TRY(launch_direct_spectrum(g, gk, dg, s));
@@ -1093,31 +1053,47 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
   return SMX_OK;
 }
 
+int smx_backward_dropout(const float* g, const float* xk, const float* w_re, const float* w_im,
+                         float* grad_x, float* gw_re, float* gw_im, float* gbias, void* workspace,
+                         size_t workspace_bytes, int B, int N, int D, int F, int phases,
+                         float dropout_p, const void* rng_state, const float* filter_pack,
+                         void* stream) {
+  if (int rc = check_shape(B, N, D, F)) return rc;
+  return backward_impl(layer_shape(B, N, D, F), g, xk, w_re, w_im, grad_x, gw_re, gw_im, gbias, workspace,
+                       workspace_bytes, phases, dropout_p, rng_state, filter_pack, stream, nullptr, nullptr,
+                       SMX_IO_F32, -1);
+}
+int smx_backward(const float* g, const float* xk, const float* w_re, const float* w_im,
+                 float* grad_x, float* gw_re, float* gw_im, float* gbias, void* workspace,
+                 size_t workspace_bytes, int B, int N, int D, int F, int phases, void* stream) {
+  return smx_backward_dropout(g, xk, w_re, w_im, grad_x, gw_re, gw_im, gbias, workspace,
+                              workspace_bytes, B, N, D, F, phases, 0.f, nullptr, nullptr, stream);
+}
+int smx_backward_ex(const smx_shape* shape, const float* g, const float* xk, const float* w_re,
+                    const float* w_im, float* grad_x, float* gw_re, float* gw_im, float* gbias,
+                    void* workspace, size_t workspace_bytes, int phases, const float* filter_pack,
+                    const float* row_scale, float* grad_row_scale, void* stream) {
+  Shape h;
+  if (int rc = shape_from(shape, &h)) return rc;
+  return backward_impl(h, g, xk, w_re, w_im, grad_x, gw_re, gw_im, gbias, workspace, workspace_bytes, phases,
+                       0.f, nullptr, filter_pack, stream, row_scale, grad_row_scale, SMX_IO_F32, -1);
+}
+
 // complex sequence FFT: (A) tile spectra + (F) columns written straight out; its own plan (any L the column
 // kernel is instantiated for, also below the 512-bin threshold of the filter plans)
 static bool cfft_plan(const Shape& h, Plan* p) {
-  if (h.N % M != 0 || h.D % 2 != 0 || h.R > h.N) return false;
-  const int L = h.N / M;
-  if (!fs_tiles_cfft(L)) return false;
-  *p = Plan{};
-  p->path = SMX_PATH_DECIMATED; p->L = L; p->k = h.N / 2 + 1; p->nb = 4; p->groups = 1;
-  p->nwg = h.B * ((h.D + DT - 1) / DT);
-  int ns = 512 / p->nwg;
-  if (ns < 1) ns = 1;
-  if (ns > L) ns = L;
-  p->fs = true;
-  p->fs_lc = (L + ns - 1) / ns;
-  p->fs_nsplit = (L + p->fs_lc - 1) / p->fs_lc;
-  p->nsplit = 1; p->lc = L;
+  if (h.N % M != 0 || h.D % 2 != 0 || h.R > h.N || !fs_tiles_cfft(h.N / M)) return false;
+  *p = tile_plan(h);
   return true;
 }
+static size_t cfft_need(const Plan& p) { return SYNC_BYTES + al((size_t)p.nwg * p.L * EX * sizeof(cf)); }   // the sync area stays untouched (ws_layout)
 int smx_cfft_workspace_bytes(const smx_shape* shape, size_t* out) {
   if (!shape || !out) return fail(SMX_ERR_INVALID, "NULL argument");
   Shape h{shape->B, shape->rows, shape->D, shape->n_fft / 2 + 1, shape->n_fft, shape->n_fft / 2 + 1};
   if (int rc = check_shape(h)) return rc;
   Plan p;
   if (!cfft_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, "smx_cfft_ex does not take this shape");
-  *out = SYNC_BYTES + al((size_t)p.nwg * p.L * EX * sizeof(cf));      // the sync area stays untouched (ws_layout)
+  *out = cfft_need(p);
   return SMX_OK;
 }
 int smx_cfft_ex(const smx_shape* shape, const float* z, float* out, void* workspace, size_t workspace_bytes,
@@ -1132,9 +1108,7 @@ int smx_cfft_ex(const smx_shape* shape, const float* z, float* out, void* worksp
   if (!cfft_plan(h, &p))
     return fail(SMX_ERR_UNSUPPORTED, "smx_cfft_ex needs n_fft = 256 L with L in {2, 4, 5..32, 36..64 step 4, 72..128 step 8, 144..256 step 16} and an even D; "
                                      "compose it from smx_spectrum_ex otherwise");
-  const size_t need = SYNC_BYTES + al((size_t)p.nwg * p.L * EX * sizeof(cf));
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
-    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes (smx_cfft_workspace_bytes)", need);
+  if (int rc = need_ws(workspace, workspace_bytes, cfft_need(p), "smx_cfft_workspace_bytes")) return rc;
   TableRef t;
   if (int rc = get_tables(h.N, &t, s)) return rc;
   Ws dummy;
@@ -1142,7 +1116,7 @@ int smx_cfft_ex(const smx_shape* shape, const float* z, float* out, void* worksp
   a.ws_z = a.ws_zs = a.ws_s = nullptr;
   a.in = z; a.out = nullptr;
   a.fa.xk_out = out;
-  a.ws_f = (cf*)((char*)workspace + SYNC_BYTES); a.nsplit = p.fs_nsplit; a.lc = p.fs_lc;
+  use_tiles(a, p, (char*)workspace + SYNC_BYTES);
   HIP_TRY(launch_fs_a(a, s));
   HIP_TRY(launch_fs_f(a, 3, s));
   return SMX_OK;
@@ -1154,19 +1128,8 @@ struct ConvWs { size_t fs = 0, pp = 0, rp = 0, total = 0, save = 0; };
 static bool conv_plan(const Shape& h, Plan* p) {
   // its own plan: tile spectra / columns / inverse tiles for n_fft = 512 ... 65536 (four columns of L values each
   // fit one thread's registers in backward up to L = 16; above that L / 16 threads share a column pair)
-  if (h.N % M != 0 || h.D % 2 != 0 || h.R > h.N) return false;
-  const int L = h.N / M;
-  if (!conv_tiles(L)) return false;
-  *p = Plan{};
-  p->path = SMX_PATH_DECIMATED; p->L = L; p->k = h.N / 2 + 1; p->nb = 4; p->groups = 1;
-  p->nwg = h.B * ((h.D + DT - 1) / DT);
-  int ns = 512 / p->nwg;
-  if (ns < 1) ns = 1;
-  if (ns > L) ns = L;
-  p->fs = true;
-  p->fs_lc = (L + ns - 1) / ns;
-  p->fs_nsplit = (L + p->fs_lc - 1) / p->fs_lc;
-  p->nsplit = 1; p->lc = L;
+  if (h.N % M != 0 || h.D % 2 != 0 || h.R > h.N || !conv_tiles(h.N / M)) return false;
+  *p = tile_plan(h);
   // One launch per direction where the zero padding allows it (k_conv1).  Its workgroup owns 32 channels (512 threads,
   // one per CU) or 16 (256 threads, two per CU, 64-byte row segments); measured, hipGraph fwd+bwd at n_fft 2048
   // (profiles/r03_f2_conv1_ab.txt), by the count w of (batch row, 32-channel tile) items:
@@ -1195,6 +1158,8 @@ static ConvWs conv_ws(const Plan& p, const Shape& h) {
   w.total = o;
   return w;
 }
+const char* const CONV_SHAPES = "smx_conv_* needs n_fft = 512 ... 65536 (a power of two), rows <= n_fft and an even "
+                                 "channel count";
 int conv_shape(const smx_shape* sh, Shape* h) {
   if (!sh) return fail(SMX_ERR_INVALID, "shape is NULL");
   *h = Shape{sh->B, sh->rows, sh->D, sh->n_fft / 2 + 1, sh->n_fft, sh->n_fft / 2 + 1};
@@ -1210,7 +1175,7 @@ int smx_conv_supported(const smx_shape* shape) {
 int smx_conv_workspace_bytes(const smx_shape* shape, size_t* workspace_bytes, size_t* save_bytes) {
   Shape h; Plan p;
   if (int rc = conv_shape(shape, &h)) return rc;
-  if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, "smx_conv_* needs n_fft = 512 ... 65536 (a power of two), rows <= n_fft and an even channel count");
+  if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, CONV_SHAPES);
   const ConvWs w = conv_ws(p, h);
   if (workspace_bytes) *workspace_bytes = w.total;
   if (save_bytes) *save_bytes = w.save;
@@ -1221,16 +1186,14 @@ int smx_conv_workspace_bytes(const smx_shape* shape, size_t* workspace_bytes, si
 // elem: bytes per element of x / y / g / grad_x (4; 2 for 2-byte rows, conv_forward_impl / conv_backward_impl)
 static int conv_args(const Shape& h, const Plan& p, const ConvWs& w, void* workspace, size_t workspace_bytes,
                      const float* h_re, const float* h_im, const float* row_scale, hipStream_t s, TableRef& t,
-                     DecimArgs* out, int elem = 4) {
-  if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 255))
-    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes", w.total);
+                     DecimArgs* out, int elem) {
+  if (int rc = need_ws(workspace, workspace_bytes, w.total, "")) return rc;
   if (!h_re || !h_im) return fail(SMX_ERR_INVALID, "h_re, h_im must be non-NULL");
   if (int rc = get_tables(h.N, &t, s)) return rc;
   Ws dummy;
   DecimArgs a = decim_args(p, t, h, (char*)workspace, dummy, elem);
   a.ws_z = a.ws_zs = a.ws_s = nullptr;
-  a.ws_f = (cf*)((char*)workspace + w.fs);
-  a.nsplit = p.fs_nsplit; a.lc = p.fs_lc;
+  use_tiles(a, p, (char*)workspace + w.fs);
   a.ca.h_re = h_re; a.ca.h_im = h_im; a.ca.sc = row_scale;
   a.ca.p_part = (cf*)((char*)workspace + w.pp);
   a.ca.r_part = (cf*)((char*)workspace + w.rp);
@@ -1249,7 +1212,7 @@ static int conv_forward_impl(const smx_shape* shape, const float* x, const float
                              size_t workspace_bytes, int io, void* stream) {
   Shape h; Plan p;
   if (int rc = conv_shape(shape, &h)) return rc;
-  if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, "smx_conv_* needs n_fft = 512 ... 65536 (a power of two), rows <= n_fft and an even channel count");
+  if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, CONV_SHAPES);
   if (io != SMX_IO_F32 && !p.conv1) return fail(SMX_ERR_UNSUPPORTED, "%s", CONV_IO_PLANS);
   if (!x || !y) return fail(SMX_ERR_INVALID, "x and y must be non-NULL");
   if (io != SMX_IO_F32) {
@@ -1291,7 +1254,7 @@ static int conv_backward_impl(const smx_shape* shape, const float* g, const floa
                               int io, void* stream) {
   Shape h; Plan p;
   if (int rc = conv_shape(shape, &h)) return rc;
-  if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, "smx_conv_* needs n_fft = 512 ... 65536 (a power of two), rows <= n_fft and an even channel count");
+  if (!conv_plan(h, &p)) return fail(SMX_ERR_UNSUPPORTED, CONV_SHAPES);
   if (io != SMX_IO_F32 && !p.conv1) return fail(SMX_ERR_UNSUPPORTED, "%s", CONV_IO_PLANS);
   if (!g || !x_spectra || !grad_x) return fail(SMX_ERR_INVALID, "g, x_spectra, grad_x must be non-NULL");
   if (io != SMX_IO_F32) {
@@ -1372,19 +1335,6 @@ int smx_conv_response_backward(int n_fft, int taps, int n_logits, const float* k
 }
 
 static int spectrum_impl(const Shape& h, const float* x, float* xk, void* workspace,
-                         size_t workspace_bytes, void* stream);
-int smx_spectrum(const float* x, float* xk, void* workspace, size_t workspace_bytes, int B, int N,
-                 int D, int F, void* stream) {
-  if (int rc = check_shape(B, N, D, F)) return rc;
-  return spectrum_impl(layer_shape(B, N, D, F), x, xk, workspace, workspace_bytes, stream);
-}
-int smx_spectrum_ex(const smx_shape* shape, const float* x, float* xk, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-  Shape h;
-  if (int rc = shape_from(shape, &h)) return rc;
-  return spectrum_impl(h, x, xk, workspace, workspace_bytes, stream);
-}
-static int spectrum_impl(const Shape& h, const float* x, float* xk, void* workspace,
                          size_t workspace_bytes, void* stream) {
   const int B = h.B, N = h.N, D = h.D;
   if (h.k == 0) return SMX_OK;
@@ -1396,77 +1346,72 @@ static int spectrum_impl(const Shape& h, const float* x, float* xk, void* worksp
   const Ws w = ws_layout(p, B, N, D);
   TableRef t;
   if (int rc = get_tables(N, &t, s)) return rc;
-  if (p.path == SMX_PATH_DECIM16) {
-    DecimArgs a = decim_args(p, t, h, (char*)workspace, w);
-    a.in = x; a.out = nullptr;
-    a.fa.xk_out = xk;
-    a.ws_s = nullptr;                        // nothing is parked (the workspace may be absent altogether)
+  if (p.kind == Kind::Direct) {
+    DirectArgs d = direct_args(p, t, h);
+    HIP_TRY(launch_direct_spectrum(x, (cf*)xk, d, s));
+    return SMX_OK;
+  }
+  if (p.nsplit > 1) if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
+  DecimArgs a = decim_args(p, t, h, (char*)workspace, w);
+  a.in = x; a.out = nullptr;
+  // mode 2: unpack only -- no weights are read, no S is produced
+  a.fa.xk_out = xk;
+  a.ws_s = nullptr;                          // nothing is parked (the workspace may be absent altogether)
+  if (p.kind == Kind::Sixteen) {
     if (p.nsplit == 1) {
       HIP_TRY(launch_fused16(a, p.nb, 2, s));
     } else {
-      if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
       HIP_TRY(launch_split16_a(a, p.nb, false, s));
       HIP_TRY(launch_split_f(a, p.nb, 2, s));
     }
-    return SMX_OK;
+  } else if (p.fs()) {
+    if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
+    use_tiles(a, p, (char*)workspace + w.fs);
+    HIP_TRY(launch_fs_a(a, s));
+    HIP_TRY(launch_fs_f(a, 2, s));
+  } else if (p.full8()) {
+    HIP_TRY(launch_full8(a, 2, s));
+  } else if (p.groups_only()) {
+    if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
+    for (int g = 0; g < p.groups; ++g) {
+      if (int rc = set_group(a, p, t, w, (char*)workspace, N, g, nullptr, s)) return rc;
+      a.ws_s = nullptr;
+      HIP_TRY(launch_fused(a, 4, 2, s));
+    }
+    DirectArgs e = edge_args(p, t, h);
+    e.rows = p.k;
+    HIP_TRY(launch_edge_spectrum(x, (cf*)xk, (double*)((char*)workspace + w.edgep), e, s));
+  } else if (p.kind == Kind::Single) {
+    HIP_TRY(launch_fused(a, p.nb, 2, s));
+  } else {
+    HIP_TRY(launch_split_a(a, p.nb, false, s));
+    HIP_TRY(launch_split_f(a, p.nb, 2, s));
   }
-  if (p.path == SMX_PATH_DECIMATED) {
-    if (p.nsplit > 1) if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
-    DecimArgs a = decim_args(p, t, h, (char*)workspace, w);
-    a.in = x; a.out = nullptr;
-    // mode 2: unpack only -- no weights are read, no S is produced
-    a.fa.xk_out = xk;
-    a.ws_s = nullptr;
-    if (p.fs) {
-      if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
-      a.ws_f = (cf*)((char*)workspace + w.fs); a.nsplit = p.fs_nsplit; a.lc = p.fs_lc;
-      HIP_TRY(launch_fs_a(a, s));
-      HIP_TRY(launch_fs_f(a, 2, s));
-      return SMX_OK;
-    }
-    if (p.full8) {
-      HIP_TRY(launch_full8(a, 2, s));
-      return SMX_OK;
-    }
-    if (p.groups > 1) {
-      if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
-      for (int g = 0; g < p.groups; ++g) {
-        if (int rc = set_group(a, p, t, w, (char*)workspace, N, g, nullptr, s)) return rc;
-        a.ws_s = nullptr;
-        HIP_TRY(launch_fused(a, 4, 2, s));
-      }
-      DirectArgs e = edge_args(p, t, h);
-      e.rows = p.k;
-      HIP_TRY(launch_edge_spectrum(x, (cf*)xk, (double*)((char*)workspace + w.edgep), e, s));
-      return SMX_OK;
-    }
-    if (p.nsplit == 1) HIP_TRY(launch_fused(a, p.nb, 2, s));
-    else {
-      HIP_TRY(launch_split_a(a, p.nb, false, s));
-      HIP_TRY(launch_split_f(a, p.nb, 2, s));
-    }
-    return SMX_OK;
-  }
-  DirectArgs d = direct_args(p, t, h);
-  HIP_TRY(launch_direct_spectrum(x, (cf*)xk, d, s));
   return SMX_OK;
 }
+int smx_spectrum(const float* x, float* xk, void* workspace, size_t workspace_bytes, int B, int N,
+                 int D, int F, void* stream) {
+  if (int rc = check_shape(B, N, D, F)) return rc;
+  return spectrum_impl(layer_shape(B, N, D, F), x, xk, workspace, workspace_bytes, stream);
+}
+int smx_spectrum_ex(const smx_shape* shape, const float* x, float* xk, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  Shape h;
+  if (int rc = shape_from(shape, &h)) return rc;
+  return spectrum_impl(h, x, xk, workspace, workspace_bytes, stream);
+}
 
-// N = 2048 with more than 512 bins (the reference's default causal-convolution length): the two halves of the
-// pair run as ONE launch each with the eight bands in registers -- the tensor and the spectrum cross HBM once
+// N = 2048 with more than 512 bins (the reference's default causal-convolution length, Plan::pair8): the two halves of
+// the pair run as ONE launch each with the eight bands in registers -- the tensor and the spectrum cross HBM once
 // (measured at (64,1024,512): rfft 153 us against 203 us on the four-step path, which round-trips a workspace).
 // These two launches touch no workspace (none is required, whatever smx_workspace_bytes_ex says for the filter
 // plans of the same shape); option full8 = 0 sends the pair down the four-step path like every other length.
-static bool pair_full8(const Plan& p) {
-  return p.path == SMX_PATH_DECIMATED && p.L == 8 && p.k > 512 && cur_opts().full8 != 0;
-}
-
 int smx_rfft_ex(const smx_shape* shape, const float* x, float* spec, float scale, int hermitian,
                 void* workspace, size_t workspace_bytes, void* stream) {
   Shape h;
   if (int rc = shape_from(shape, &h)) return rc;
   const Plan p8 = make_plan(h);
-  if (h.k > 0 && pair_full8(p8)) {
+  if (h.k > 0 && p8.pair8) {
     if (!x || !spec) return fail(SMX_ERR_INVALID, "x and spec must be non-NULL");
     if (((uintptr_t)x & 7) || ((uintptr_t)spec & 15))
       return fail(SMX_ERR_INVALID, "x must be 8-byte and spec 16-byte aligned");
@@ -1501,24 +1446,21 @@ int smx_irfft_ex(const smx_shape* shape, const float* spec, float* y, float scal
   TableRef t;
   if (int rc = get_tables(N, &t, s)) return rc;
   char* ws = (char*)workspace;
-  if (p.path == SMX_PATH_DECIMATED && (p.fs || p.groups == 1 || pair_full8(p))) {
-    const bool l8 = pair_full8(p);
-    if (!l8 && (p.fs || p.nsplit > 1)) if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
+  if (p.row_scale() || p.pair8) {      // (the kinds with synthesis kernels: up to 512 bins, four-step, the pair's eight bands)
+    if (!p.pair8 && (p.fs() || p.nsplit > 1)) if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
     DecimArgs a = decim_args(p, t, h, ws, w);
     a.in = nullptr; a.out = y;
     a.fa.xk_in = spec; a.fa.sp_scale = scale; a.fa.sp_herm = hermitian;
-    if (l8) {
+    if (p.pair8) {
       HIP_TRY(launch_synth8(a, s));
-    } else if (p.fs) {
-      a.ws_f = (cf*)(ws + w.fs); a.nsplit = p.fs_nsplit; a.lc = p.fs_lc;
+    } else if (p.fs()) {
+      use_tiles(a, p, ws + w.fs);
       HIP_TRY(launch_fs_f(a, 4, s));
       HIP_TRY(launch_fs_b(a, s));
     } else if (p.nsplit == 1) {
       HIP_TRY(launch_synth(a, p.nb, s));
     } else {
-      DecimArgs park = a;
-      park.out = nullptr;
-      HIP_TRY(launch_synth(park, p.nb, s));
+      HIP_TRY(launch_synth(no_out(a), p.nb, s));
       HIP_TRY(launch_split_b(a, p.nb, false, s));
     }
     return SMX_OK;
@@ -1527,8 +1469,7 @@ int smx_irfft_ex(const smx_shape* shape, const float* spec, float* y, float scal
   // not take) -- weighted copy of the spectrum in the workspace, then the synthesis kernels of the direct path
   if (int rc = need_ws(w, workspace, workspace_bytes)) return rc;
   cf* sk = (cf*)(ws + (p.path == SMX_PATH_DECIMATED ? w.slab : w.spec1));
-  DirectArgs d{B, N, D, h.F, p.k, t.tw};
-  d.R = h.R;
+  DirectArgs d = direct_args(p, t, h);
   HIP_TRY(launch_scale_bins((const cf*)spec, sk, B, p.k, D, N, scale, hermitian, s));
   HIP_TRY(launch_direct_synth(sk, nullptr, y, d, s));
   return SMX_OK;
@@ -1594,38 +1535,11 @@ int smx_rng_next(void* state, void* saved, void* stream) {
 
 int smx_block_supported(int D) { return ln_supported(D) ? 1 : 0; }
 
-int smx_block_forward(const float* x, const float* ln_w, const float* ln_b, float eps,
-                      const float* w_re, const float* w_im, const float* bias, float* y,
-                      float* xk_save, float* ln_stats, void* workspace, size_t workspace_bytes,
-                      int B, int N, int D, int F, void* stream) {
-  return smx_block_forward_dropout(x, ln_w, ln_b, eps, w_re, w_im, bias, y, xk_save, ln_stats,
-                                   workspace, workspace_bytes, B, N, D, F, 0.f, nullptr, nullptr,
-                                   stream);
-}
-
 // The fused block with 2-byte x / y / g / grad_x exists where k_fused_blk does -- the decimated single-launch plan --
 // and where the row kernels move 2-byte chunks (ln_io_supported: D % 4 == 0).
-static bool block_fused_plan(const Plan& p) {
-  return p.path == SMX_PATH_DECIMATED && p.nsplit == 1 && p.groups == 1 && !p.fs && !p.full8;
-}
-static bool block_io_native(const Plan& p, int D) { return block_fused_plan(p) && io_native(p) && ln_io_supported(D); }
+static bool block_io_native(const Plan& p, int D) { return p.block_fused() && ln_io_supported(D); }
 static const char* const BLOCK_IO_PLANS = "no 2-byte block rows on this plan (smx_block_io_supported: the decimated "
                                           "single-launch plan, D %% 4 == 0): widen the input and call the f32 entry";
-
-static int block_forward_impl(const float* x, const float* ln_w, const float* ln_b, float eps,
-                              const float* w_re, const float* w_im, const float* bias, float* y,
-                              float* xk_save, float* ln_stats, void* workspace,
-                              size_t workspace_bytes, int B, int N, int D, int F, float dropout_p,
-                              const void* rng_state, float* filter_pack, void* stream, int io);
-
-int smx_block_forward_dropout(const float* x, const float* ln_w, const float* ln_b, float eps,
-                              const float* w_re, const float* w_im, const float* bias, float* y,
-                              float* xk_save, float* ln_stats, void* workspace,
-                              size_t workspace_bytes, int B, int N, int D, int F, float dropout_p,
-                              const void* rng_state, float* filter_pack, void* stream) {
-  return block_forward_impl(x, ln_w, ln_b, eps, w_re, w_im, bias, y, xk_save, ln_stats, workspace, workspace_bytes, B, N,
-                            D, F, dropout_p, rng_state, filter_pack, stream, SMX_IO_F32);
-}
 
 // io: element type of x and y (2-byte rows behind the float pointers, as in forward_impl)
 static int block_forward_impl(const float* x, const float* ln_w, const float* ln_b, float eps,
@@ -1637,8 +1551,9 @@ static int block_forward_impl(const float* x, const float* ln_w, const float* ln
   DropCfg dc;
   if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
   if (!ln_supported(D)) return fail(SMX_ERR_UNSUPPORTED, "LayerNorm width D=%d is not supported", D);
-  if (io != SMX_IO_F32 && !block_io_native(make_plan(layer_shape(B, N, D, F)), D))
-    return fail(SMX_ERR_UNSUPPORTED, BLOCK_IO_PLANS);
+  const Shape h = layer_shape(B, N, D, F);
+  const Plan p = make_plan(h);
+  if (io != SMX_IO_F32 && !block_io_native(p, D)) return fail(SMX_ERR_UNSUPPORTED, BLOCK_IO_PLANS);
   if (!x || !w_re || !w_im || !y || !ln_stats)
     return fail(SMX_ERR_INVALID, "x, w_re, w_im, y, ln_stats must be non-NULL");
   if (x == y) return fail(SMX_ERR_INVALID, "y must not alias x");
@@ -1655,37 +1570,30 @@ static int block_forward_impl(const float* x, const float* ln_w, const float* ln
   if ((uintptr_t)xk_save & 15) return fail(SMX_ERR_INVALID, "xk_save must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const long long rows = (long long)B * N;
-  const Shape h = layer_shape(B, N, D, F);
-  const Plan p = make_plan(h);
-  const bool by_groups = p.groups > 1 && !p.fs && !p.full8;
   if (io != SMX_IO_F32) HIP_TRY(launch_ln_stats_io(x, (cf*)ln_stats, rows, D, eps, s, io));
   else HIP_TRY(launch_ln_stats(x, (cf*)ln_stats, rows, D, eps, s));
-  if (block_fused_plan(p)) {
+  if (p.block_fused()) {
     TableRef t;
     if (int rc = get_tables(N, &t, s)) return rc;
     const Ws w = ws_layout(p, B, N, D);
     DecimArgs a = decim_args(p, t, h, (char*)workspace, w, io != SMX_IO_F32 ? 2 : 4);
     a.in = x; a.out = y;
-    a.fa.w_re = w_re; a.fa.w_im = w_im; a.fa.bias = bias; a.fa.conj_w = 0;
-    a.fa.xk_out = xk_save;
+    filter_fwd(a, w_re, w_im, bias, 0, xk_save);
     a.ln_stats = (const cf*)ln_stats; a.ln_w = ln_w; a.ln_b = ln_b;
     set_drop(a, dc);
     if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F, nullptr, filter_pack,
                              s))
       return rc;
-    if (workspace && workspace_bytes >= w.total && !((uintptr_t)workspace & 255) &&
-        sync_words(B, D) * sizeof(unsigned) <= SYNC_BYTES)
-      a.sync = (unsigned*)((char*)workspace + w.sync);        // left zero for smx_block_backward (SYNC_CLEAN)
+    use_sync(a, w, workspace, workspace_bytes);                // left zero for smx_block_backward (SYNC_CLEAN)
     HIP_TRY(launch_fused_block(a, p.nb, s, io));
     return SMX_OK;
   }
   // other plans: normalise into y, transform y in place (every kernel reads its whole input column
   // before the first store to it), add x
   float* hbuf = y;
-  if (by_groups) {          // no in-place form there: LayerNorm(x) goes to the workspace's row copy
+  if (p.groups_only()) {    // no in-place form there: LayerNorm(x) goes to the workspace's row copy
     const Ws w = ws_layout(p, B, N, D);
-    if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 255))
-      return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes", w.total);
+    if (int rc = need_ws(workspace, workspace_bytes, w.total, "")) return rc;
     hbuf = (float*)((char*)workspace + w.rows);
   }
   HIP_TRY(launch_ln_apply(x, (const cf*)ln_stats, ln_w, ln_b, hbuf, rows, D, s));
@@ -1694,6 +1602,22 @@ static int block_forward_impl(const float* x, const float* ln_w, const float* ln
     return rc;
   HIP_TRY(launch_add_rows(y, x, (size_t)rows * D, s));
   return SMX_OK;
+}
+int smx_block_forward_dropout(const float* x, const float* ln_w, const float* ln_b, float eps,
+                              const float* w_re, const float* w_im, const float* bias, float* y,
+                              float* xk_save, float* ln_stats, void* workspace,
+                              size_t workspace_bytes, int B, int N, int D, int F, float dropout_p,
+                              const void* rng_state, float* filter_pack, void* stream) {
+  return block_forward_impl(x, ln_w, ln_b, eps, w_re, w_im, bias, y, xk_save, ln_stats, workspace, workspace_bytes, B, N,
+                            D, F, dropout_p, rng_state, filter_pack, stream, SMX_IO_F32);
+}
+int smx_block_forward(const float* x, const float* ln_w, const float* ln_b, float eps,
+                      const float* w_re, const float* w_im, const float* bias, float* y,
+                      float* xk_save, float* ln_stats, void* workspace, size_t workspace_bytes,
+                      int B, int N, int D, int F, void* stream) {
+  return smx_block_forward_dropout(x, ln_w, ln_b, eps, w_re, w_im, bias, y, xk_save, ln_stats,
+                                   workspace, workspace_bytes, B, N, D, F, 0.f, nullptr, nullptr,
+                                   stream);
 }
 
 int smx_block_backward(const float* g, const float* x, const float* ln_stats, const float* ln_w,
@@ -1742,10 +1666,12 @@ static int dw_check(int B, int T, int C) {
     return fail(SMX_ERR_UNSUPPORTED, "smx_dwconv3_*: tensor too large for one launch");
   return SMX_OK;
 }
+// (the workspaces of the small ops lie behind the sync area, as every layout: ws_layout)
+static size_t dw_need(int B, int T, int C) { return SYNC_BYTES + al(dwconv3_workspace_bytes(B, T, C)); }
 int smx_dwconv3_workspace_bytes(int B, int T, int C, size_t* out) {
   if (!out) return fail(SMX_ERR_INVALID, "out is NULL");
   if (int rc = dw_check(B, T, C)) return rc;
-  *out = SYNC_BYTES + al(dwconv3_workspace_bytes(B, T, C));          // behind the sync area, as every layout (ws_layout)
+  *out = dw_need(B, T, C);
   return SMX_OK;
 }
 int smx_dwconv3_forward(const float* x, const float* w, const float* bias, const float* scale, float* y, int B, int T,
@@ -1763,9 +1689,7 @@ int smx_dwconv3_backward(const float* g, const float* x, const float* w, const f
   if (!g || !x || !w) return fail(SMX_ERR_INVALID, "g, x, w must be non-NULL");
   if (grad_x == g || grad_x == x) return fail(SMX_ERR_INVALID, "grad_x must not alias g or x");
   if (grad_scale && !scale) return fail(SMX_ERR_INVALID, "grad_scale without scale");
-  const size_t need = SYNC_BYTES + al(dwconv3_workspace_bytes(B, T, C));
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
-    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes (smx_dwconv3_workspace_bytes)", need);
+  if (int rc = need_ws(workspace, workspace_bytes, dw_need(B, T, C), "smx_dwconv3_workspace_bytes")) return rc;
   HIP_TRY(launch_dwconv3_bwd(g, x, w, bias, scale, grad_x, grad_w, grad_bias, grad_scale,
                              (float*)((char*)workspace + SYNC_BYTES), B, T, C, (hipStream_t)stream));
   return SMX_OK;
@@ -1835,10 +1759,11 @@ static int gate_check(int B, int F, int C) {
   if (B > 65535) return fail(SMX_ERR_UNSUPPORTED, "smx_spectral_gate_* takes at most 65535 batch rows");
   return SMX_OK;
 }
+static size_t gate_need(int B, int F, int C) { return SYNC_BYTES + al(gate_workspace_bytes(B, F, C)); }
 int smx_spectral_gate_workspace_bytes(int B, int F, int C, size_t* out) {
   if (int rc = gate_check(B, F, C)) return rc;
   if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
-  *out = SYNC_BYTES + al(gate_workspace_bytes(B, F, C));            // behind the sync area, as every layout (ws_layout)
+  *out = gate_need(B, F, C);
   return SMX_OK;
 }
 int smx_spectral_gate_forward(const float* x, const float* a, const float* u, const float* p, const float* q,
@@ -1858,18 +1783,17 @@ int smx_spectral_gate_backward(const float* g, const float* x, const float* a, c
   if (((uintptr_t)g | (uintptr_t)x | (uintptr_t)grad_x) & 15) return fail(SMX_ERR_INVALID, "g, x, grad_x must be 16-byte aligned");
   if (((uintptr_t)a | (uintptr_t)s1) & 7) return fail(SMX_ERR_INVALID, "a and s1 must be 8-byte aligned");
   if (grad_x == g || grad_x == x) return fail(SMX_ERR_INVALID, "grad_x must not alias g or x");
-  const size_t need = SYNC_BYTES + al(gate_workspace_bytes(B, F, C));
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
-    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes (smx_spectral_gate_workspace_bytes)", need);
+  if (int r = need_ws(workspace, workspace_bytes, gate_need(B, F, C), "smx_spectral_gate_workspace_bytes")) return r;
   HIP_TRY(launch_gate_bwd((const cf*)g, (const cf*)x, (const cf*)a, u, p, q, m, (cf*)grad_x, (cf*)s1, rc, rp,
                           (cf*)((char*)workspace + SYNC_BYTES), B, F, C, (hipStream_t)stream));
   return SMX_OK;
 }
 
 // ---- BicameralBlock's fusion line (smx_time.hip) --------------------------------------------------------------------------
+static size_t mix_need() { return SYNC_BYTES + al(mix_workspace_bytes()); }
 int smx_mix_workspace_bytes(size_t* out) {
   if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
-  *out = SYNC_BYTES + al(mix_workspace_bytes());
+  *out = mix_need();
   return SMX_OK;
 }
 static int mix_check(long long n, const void* p0, const void* p1, const void* p2, const void* p3, const void* p4) {
@@ -1890,9 +1814,7 @@ int smx_mix_backward(const float* g, const float* a, const float* b, const float
   if (!g || !a || !b || !w) return fail(SMX_ERR_INVALID, "g, a, b, w must be non-NULL");
   if (int rc = mix_check(n, g, a, b, grad_a, grad_b)) return rc;
   if ((uintptr_t)grad_c & 15) return fail(SMX_ERR_INVALID, "tensors must be 16-byte aligned");
-  const size_t need = SYNC_BYTES + al(mix_workspace_bytes());
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
-    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes (smx_mix_workspace_bytes)", need);
+  if (int rc = need_ws(workspace, workspace_bytes, mix_need(), "smx_mix_workspace_bytes")) return rc;
   HIP_TRY(launch_mix_bwd(g, a, b, w, c3, grad_a, grad_b, grad_c, grad_w, (float*)((char*)workspace + SYNC_BYTES), n,
                          (hipStream_t)stream));
   return SMX_OK;
@@ -1901,10 +1823,11 @@ int smx_mix_backward(const float* g, const float* a, const float* b, const float
 
 // ---- EnhancedSpectralBlock row lines (smx_enh.hip) ----
 int smx_enh_supported(int D) { return enh_supported(D) ? 1 : 0; }
+static size_t enh_need(int B, int T, int D) { return SYNC_BYTES + al(enh_part_floats((long long)B * T, D) * sizeof(float)); }
 int smx_enh_workspace_bytes(int B, int T, int D, size_t* out) {
   if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
   if (B <= 0 || T <= 0 || D <= 0) return fail(SMX_ERR_INVALID, "shape must be positive: B=%d T=%d D=%d", B, T, D);
-  *out = SYNC_BYTES + al(enh_part_floats((long long)B * T, D) * sizeof(float));
+  *out = enh_need(B, T, D);
   return SMX_OK;
 }
 static int enh_check(int B, int T, int D, std::initializer_list<const void*> ptrs) {
@@ -1915,9 +1838,7 @@ static int enh_check(int B, int T, int D, std::initializer_list<const void*> ptr
   return SMX_OK;
 }
 static int enh_ws(void* workspace, size_t workspace_bytes, int B, int T, int D, float** part) {
-  const size_t need = SYNC_BYTES + al(enh_part_floats((long long)B * T, D) * sizeof(float));
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
-    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes (smx_enh_workspace_bytes)", need);
+  if (int rc = need_ws(workspace, workspace_bytes, enh_need(B, T, D), "smx_enh_workspace_bytes")) return rc;
   *part = (float*)((char*)workspace + SYNC_BYTES);
   return SMX_OK;
 }
@@ -2017,7 +1938,7 @@ int smx_gate_blend_backward(const float* g3, const float* a, const float* v, con
 int smx_io_supported(int B, int N, int D, int F, int io) {
   if (io_check(io) || check_shape(B, N, D, F)) return 0;
   if (io == SMX_IO_F32) return 1;
-  return io_native(make_plan(layer_shape(B, N, D, F))) ? 1 : 0;
+  return make_plan(layer_shape(B, N, D, F)).io_native() ? 1 : 0;
 }
 
 int smx_forward_io(const void* x, const float* w_re, const float* w_im, const float* bias, void* y,
@@ -2037,7 +1958,7 @@ int smx_backward_io(const void* g, const float* xk, const float* w_re, const flo
   if (int rc = check_shape(B, N, D, F)) return rc;
   return backward_impl(layer_shape(B, N, D, F), (const float*)g, xk, w_re, w_im, (float*)grad_x, gw_re, gw_im, gbias,
                        workspace, workspace_bytes, phases, dropout_p, rng_state, filter_pack, stream, nullptr, nullptr,
-                       io);
+                       io, -1);
 }
 
 // ---- 2-byte activations of the convolution (bf16 / fp16 x, y, g, grad_x) -------------------------------------------
@@ -2160,9 +2081,7 @@ static int ema_bwd(const EmaSrc& src, int mode, const float* g, const float* ini
   if (((uintptr_t)g | (uintptr_t)init | (uintptr_t)grad_chunks | (uintptr_t)grad_init) & 7)
     return fail(SMX_ERR_INVALID, "g, init, grad_chunks, grad_init must be 8-byte aligned");
   if (grad_chunks && grad_chunks == src.ptr) return fail(SMX_ERR_INVALID, "grad_chunks must not alias chunks");
-  const size_t need = ema_need(src.B, src.S, src.F);
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
-    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes (smx_ema_workspace_bytes)", need);
+  if (int rc = need_ws(workspace, workspace_bytes, ema_need(src.B, src.S, src.F), "smx_ema_workspace_bytes")) return rc;
   char* states = (char*)workspace + SYNC_BYTES;
   HIP_TRY(launch_ema_bwd(src, mode == SMX_EMA_POLAR, (const cf*)g, (const cf*)init, rho_logit, theta_raw, (cf*)grad_chunks,
                          (cf*)grad_init, grad_rho_logit, grad_theta_raw, (cf*)states,
@@ -2172,7 +2091,7 @@ static int ema_bwd(const EmaSrc& src, int mode, const float* g, const float* ini
 int smx_ema_workspace_bytes(int B, int S, int F, size_t* out) {
   if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
   if (int rc = ema_check(SMX_EMA_ALIGNED, B, S, F)) return rc;
-  *out = ema_need(B, S, F);                                         // behind the sync area, as every layout (ws_layout)
+  *out = ema_need(B, S, F);
   return SMX_OK;
 }
 int smx_ema_scan_forward(const float* chunks, const float* init, const float* rho_logit, const float* theta_raw,
