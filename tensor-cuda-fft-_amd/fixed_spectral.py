@@ -21,8 +21,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from . import _lib
-from .functional import _stream, conv_response, conv_supported, hermitian_scale, rank_one_conv, spectral_filter
+from .functional import _call, _stream, conv_response, conv_supported, hermitian_scale, rank_one_conv, spectral_filter
 
 
 def next_pow2(n: int) -> int:
@@ -208,9 +207,8 @@ class FrequencyConvFunc(torch.autograd.Function):
         x = x_freq.resolve_conj().contiguous()
         w = (kernel_freq.to(torch.complex64).unsqueeze(1) * gain.unsqueeze(0)).contiguous()    # (F, C)
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().smx_cmul(x.data_ptr(), w.data_ptr(), out.data_ptr(), x.shape[0],
-                                           w.numel(), 0, _stream(x.device)))
+        _call(x.device, "smx_cmul", x.data_ptr(), w.data_ptr(), out.data_ptr(), x.shape[0], w.numel(), 0,
+              _stream(x.device))
         ctx.save_for_backward(x, kernel_freq, gain, w)
         return out
 
@@ -224,12 +222,10 @@ class FrequencyConvFunc(torch.autograd.Function):
         s_conj = torch.empty_like(w)          # sum_b g * conj(x)
         s_plain = torch.empty_like(w)         # sum_b g * x
         xc = x.conj().resolve_conj()
-        with torch.cuda.device(x.device):
-            s = _stream(x.device)
-            lib = _lib.lib()
-            _lib.check(lib.smx_cmul(g.data_ptr(), w.data_ptr(), grad_x.data_ptr(), B, inner, 1, s))     # :111
-            _lib.check(lib.smx_cmul_grad_w(x.data_ptr(), g.data_ptr(), s_conj.data_ptr(), B, inner, s))
-            _lib.check(lib.smx_cmul_grad_w(xc.data_ptr(), g.data_ptr(), s_plain.data_ptr(), B, inner, s))
+        s = _stream(x.device)
+        _call(x.device, "smx_cmul", g.data_ptr(), w.data_ptr(), grad_x.data_ptr(), B, inner, 1, s)     # :111
+        _call(x.device, "smx_cmul_grad_w", x.data_ptr(), g.data_ptr(), s_conj.data_ptr(), B, inner, s)
+        _call(x.device, "smx_cmul_grad_w", xc.data_ptr(), g.data_ptr(), s_plain.data_ptr(), B, inner, s)
         grad_kernel = (s_conj * gain.unsqueeze(0)).sum(dim=1)                                 # :114
         grad_gain = (s_plain * kernel_freq.unsqueeze(1)).real.sum(dim=0)                      # :117
         return grad_x, grad_kernel, grad_gain

@@ -5,6 +5,9 @@ hot path runs in libsmx.so's HIP kernels on torch's current stream.
 """
 from __future__ import annotations
 
+import ctypes
+import functools
+import warnings
 from typing import Optional
 
 import torch
@@ -18,8 +21,6 @@ def _under_forward_options(backward):
     (`with _lib.options(...)`, thread-local) are not in force: forward and backward of one node would plan
     differently -- other kernels, another workspace layout for the workspace forward hands over.  Every Function
     below notes the options its forward ran under (ctx.smx_opts) and re-applies them around its backward."""
-    import functools
-
     @functools.wraps(backward)
     def wrapped(ctx, *args):
         o = getattr(ctx, "smx_opts", None)
@@ -34,27 +35,61 @@ def _under_forward_options(backward):
 _IO = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
-def _require_gpu_io(name: str, t: torch.Tensor) -> None:
-    """fp32, bf16 or fp16 on a ROCm device (the activations spectral_mix takes)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise RuntimeError(
-            f"{name} is on {t.device}: the MI355X spectral-mixing path has no CPU implementation "
-            f"(move the module and its input to a ROCm device)")
-    if t.dtype not in _IO:
-        raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype} (the kernels compute in fp32)")
+_F32 = (torch.float32,)
+_C64 = (torch.complex64,)
+_ACT = tuple(_IO)
+_DTYPE_TEXT = {_ACT: "float32, bfloat16 or float16", _F32: "float32", _C64: "complex64"}
+_MIX_PATH = "the MI355X spectral-mixing path has no CPU implementation (move the module and its input to a ROCm device)"
+_ANY_PATH = "the MI355X path has no CPU implementation"
 
 
-def _require_gpu_f32(name: str, t: torch.Tensor) -> None:
-    if not isinstance(t, torch.Tensor):
+def _require(name: str, t, dtypes=_F32, path: str = _MIX_PATH, what: Optional[str] = None, dim: Optional[int] = None,
+             typed: bool = True):
+    """`t` is a tensor on a ROCm device with one of `dtypes` (None: any; _ACT: the activations spectral_mix takes).
+    `path`: the sentence of the device error.  `what` ("a (B, F, C) complex64 tensor"): the ops that describe
+    their operand in one sentence raise that one TypeError for a wrong type, device, dtype or rank `dim`.
+    typed=False: the ops that never asked whether `t` is a tensor at all -- a non-tensor fails on the first attribute
+    read (dtype in the `what` form, is_cuda otherwise) with Python's AttributeError, as it always did there."""
+    if what is not None:
+        if not ((not typed or isinstance(t, torch.Tensor)) and t.dtype in dtypes and t.is_cuda
+                and dim in (None, t.dim())):
+            raise TypeError(f"{name} must be {what} on a ROCm device")
+        return
+    if typed and not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if not t.is_cuda:
-        raise RuntimeError(
-            f"{name} is on {t.device}: the MI355X spectral-mixing path has no CPU implementation "
-            f"(move the module and its input to a ROCm device)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype} (the kernels compute in fp32)")
+        raise RuntimeError(f"{name} is on {t.device}: {path}")
+    if dtypes is not None and t.dtype not in dtypes:
+        raise TypeError(f"{name} must be {_DTYPE_TEXT[dtypes]}, got {t.dtype}"
+                        + ("" if dtypes == _C64 else " (the kernels compute in fp32)"))
+
+
+def _check_filter(x: torch.Tensor, w_re: torch.Tensor, w_im: torch.Tensor) -> None:
+    if w_re.shape != w_im.shape or w_re.dim() != 2 or w_re.shape[0] != x.shape[2]:
+        raise ValueError("weights must both be (D, num_filters)")
+
+
+# bf16 / fp16 activations take two steps, the same for every op that has them: the parameters are read as fp32
+# (_fp32_params), and the op runs its native 2-byte rows where the library has them for the shape (_half_native) and
+# itself on x.float(), rounded once with .to(x.dtype), everywhere else.
+def _fp32_params(x: torch.Tensor, params, required: int = 0) -> tuple:
+    """The parameters ((name, tensor or None), ...) beside the activations x, as fp32: they must be fp32 beside an fp32
+    x, and fp32 or x's dtype beside a bf16 / fp16 x (`.float()`, so autograd returns their gradients in their own
+    dtype).  Beside an fp32 x the first `required` may not be None."""
+    half = x.dtype != torch.float32
+    for i, (name, t) in enumerate(params):
+        if t is None and (half or i >= required):
+            continue
+        _require(name, t, _ACT if half else _F32)
+        if half and t.dtype not in (torch.float32, x.dtype):
+            raise TypeError(f"{name} must be float32 or {x.dtype} like x, got {t.dtype}")
+    return tuple(t.float() if half and t is not None else t for _, t in params)
+
+
+def _half_native(x: torch.Tensor, memo: "_Memo", shape: tuple, supported) -> bool:
+    """Does the library run this shape with x's 2-byte rows natively?  `supported(*shape, io)`, memoised per shape,
+    dtype and plan options."""
+    return bool(memo.get(shape + (x.dtype,), lambda: supported(*shape, _IO[x.dtype])))
 
 
 # One workspace per (device, stream): calls on the same stream are ordered, so reuse is safe.
@@ -66,10 +101,10 @@ _ws_cache: dict = {}
 _WS_CACHE_MAX = 16                      # (device, stream) pairs kept; least recently used goes first
 
 
-def _raw_stream(dev: torch.device) -> int:
+def _stream(dev: torch.device) -> int:
     """The hipStream_t of torch's current stream on `dev` as an integer (the raw C query: torch.cuda.current_stream
     builds a Stream object, ~8 us a call, four calls per eager fwd+bwd: host cost of a small step 0.18-0.22 -> 0.145-0.19 ms,
-    A/B in one gpurun call, the spread being the shared host CPUs)."""
+    A/B in one run, the spread being the shared host CPUs)."""
     return torch._C._cuda_getCurrentRawStream(dev.index)
 
 
@@ -78,7 +113,7 @@ def _workspace(dev: torch.device, nbytes: int) -> Optional[torch.Tensor]:
         return None
     if torch._C._cuda_isCurrentStreamCapturing():
         return torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    key = (dev.index, _raw_stream(dev))
+    key = (dev.index, _stream(dev))
     ws = _ws_cache.pop(key, None)
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -140,8 +175,7 @@ def _prepare(dev: torch.device, N: int) -> None:
         _prepared_epoch[0] = ep
     key = (dev.index, int(N))
     if key not in _prepared:
-        with _on_device(dev):
-            _lib.check(_lib.lib().smx_prepare(int(N)))
+        _call(dev, "smx_prepare", int(N))
         _prepared.add(key)
 
 
@@ -171,7 +205,6 @@ def _note_plan(p, B: int, R: int, D: int, n_fft: int) -> None:
         return
     if why[0] not in _slow_plan_warned:
         _slow_plan_warned.add(why[0])
-        import warnings
         warnings.warn("tensor_cuda_fft_amd: " + why[1], RuntimeWarning, stacklevel=4)
 
 
@@ -181,21 +214,6 @@ def _ws_bytes(B: int, N: int, D: int, F: int) -> int:
         _note_plan(_lib.plan(B, N, D, F), B, N, D, N)
         return _lib.workspace_bytes(B, N, D, F)
     return _ws_bytes_cache.get((B, N, D, F), make)
-
-
-class _on_device:
-    """`with torch.cuda.device(dev)` only when dev is not already current (it is the slow part of a call)."""
-
-    def __init__(self, dev: torch.device):
-        self.ctx = None if dev.index == torch.cuda.current_device() else torch.cuda.device(dev)
-
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
-
-    def __exit__(self, *a):
-        if self.ctx is not None:
-            self.ctx.__exit__(*a)
 
 
 def _dense(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -213,8 +231,49 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
-def _stream(dev: torch.device) -> int:
-    return _raw_stream(dev)
+def _ws_arg(ws: Optional[torch.Tensor]) -> tuple:
+    """the (workspace, workspace_bytes) argument pair"""
+    return (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
+
+
+def _call(dev: torch.device, name: str, *args) -> None:
+    """One native call on `dev`: the entry point is looked up on the library object by name at every call (tests
+    wrap entry points there), a non-zero return code raises SmxError.  The caller places _stream(dev) among `args`."""
+    if dev.index == torch.cuda.current_device():
+        _lib.check(getattr(_lib.lib(), name)(*args))
+    else:                    # (`with torch.cuda.device` is the slow part of a call: only when dev is not current)
+        with torch.cuda.device(dev):
+            _lib.check(getattr(_lib.lib(), name)(*args))
+
+
+def _query(name: str, *args, outs: int = 1, unsupported: Optional[int] = None):
+    """The size_t out-parameters of a *_workspace_bytes entry: an int, or a tuple for `outs` > 1.  `unsupported`:
+    the answer where the entry refuses the shape (default: raise)."""
+    out = [ctypes.c_size_t() for _ in range(outs)]
+    rc = getattr(_lib.lib(), name)(*args, *(ctypes.byref(o) for o in out))
+    if rc != 0 and unsupported is not None:
+        return unsupported
+    _lib.check(rc)
+    return int(out[0].value) if outs == 1 else tuple(int(o.value) for o in out)
+
+
+def _grad_f32(g: torch.Tensor) -> torch.Tensor:
+    """upstream gradient as dense fp32"""
+    return _dense(g if g.dtype == torch.float32 else g.float())
+
+
+def _grad_c64(g: torch.Tensor) -> torch.Tensor:
+    """upstream gradient as dense complex64"""
+    return _dense(g.to(torch.complex64))
+
+
+def _grad_slab(D: int, F: int, dev=None, flat: Optional[torch.Tensor] = None):
+    """The parameter gradients of one filter live in ONE fp32 buffer [gw_re (D F) | gw_im (D F) | gbias (D)], so a
+    single collective reduces all three: (flat, gw_re, gw_im, gbias), the three as views of `flat` (allocated here
+    unless given)."""
+    if flat is None:
+        flat = torch.empty(2 * D * F + D, dtype=torch.float32, device=dev)
+    return flat, flat[:D * F], flat[D * F:2 * D * F], flat[2 * D * F:]
 
 
 def num_bins(N: int, F: int) -> int:
@@ -244,6 +303,17 @@ def _check_p(p: float) -> float:
     return p
 
 
+def _check_dropout(p: float, drop_state) -> float:
+    p = _check_p(p)
+    if p > 0.0 and drop_state is None:
+        raise ValueError("dropout_p > 0 needs a DropoutState")
+    return p
+
+
+_ODD_D_PAD_MIN = 1 << 18        # below this the literal kernels of the direct plan are launch-bound anyway
+_io_cache = _Memo()
+
+
 def forward_raw(x, w_re, w_im, bias, *, conj_w=False, save_spectrum=False, dropout_p=0.0, rng=None,
                 pack=None, pack_ready=False, ws=None, io=0):
     """y, xk = smx_forward[_dropout](...).  x (B,N,D) contiguous f32 on GPU; returns xk (B,k,D) c64 or
@@ -260,13 +330,14 @@ def forward_raw(x, w_re, w_im, bias, *, conj_w=False, save_spectrum=False, dropo
     _prepare(x.device, N)
     if ws is None:
         ws = _workspace(x.device, _ws_bytes(B, N, D, F))
-    with _on_device(x.device):
-        args = (x.data_ptr(), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(xk),
-                _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F,
-                int(bool(conj_w)) | (2 if pack_ready else 0), float(dropout_p), _ptr(rng), _ptr(pack),
-                _stream(x.device))
-        # (2-byte rows through the _io entry, f32 through the f32 entry: the tests tell the routes apart by the call)
-        _lib.check(_lib.lib().smx_forward_io(*args, int(io)) if io else _lib.lib().smx_forward_dropout(*args))
+    args = (x.data_ptr(), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(xk), *_ws_arg(ws),
+            B, N, D, F, int(bool(conj_w)) | (2 if pack_ready else 0), float(dropout_p), _ptr(rng), _ptr(pack),
+            _stream(x.device))
+    # (2-byte rows through the _io entry, f32 through the f32 entry: the tests tell the routes apart by the call)
+    if io:
+        _call(x.device, "smx_forward_io", *args, int(io))
+    else:
+        _call(x.device, "smx_forward_dropout", *args)
     return y, xk
 
 
@@ -286,11 +357,9 @@ def backward_raw(g, xk, w_re, w_im, *, want_x=True, want_w=True, phases=PHASE_AL
     # with dropout the direct plan stages g * mask in grad_x during the SPECTRUM phase
     if (want_x or (dropout_p > 0.0 and phases & PHASE_SPECTRUM)) and grad_x is None:
         grad_x = torch.empty_like(g)
-    if want_w and flat is None:
-        flat = torch.empty(2 * D * F + D, dtype=torch.float32, device=g.device)
     gw_re = gw_im = gb = None
     if want_w:
-        gw_re, gw_im, gb = flat[:D * F], flat[D * F:2 * D * F], flat[2 * D * F:]
+        flat, gw_re, gw_im, gb = _grad_slab(D, F, g.device, flat)
     if ws is None:
         ws = _workspace(g.device, _ws_bytes(B, N, D, F))
     if not want_x:
@@ -298,11 +367,12 @@ def backward_raw(g, xk, w_re, w_im, *, want_x=True, want_w=True, phases=PHASE_AL
     if sync_clean:
         phases |= PHASE_SYNC_CLEAN
     _prepare(g.device, N)
-    with _on_device(g.device):
-        args = (g.data_ptr(), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(), _ptr(grad_x), _ptr(gw_re),
-                _ptr(gw_im), _ptr(gb), _ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F, phases,
-                float(dropout_p), _ptr(rng), _ptr(pack), _stream(g.device))
-        _lib.check(_lib.lib().smx_backward_io(*args, int(io)) if io else _lib.lib().smx_backward_dropout(*args))
+    args = (g.data_ptr(), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(), _ptr(grad_x), _ptr(gw_re), _ptr(gw_im), _ptr(gb),
+            *_ws_arg(ws), B, N, D, F, phases, float(dropout_p), _ptr(rng), _ptr(pack), _stream(g.device))
+    if io:
+        _call(g.device, "smx_backward_io", *args, int(io))
+    else:
+        _call(g.device, "smx_backward_dropout", *args)
     return grad_x, flat
 
 
@@ -324,13 +394,25 @@ def _new_pack(x: torch.Tensor, w_re: torch.Tensor) -> Optional[torch.Tensor]:
     return torch.empty((num_bins(N, F), D), dtype=torch.complex64, device=x.device)
 
 
+def _phase_split(sync, run, want_x: bool = True):
+    """Backward of one node under a gradient sync: SMX_PHASE_SPECTRUM on the main stream, then the parameter-gradient
+    reduction (SMX_PHASE_PARAMS, handed to the collective as `pre`) while the grad_x inverse transform
+    (SMX_PHASE_INVERSE) runs on the main stream; sync.mode == "fused" folds INVERSE into the first call.
+    `run(phases, bufs)` runs those phases into the buffers an earlier phase returned (None: it allocates them) and
+    returns them, the gradient slab second.  Returns (bufs, handle); the caller waits on the handle."""
+    fused = getattr(sync, "mode", "overlap") == "fused" and want_x
+    bufs = run((PHASE_SPECTRUM | PHASE_INVERSE) if fused else PHASE_SPECTRUM, None)
+    handle = sync.all_reduce(bufs[1], pre=lambda: run(PHASE_PARAMS, bufs))
+    if want_x and not fused:
+        run(PHASE_INVERSE, bufs)
+    return bufs, handle
+
+
 class _SpectralMix(torch.autograd.Function):
     """y = real(ifft(pad_k(W * fft(x)[:k]))) + bias, reference fft_tensor/spectral_layers.py:88-116.
 
-    `sync` is None or an object with `.all_reduce(flat, pre)` -> handle-with-wait(); when given,
-    backward runs SMX_PHASE_SPECTRUM on the main stream, then the parameter-gradient reduction
-    (SMX_PHASE_PARAMS, passed as `pre`) and the collective on a side stream while the grad_x inverse
-    transform (SMX_PHASE_INVERSE) runs on the main one.
+    `sync` is None or an object with `.all_reduce(flat, pre)` -> handle-with-wait(); when given and active,
+    backward runs in phases around the collective (_phase_split).
     """
 
     @staticmethod
@@ -377,23 +459,17 @@ class _SpectralMix(torch.autograd.Function):
             if not want_x:
                 gx = None
         else:
-            ws = ctx.ws
-            kw = dict(want_w=True, ws=ws, **dkw)
-            fused = getattr(sync, "mode", "overlap") == "fused" and want_x
-            first = (PHASE_SPECTRUM | PHASE_INVERSE) if fused else PHASE_SPECTRUM
-            gx, flat = backward_raw(g, xk, w_re, w_im, want_x=want_x, phases=first, **kw)
-            handle = sync.all_reduce(flat, pre=lambda: backward_raw(
-                g, xk, w_re, w_im, want_x=False, phases=PHASE_PARAMS, flat=flat, **kw))
-            if want_x and not fused:
-                backward_raw(g, xk, w_re, w_im, want_x=True, phases=PHASE_INVERSE, grad_x=gx, flat=flat,
-                             **kw)
+            def run(phases, bufs):
+                inv = phases != PHASE_PARAMS                 # the PARAMS call neither reads nor writes grad_x
+                return backward_raw(g, xk, w_re, w_im, want_x=want_x and inv, want_w=True, phases=phases,
+                                    grad_x=bufs[0] if bufs and inv else None, flat=bufs[1] if bufs else None,
+                                    ws=ctx.ws, **dkw)
+            (gx, flat), handle = _phase_split(sync, run, want_x)
             handle.wait()
-        gwr = gwi = gb = None
-        if want_w:
-            gwr = flat[:D * F].view(D, F)
-            gwi = flat[D * F:2 * D * F].view(D, F)
-            gb = flat[2 * D * F:] if ctx.has_bias else None
-        return gx, gwr, gwi, gb, None, None, None, None
+        if not want_w:
+            return gx, None, None, None, None, None, None, None
+        _, gwr, gwi, gb = _grad_slab(D, F, flat=flat)
+        return gx, gwr.view(D, F), gwi.view(D, F), gb if ctx.has_bias else None, None, None, None, None
 
 
 def spectral_mix(x: torch.Tensor, weight_real: torch.Tensor, weight_imag: torch.Tensor,
@@ -406,31 +482,22 @@ def spectral_mix(x: torch.Tensor, weight_real: torch.Tensor, weight_imag: torch.
     read as fp32 (`.float()`, so autograd returns their gradients in their own dtype).  All arithmetic is fp32: the
     result is the fp32 layer's on x.float(), rounded once to x's dtype -- by the kernels' stores where the plan has
     native 2-byte rows (_lib.io_supported), by `.to(dtype)` after the fp32 op everywhere else."""
-    _require_gpu_io("x", x)
-    if x.dtype != torch.float32:
-        for name, t in (("weight_real", weight_real), ("weight_imag", weight_imag), ("bias", bias)):
-            if t is not None:
-                _require_gpu_io(name, t)
-                if t.dtype not in (torch.float32, x.dtype):
-                    raise TypeError(f"{name} must be float32 or {x.dtype} like x, got {t.dtype}")
-        return _spectral_mix_half(x, weight_real.float(), weight_imag.float(),
-                                  None if bias is None else bias.float(), sync, dropout_p, drop_state)
-    _require_gpu_f32("weight_real", weight_real)
-    _require_gpu_f32("weight_imag", weight_imag)
-    if bias is not None:
-        _require_gpu_f32("bias", bias)
+    _require("x", x, _ACT)
+    weight_real, weight_imag, bias = _fp32_params(x, (("weight_real", weight_real), ("weight_imag", weight_imag),
+                                                      ("bias", bias)), required=2)
     if x.dim() != 3:
         raise ValueError(f"expected x of shape (B, T, D), got {tuple(x.shape)}")
-    if weight_real.shape != weight_imag.shape or weight_real.dim() != 2 \
-            or weight_real.shape[0] != x.shape[2]:
-        raise ValueError("weights must both be (D, num_filters)")
+    _check_filter(x, weight_real, weight_imag)
+    B, N, D = x.shape
+    half = x.dtype != torch.float32
+    # bf16 / fp16 x: native 2-byte rows where the plan has them (the single-launch and residue-split plans with at
+    # most 512 bins); everywhere else the up-cast route, which is the same result by construction
+    if half and not (x.numel() > 0 and _half_native(x, _io_cache, (B, N, D, weight_real.shape[1]), _lib.io_supported)):
+        return spectral_mix(x.float(), weight_real, weight_imag, bias, sync, dropout_p, drop_state).to(x.dtype)
     if x.numel() == 0:
         return torch.empty_like(x)
-    dropout_p = _check_p(dropout_p)
-    if dropout_p > 0.0 and drop_state is None:
-        raise ValueError("dropout_p > 0 needs a DropoutState")
-    B, N, D = x.shape
-    if D % 2 == 1 and x.numel() >= _ODD_D_PAD_MIN and (
+    dropout_p = _check_dropout(dropout_p, drop_state)
+    if not half and D % 2 == 1 and x.numel() >= _ODD_D_PAD_MIN and (
             N % 256 == 0 or (N % 8 == 0 and num_bins(N, weight_real.shape[1]) <= (256 if N % 16 == 0 else 128))):
         # An odd channel count cannot be read as packed float2 pairs, which alone would send the shape to the
         # O(N k) DFT products (~10x).  One zero channel more (its weights and bias zero as well) runs the streaming
@@ -442,7 +509,7 @@ def spectral_mix(x: torch.Tensor, weight_real: torch.Tensor, weight_imag: torch.
         return y[..., :D]
     F = weight_real.shape[1]
     k = num_bins(N, F)
-    if (N % 16 == 8 and D % 2 == 0 and 1 <= k <= 128 and x.numel() >= _ODD_D_PAD_MIN
+    if (not half and N % 16 == 8 and D % 2 == 0 and 1 <= k <= 128 and x.numel() >= _ODD_D_PAD_MIN
             and (sync is None or not sync.active())):
         # N = 8 (odd): no sub-transform of the decimated kernels divides it, but the N-point bins ARE the even bins of
         # the 2N-point transform of the zero-padded sequence (w_N^{f n} = w_2N^{2 f n}), and 2N is a multiple of 16:
@@ -455,34 +522,8 @@ def spectral_mix(x: torch.Tensor, weight_real: torch.Tensor, weight_imag: torch.
         y = spectral_filter(x, even_bins(weight_real), even_bins(weight_imag), bias, n_fft=2 * N, k=2 * k - 1)
         # (training-mode dropout as a separate pass here: the general entry point has no fused one)
         return torch.nn.functional.dropout(y, dropout_p, True) if dropout_p > 0.0 else y
-    return _SpectralMix.apply(_dense(x), _dense(weight_real), _dense(weight_imag), _dense(bias), sync,
-                              dropout_p, drop_state, torch.is_grad_enabled())
-
-
-_ODD_D_PAD_MIN = 1 << 18        # below this the literal kernels of the direct plan are launch-bound anyway
-
-_io_cache = _Memo()
-
-
-def _spectral_mix_half(x, w_re, w_im, bias, sync, dropout_p, drop_state):
-    """bf16 / fp16 x with fp32 parameters.  Native 2-byte rows where the plan has them (the single-launch and
-    residue-split plans with at most 512 bins); everywhere else the up-cast route x.float() -> fp32 op -> .to(dtype),
-    which is the same result by construction."""
-    if x.dim() != 3:
-        raise ValueError(f"expected x of shape (B, T, D), got {tuple(x.shape)}")
-    if w_re.shape != w_im.shape or w_re.dim() != 2 or w_re.shape[0] != x.shape[2]:
-        raise ValueError("weights must both be (D, num_filters)")
-    B, N, D = x.shape
-    F = w_re.shape[1]
-    native = x.numel() > 0 and _io_cache.get((B, N, D, F, x.dtype),
-                                            lambda: _lib.io_supported(B, N, D, F, _IO[x.dtype]))
-    if not native:
-        return spectral_mix(x.float(), w_re, w_im, bias, sync, dropout_p, drop_state).to(x.dtype)
-    dropout_p = _check_p(dropout_p)
-    if dropout_p > 0.0 and drop_state is None:
-        raise ValueError("dropout_p > 0 needs a DropoutState")
     # _dense: contiguous and 16-byte aligned -- a view with a storage offset is copied before it reaches the library
-    return _SpectralMix.apply(_dense(x), _dense(w_re), _dense(w_im), _dense(bias), sync,
+    return _SpectralMix.apply(_dense(x), _dense(weight_real), _dense(weight_imag), _dense(bias), sync,
                               dropout_p, drop_state, torch.is_grad_enabled())
 
 
@@ -500,14 +541,13 @@ def block_forward_raw(x, ln_w, ln_b, eps, w_re, w_im, bias, *, save=True, dropou
     _prepare(x.device, N)
     if ws is None:
         ws = _workspace(x.device, _ws_bytes(B, N, D, F))
-    with _on_device(x.device):
-        args = (x.data_ptr(), _ptr(ln_w), _ptr(ln_b), float(eps), w_re.data_ptr(), w_im.data_ptr(),
-                _ptr(bias), y.data_ptr(), _ptr(xk), stats.data_ptr(), _ptr(ws),
-                0 if ws is None else ws.numel(), B, N, D, F, float(dropout_p), _ptr(rng), _ptr(pack),
-                _stream(x.device))
-        # (as forward_raw: 2-byte rows through the _io entry, f32 through the f32 entry)
-        _lib.check(_lib.lib().smx_block_forward_io(*args, int(io)) if io
-                   else _lib.lib().smx_block_forward_dropout(*args))
+    args = (x.data_ptr(), _ptr(ln_w), _ptr(ln_b), float(eps), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias),
+            y.data_ptr(), _ptr(xk), stats.data_ptr(), *_ws_arg(ws), B, N, D, F, float(dropout_p), _ptr(rng), _ptr(pack),
+            _stream(x.device))
+    if io:                                                   # (as forward_raw: 2-byte rows through the _io entry)
+        _call(x.device, "smx_block_forward_io", *args, int(io))
+    else:
+        _call(x.device, "smx_block_forward_dropout", *args)
     return y, xk, stats
 
 
@@ -523,8 +563,7 @@ def block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, *, phases=PHASE_ALL, g
     F = w_re.shape[1]
     if grad_x is None:
         grad_x = torch.empty_like(g)
-    if flat is None:
-        flat = torch.empty(2 * D * F + D, dtype=torch.float32, device=g.device)
+    flat, gw_re, gw_im, gb = _grad_slab(D, F, g.device, flat)
     if ln_flat is None:
         ln_flat = torch.empty(2 * D, dtype=torch.float32, device=g.device)
     if io and grad_h is None:
@@ -534,14 +573,14 @@ def block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, *, phases=PHASE_ALL, g
     if sync_clean:
         phases |= PHASE_SYNC_CLEAN
     _prepare(g.device, N)
-    with _on_device(g.device):
-        head = (g.data_ptr(), x.data_ptr(), stats.data_ptr(), _ptr(ln_w), _ptr(xk), w_re.data_ptr(),
-                w_im.data_ptr(), grad_x.data_ptr(), ln_flat[:D].data_ptr(), ln_flat[D:].data_ptr(),
-                flat[:D * F].data_ptr(), flat[D * F:2 * D * F].data_ptr(), flat[2 * D * F:].data_ptr())
-        tail = (_ptr(ws), 0 if ws is None else ws.numel(), B, N, D, F, phases, float(dropout_p),
-                _ptr(rng), _ptr(pack), _stream(g.device))
-        _lib.check(_lib.lib().smx_block_backward_io(*head, grad_h.data_ptr(), *tail, int(io)) if io
-                   else _lib.lib().smx_block_backward_dropout(*head, *tail))
+    head = (g.data_ptr(), x.data_ptr(), stats.data_ptr(), _ptr(ln_w), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(),
+            grad_x.data_ptr(), ln_flat[:D].data_ptr(), ln_flat[D:].data_ptr(), gw_re.data_ptr(), gw_im.data_ptr(),
+            gb.data_ptr())
+    tail = (*_ws_arg(ws), B, N, D, F, phases, float(dropout_p), _ptr(rng), _ptr(pack), _stream(g.device))
+    if io:
+        _call(g.device, "smx_block_backward_io", *head, grad_h.data_ptr(), *tail, int(io))
+    else:
+        _call(g.device, "smx_block_backward_dropout", *head, *tail)
     return grad_x, flat, ln_flat
 
 
@@ -570,8 +609,7 @@ class _SpectralBlockMix(torch.autograd.Function):
         ctx.pack = pack
         ctx.flags = (ln_w is not None, ln_b is not None, bias is not None)
         if needs:
-            ctx.save_for_backward(x, stats, xk, w_re, w_im,
-                                  ln_w if ln_w is not None else x.new_empty(0))
+            ctx.save_for_backward(x, stats, xk, w_re, w_im, ln_w)
         return y
 
     @staticmethod
@@ -580,8 +618,6 @@ class _SpectralBlockMix(torch.autograd.Function):
     def backward(ctx, g):
         x, stats, xk, w_re, w_im, ln_w = ctx.saved_tensors
         has_w, has_b, has_bias = ctx.flags
-        if not has_w:
-            ln_w = None
         if g.dtype != ctx.io_dtype:
             g = g.to(ctx.io_dtype)
         g = _dense(g)
@@ -594,15 +630,11 @@ class _SpectralBlockMix(torch.autograd.Function):
             gx, flat, lnf = block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, ws=ctx.ws,
                                                sync_clean=ctx.ws is not None, **dkw)
         else:
-            args = (g, x, stats, ln_w, xk, w_re, w_im)
-            ws = ctx.ws
-            fused = getattr(sync, "mode", "overlap") == "fused"
-            first = (PHASE_SPECTRUM | PHASE_INVERSE) if fused else PHASE_SPECTRUM
-            gx, flat, lnf = block_backward_raw(*args, phases=first, ws=ws, **dkw)
-            kw = dict(grad_x=gx, flat=flat, ln_flat=lnf, ws=ws, **dkw)
-            handle = sync.all_reduce(flat, pre=lambda: block_backward_raw(*args, phases=PHASE_PARAMS, **kw))
-            if not fused:
-                block_backward_raw(*args, phases=PHASE_INVERSE, **kw)
+            def run(phases, bufs):
+                gx, flat, lnf = bufs or (None, None, None)
+                return block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, phases=phases, grad_x=gx, flat=flat,
+                                          ln_flat=lnf, ws=ctx.ws, **dkw)
+            (gx, flat, lnf), handle = _phase_split(sync, run)
             # norm1's weight / bias gradients come out of the LayerNorm backward at the end of the INVERSE
             # phase: a second, tiny (2 D floats) collective, so that every gradient this op returns is
             # already summed over the ranks
@@ -610,9 +642,9 @@ class _SpectralBlockMix(torch.autograd.Function):
             handle.wait()
             if handle2 is not None:
                 handle2.wait()
-        return (gx, lnf[:D] if has_w else None, lnf[D:] if has_b else None, None,
-                flat[:D * F].view(D, F), flat[D * F:2 * D * F].view(D, F),
-                flat[2 * D * F:2 * D * F + D] if has_bias else None, None, None, None, None)
+        _, gwr, gwi, gb = _grad_slab(D, F, flat=flat)
+        return (gx, lnf[:D] if has_w else None, lnf[D:] if has_b else None, None, gwr.view(D, F), gwi.view(D, F),
+                gb if has_bias else None, None, None, None, None)
 
 
 _block_io_cache = _Memo()
@@ -634,43 +666,27 @@ def spectral_block_mix(x: torch.Tensor, ln_weight: Optional[torch.Tensor],
     as fp32 (`.float()`, so autograd returns their gradients in their own dtype).  All arithmetic is fp32: the result is
     the fp32 op's on x.float(), rounded once to x's dtype -- by the kernels' stores where the shape has native 2-byte
     block rows (_lib.block_io_supported), by `.to(dtype)` after the fp32 op everywhere else."""
-    _require_gpu_io("x", x)
-    params = (("ln_weight", ln_weight), ("ln_bias", ln_bias), ("weight_real", weight_real),
-              ("weight_imag", weight_imag), ("bias", bias))
+    _require("x", x, _ACT)
+    ln_weight, ln_bias, weight_real, weight_imag, bias = _fp32_params(
+        x, (("ln_weight", ln_weight), ("ln_bias", ln_bias), ("weight_real", weight_real), ("weight_imag", weight_imag),
+            ("bias", bias)))
     if x.dtype != torch.float32:
-        for name, t in params:
-            if t is not None:
-                _require_gpu_io(name, t)
-                if t.dtype not in (torch.float32, x.dtype):
-                    raise TypeError(f"{name} must be float32 or {x.dtype} like x, got {t.dtype}")
-        ln_weight, ln_bias, weight_real, weight_imag, bias = (None if t is None else t.float() for _, t in params)
-        if x.dim() == 3 and weight_real.dim() == 2 and x.numel() > 0:
-            B, N, D = x.shape
-            F = weight_real.shape[1]
-            native = _block_io_cache.get((B, N, D, F, x.dtype),
-                                         lambda: _lib.block_io_supported(B, N, D, F, _IO[x.dtype]))
-        else:
-            native = False                                   # (the fp32 call below raises what there is to raise)
-        if not native:
+        # (a shape that is none: not native, and the fp32 call raises what there is to raise)
+        shaped = x.dim() == 3 and weight_real.dim() == 2 and x.numel() > 0
+        if not (shaped and _half_native(x, _block_io_cache, (*x.shape, weight_real.shape[1]),
+                                        _lib.block_io_supported)):
             return spectral_block_mix(x.float(), ln_weight, ln_bias, eps, weight_real, weight_imag, bias, sync,
                                       dropout_p, drop_state).to(x.dtype)
-    else:
-        for name, t in params:
-            if t is not None:
-                _require_gpu_f32(name, t)
     if x.dim() != 3:
         raise ValueError(f"expected x of shape (B, T, D), got {tuple(x.shape)}")
     D = x.shape[2]
-    if weight_real.shape != weight_imag.shape or weight_real.dim() != 2 or weight_real.shape[0] != D:
-        raise ValueError("weights must both be (D, num_filters)")
+    _check_filter(x, weight_real, weight_imag)
     for name, t in (("ln_weight", ln_weight), ("ln_bias", ln_bias), ("bias", bias)):
         if t is not None and tuple(t.shape) != (D,):
             raise ValueError(f"{name} must have shape ({D},)")
     if x.numel() == 0:
         return torch.empty_like(x)
-    dropout_p = _check_p(dropout_p)
-    if dropout_p > 0.0 and drop_state is None:
-        raise ValueError("dropout_p > 0 needs a DropoutState")
+    dropout_p = _check_dropout(dropout_p, drop_state)
     N = x.shape[1]
     if not block_supported(D) or (x.numel() >= _ODD_D_PAD_MIN and
                                   ((D % 2 == 1 and N % 8 == 0) or (D % 2 == 0 and N % 16 == 8))):
@@ -687,7 +703,7 @@ def spectral_block_mix(x: torch.Tensor, ln_weight: Optional[torch.Tensor],
 
 def pruned_rfft(x: torch.Tensor, num_filters: int) -> torch.Tensor:
     """fft(x, dim=1)[:, :k, :] with k = min(num_filters, T//2), without forming the other bins."""
-    _require_gpu_f32("x", x)
+    _require("x", x)
     x = _dense(x)
     B, N, D = x.shape
     k = num_bins(N, num_filters)
@@ -696,10 +712,7 @@ def pruned_rfft(x: torch.Tensor, num_filters: int) -> torch.Tensor:
         return xk
     _prepare(x.device, N)
     ws = _workspace(x.device, _ws_bytes(B, N, D, num_filters))
-    with _on_device(x.device):
-        _lib.check(_lib.lib().smx_spectrum(x.data_ptr(), xk.data_ptr(), _ptr(ws),
-                                           0 if ws is None else ws.numel(), B, N, D, num_filters,
-                                           _stream(x.device)))
+    _call(x.device, "smx_spectrum", x.data_ptr(), xk.data_ptr(), *_ws_arg(ws), B, N, D, num_filters, _stream(x.device))
     return xk
 
 
@@ -775,16 +788,12 @@ class _SpectralFilter(torch.autograd.Function):
         xk = torch.empty((B, k, D), dtype=torch.complex64, device=x.device) if needs else None
         _prepare(x.device, n_fft)
         ws = _workspace(x.device, _ws_bytes_ex(key))
-        sh = _shape(*key)
-        with _on_device(x.device):
-            _lib.check(_lib.lib().smx_forward_ex(
-                sh, x.data_ptr(), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(xk),
-                _ptr(ws), 0 if ws is None else ws.numel(), 0, None, _ptr(row_scale), _stream(x.device)))
+        _call(x.device, "smx_forward_ex", _shape(*key), x.data_ptr(), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias),
+              y.data_ptr(), _ptr(xk), *_ws_arg(ws), 0, None, _ptr(row_scale), _stream(x.device))
         ctx.key = key
         ctx.has_bias = bias is not None
-        ctx.has_scale = row_scale is not None
         if needs:
-            ctx.save_for_backward(xk, w_re, w_im, row_scale if row_scale is not None else x.new_empty(0))
+            ctx.save_for_backward(xk, w_re, w_im, row_scale)
         return y
 
     @staticmethod
@@ -792,32 +801,23 @@ class _SpectralFilter(torch.autograd.Function):
     @_under_forward_options
     def backward(ctx, g):
         xk, w_re, w_im, row_scale = ctx.saved_tensors
-        if not ctx.has_scale:
-            row_scale = None
         B, R, D, F, n_fft, k = ctx.key
-        if g.dtype != torch.float32:
-            g = g.float()
-        g = _dense(g)
+        g = _grad_f32(g)
         want_x = ctx.needs_input_grad[0]
         want_w = any(ctx.needs_input_grad[1:4])
-        want_s = ctx.has_scale and ctx.needs_input_grad[4]
+        want_s = row_scale is not None and ctx.needs_input_grad[4]
         gx = torch.empty_like(g) if want_x else None
-        flat = torch.empty(2 * D * F + D, dtype=torch.float32, device=g.device) if want_w else None
-        gs = torch.empty((B, D), dtype=torch.float32, device=g.device) if want_s else None
-        ptrs = (None, None, None) if flat is None else \
-            (flat[:D * F].data_ptr(), flat[D * F:2 * D * F].data_ptr(), flat[2 * D * F:].data_ptr())
-        ws = _workspace(g.device, _ws_bytes_ex(ctx.key))
-        phases = PHASE_ALL if want_x else (PHASE_SPECTRUM | PHASE_PARAMS)
-        with _on_device(g.device):
-            _lib.check(_lib.lib().smx_backward_ex(
-                _shape(*ctx.key), g.data_ptr(), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(), _ptr(gx),
-                ptrs[0], ptrs[1], ptrs[2], _ptr(ws), 0 if ws is None else ws.numel(), phases, None,
-                _ptr(row_scale), _ptr(gs), _stream(g.device)))
         gwr = gwi = gb = None
         if want_w:
-            gwr = flat[:D * F].view(D, F)
-            gwi = flat[D * F:2 * D * F].view(D, F)
-            gb = flat[2 * D * F:] if ctx.has_bias else None
+            _, gwr, gwi, gb = _grad_slab(D, F, g.device)
+        gs = torch.empty((B, D), dtype=torch.float32, device=g.device) if want_s else None
+        ws = _workspace(g.device, _ws_bytes_ex(ctx.key))
+        phases = PHASE_ALL if want_x else (PHASE_SPECTRUM | PHASE_PARAMS)
+        _call(g.device, "smx_backward_ex", _shape(*ctx.key), g.data_ptr(), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(),
+              _ptr(gx), _ptr(gwr), _ptr(gwi), _ptr(gb), *_ws_arg(ws), phases, None, _ptr(row_scale), _ptr(gs),
+              _stream(g.device))
+        if want_w:
+            gwr, gwi, gb = gwr.view(D, F), gwi.view(D, F), gb if ctx.has_bias else None
         return gx, gwr, gwi, gb, gs, None, None, None
 
 
@@ -831,16 +831,15 @@ def spectral_filter(x: torch.Tensor, weight_real: torch.Tensor, weight_imag: tor
     row_scale (B, D): an extra real factor per (batch row, channel) on the filter -- a gate that depends on
     the batch row -- applied inside the native filter stage where the plan allows (row_scale_supported),
     as a multiply of the output otherwise; differentiable either way."""
-    _require_gpu_f32("x", x)
-    _require_gpu_f32("weight_real", weight_real)
-    _require_gpu_f32("weight_imag", weight_imag)
+    _require("x", x)
+    _require("weight_real", weight_real)
+    _require("weight_imag", weight_imag)
     if bias is not None:
-        _require_gpu_f32("bias", bias)
+        _require("bias", bias)
     if x.dim() != 3:
         raise ValueError(f"expected x of shape (B, T, D), got {tuple(x.shape)}")
     B, R, D = x.shape
-    if weight_real.shape != weight_imag.shape or weight_real.dim() != 2 or weight_real.shape[0] != D:
-        raise ValueError("weights must both be (D, num_filters)")
+    _check_filter(x, weight_real, weight_imag)
     F = weight_real.shape[1]
     n_fft = R if n_fft is None else int(n_fft)
     if n_fft < R:
@@ -849,7 +848,7 @@ def spectral_filter(x: torch.Tensor, weight_real: torch.Tensor, weight_imag: tor
     if not 0 <= k <= min(F, n_fft // 2 + 1):
         raise ValueError(f"k={k} must be in [0, min(F, n_fft // 2 + 1)] = [0, {min(F, n_fft // 2 + 1)}]")
     if row_scale is not None:
-        _require_gpu_f32("row_scale", row_scale)
+        _require("row_scale", row_scale)
         if tuple(row_scale.shape) != (B, D):
             raise ValueError(f"row_scale must be (B, D) = ({B}, {D}), got {tuple(row_scale.shape)}")
         if bias is not None:
@@ -873,9 +872,8 @@ def _rfft_raw(x: torch.Tensor, n_fft: int, k: int, scale: float = 1.0, hermitian
     key = (B, R, D, max(k, 1), n_fft, k)
     _prepare(x.device, n_fft)
     ws = _workspace(x.device, _ws_bytes_ex(key))
-    with _on_device(x.device):
-        _lib.check(_lib.lib().smx_rfft_ex(_shape(*key), x.data_ptr(), xk.data_ptr(), float(scale), int(hermitian),
-                                          _ptr(ws), 0 if ws is None else ws.numel(), _stream(x.device)))
+    _call(x.device, "smx_rfft_ex", _shape(*key), x.data_ptr(), xk.data_ptr(), float(scale), int(hermitian),
+          *_ws_arg(ws), _stream(x.device))
     return xk
 
 
@@ -888,20 +886,9 @@ def _irfft_raw(spec: torch.Tensor, n_fft: int, rows: int, scale: float, hermitia
     key = (B, rows, D, max(k, 1), n_fft, k)
     _prepare(spec.device, n_fft)
     ws = _workspace(spec.device, _ws_bytes_ex(key))
-    with _on_device(spec.device):
-        _lib.check(_lib.lib().smx_irfft_ex(_shape(*key), spec.data_ptr(), y.data_ptr(), float(scale),
-                                           int(hermitian), _ptr(ws), 0 if ws is None else ws.numel(),
-                                           _stream(spec.device)))
+    _call(spec.device, "smx_irfft_ex", _shape(*key), spec.data_ptr(), y.data_ptr(), float(scale), int(hermitian),
+          *_ws_arg(ws), _stream(spec.device))
     return y
-
-
-def _require_gpu_c64(name: str, t: torch.Tensor) -> None:
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} is on {t.device}: the MI355X path has no CPU implementation")
-    if t.dtype != torch.complex64:
-        raise TypeError(f"{name} must be complex64, got {t.dtype}")
-    if t.dim() != 3:
-        raise ValueError(f"{name}: expected (B, bins, D), got {tuple(t.shape)}")
 
 
 def _check_bins(R: int, n_fft: int, k: int) -> None:
@@ -912,7 +899,7 @@ def _check_bins(R: int, n_fft: int, k: int) -> None:
 def rfft_bins(x: torch.Tensor, k: Optional[int] = None, n_fft: Optional[int] = None) -> torch.Tensor:
     """torch.fft.rfft(x, n=n_fft, dim=1)[:, :k, :] (default: every bin, k = n_fft // 2 + 1) without forming
     the others; no autograd (functional.rfft is the differentiable form)."""
-    _require_gpu_f32("x", x)
+    _require("x", x)
     x = _dense(x.detach())
     R = x.shape[1]
     n_fft = R if n_fft is None else int(n_fft)
@@ -961,7 +948,7 @@ class _IRFFT(torch.autograd.Function):
 def rfft(x: torch.Tensor, n: Optional[int] = None, k: Optional[int] = None) -> torch.Tensor:
     """torch.fft.rfft(x, n=n, dim=1)[:, :k] of a real (B, rows, D) tensor, rows <= n (zero-padded), with autograd.
     Default k = n // 2 + 1 (every bin)."""
-    _require_gpu_f32("x", x)
+    _require("x", x)
     R = x.shape[1]
     n = R if n is None else int(n)
     k = n // 2 + 1 if k is None else int(k)
@@ -972,7 +959,9 @@ def rfft(x: torch.Tensor, n: Optional[int] = None, k: Optional[int] = None) -> t
 def irfft(spec: torch.Tensor, n: Optional[int] = None, rows: Optional[int] = None) -> torch.Tensor:
     """torch.fft.irfft(spec, n=n, dim=1)[:, :rows] of a (B, k, D) complex64 spectrum (bins >= k read as zero,
     as torch pads), with autograd.  Default n = 2 (k - 1), rows = n."""
-    _require_gpu_c64("spec", spec)
+    _require("spec", spec, _C64, _ANY_PATH, typed=False)
+    if spec.dim() != 3:
+        raise ValueError(f"spec: expected (B, bins, D), got {tuple(spec.shape)}")
     k = spec.shape[1]
     n = 2 * (k - 1) if n is None else int(n)
     rows = n if rows is None else int(rows)
@@ -1007,10 +996,7 @@ _cfft_native = _Memo()
 
 
 def seq_fft_raw(z: torch.Tensor) -> torch.Tensor:
-    if not z.is_cuda:
-        raise RuntimeError(f"z is on {z.device}: the MI355X path has no CPU implementation")
-    if z.dtype != torch.complex64:
-        raise TypeError(f"z must be complex64, got {z.dtype}")
+    _require("z", z, _C64, _ANY_PATH, typed=False)
     if z.dim() != 3:
         raise ValueError(f"expected (B, N, D), got {tuple(z.shape)}")
     B, N, D = z.shape
@@ -1020,20 +1006,12 @@ def seq_fft_raw(z: torch.Tensor) -> torch.Tensor:
     # tensors, view_as_real does not -- and a misaligned view is copied
     xr = torch.view_as_real(_dense(z)).reshape(B, N, 2 * D)
     key = (B, N, 2 * D, N // 2 + 1, N, N // 2 + 1)
-
-    def native_bytes():
-        import ctypes
-        nb = ctypes.c_size_t()
-        rc = _lib.lib().smx_cfft_workspace_bytes(_shape(*key), ctypes.byref(nb))
-        return int(nb.value) if rc == 0 else 0
-    fs = _cfft_native.get(key, native_bytes)
+    fs = _cfft_native.get(key, lambda: _query("smx_cfft_workspace_bytes", _shape(*key), unsupported=0))
     if fs:               # the packed spectrum goes straight out: tile spectra + one column pass
         out = torch.empty((B, N, D), dtype=torch.complex64, device=z.device)
         _prepare(z.device, N)
         ws = _workspace(z.device, fs)
-        with _on_device(z.device):
-            _lib.check(_lib.lib().smx_cfft_ex(_shape(*key), xr.data_ptr(), out.data_ptr(), _ptr(ws),
-                                              0 if ws is None else ws.numel(), _stream(z.device)))
+        _call(z.device, "smx_cfft_ex", _shape(*key), xr.data_ptr(), out.data_ptr(), *_ws_arg(ws), _stream(z.device))
         return out
     half = rfft_bins(xr, N // 2 + 1, N)                          # (B, N//2+1, 2D): spectra of re / im parts
     A, Bc = half[..., 0::2], half[..., 1::2]
@@ -1058,10 +1036,7 @@ def _conv_plan(B: int, R: int, D: int, n_fft: int):
     def make():
         sh = _shape(B, R, D, n_fft // 2 + 1, n_fft, n_fft // 2 + 1)
         if D % 2 == 0 and n_fft % 256 == 0 and _lib.lib().smx_conv_supported(sh):
-            import ctypes
-            a, b = ctypes.c_size_t(), ctypes.c_size_t()
-            _lib.check(_lib.lib().smx_conv_workspace_bytes(sh, ctypes.byref(a), ctypes.byref(b)))
-            return (int(a.value), int(b.value))
+            return _query("smx_conv_workspace_bytes", sh, outs=2)
         return ()
     v = _conv_info.get((B, R, D, n_fft), make)
     return v if v else None
@@ -1090,16 +1065,15 @@ class _RankOneConv(torch.autograd.Function):
         ws = _workspace(x.device, wsb)
         sh = _shape(B, R, D, n_fft // 2 + 1, n_fft, n_fft // 2 + 1)
         io = ctx.io = _IO[x.dtype]                           # bf16 / fp16 x: the single-launch plan only (rank_one_conv)
-        with _on_device(x.device):
-            args = (sh, x.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), y.data_ptr(), _ptr(xs),
-                    ws.data_ptr(), ws.numel())
-            s = _stream(x.device)
-            _lib.check(_lib.lib().smx_conv_forward_io(*args, io, s) if io else _lib.lib().smx_conv_forward(*args, s))
+        args = (sh, x.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), y.data_ptr(), _ptr(xs), *_ws_arg(ws))
+        if io:
+            _call(x.device, "smx_conv_forward_io", *args, io, _stream(x.device))
+        else:
+            _call(x.device, "smx_conv_forward", *args, _stream(x.device))
         ctx.dtype = x.dtype
         ctx.n_fft = n_fft
-        ctx.has_scale = scale is not None
         if needs:
-            ctx.save_for_backward(xs, h_re, h_im, scale if scale is not None else x.new_empty(0))
+            ctx.save_for_backward(xs, h_re, h_im, scale)
         return y
 
     @staticmethod
@@ -1107,8 +1081,6 @@ class _RankOneConv(torch.autograd.Function):
     @_under_forward_options
     def backward(ctx, g):
         xs, h_re, h_im, scale = ctx.saved_tensors
-        if not ctx.has_scale:
-            scale = None
         if g.dtype != ctx.dtype:
             g = g.to(ctx.dtype)
         g = _dense(g)
@@ -1119,15 +1091,16 @@ class _RankOneConv(torch.autograd.Function):
         fb = n // 2 + 1
         want_h = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         gh = torch.empty((2, fb), dtype=torch.float32, device=g.device) if want_h else None
-        gs = torch.empty((B, D), dtype=torch.float32, device=g.device) if ctx.has_scale else None
+        gs = torch.empty((B, D), dtype=torch.float32, device=g.device) if scale is not None else None
         ws = _workspace(g.device, wsb)
         sh = _shape(B, R, D, n // 2 + 1, n, n // 2 + 1)
-        with _on_device(g.device):
-            args = (sh, g.data_ptr(), xs.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), gx.data_ptr(),
-                    None if gh is None else gh[0].data_ptr(), None if gh is None else gh[1].data_ptr(), _ptr(gs),
-                    ws.data_ptr(), ws.numel())
-            s, io = _stream(g.device), ctx.io
-            _lib.check(_lib.lib().smx_conv_backward_io(*args, io, s) if io else _lib.lib().smx_conv_backward(*args, s))
+        args = (sh, g.data_ptr(), xs.data_ptr(), h_re.data_ptr(), h_im.data_ptr(), _ptr(scale), gx.data_ptr(),
+                None if gh is None else gh[0].data_ptr(), None if gh is None else gh[1].data_ptr(), _ptr(gs),
+                *_ws_arg(ws))
+        if ctx.io:
+            _call(g.device, "smx_conv_backward_io", *args, ctx.io, _stream(g.device))
+        else:
+            _call(g.device, "smx_conv_backward", *args, _stream(g.device))
         return gx, None if gh is None else gh[0], None if gh is None else gh[1], gs, None, None
 
 
@@ -1139,34 +1112,24 @@ class _CausalDwConv3(torch.autograd.Function):
     def forward(ctx, x, w, bias, scale):
         B, T, C = x.shape
         y = torch.empty_like(x)
-        with _on_device(x.device):
-            _lib.check(_lib.lib().smx_dwconv3_forward(x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(scale), y.data_ptr(),
-                                                      B, T, C, _stream(x.device)))
-        ctx.has = (bias is not None, scale is not None)
-        ctx.save_for_backward(x, w, bias if bias is not None else x.new_empty(0),
-                              scale if scale is not None else x.new_empty(0))
+        _call(x.device, "smx_dwconv3_forward", x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(scale), y.data_ptr(), B, T, C,
+              _stream(x.device))
+        ctx.save_for_backward(x, w, bias, scale)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        import ctypes
         x, w, bias, scale = ctx.saved_tensors
-        bias = bias if ctx.has[0] else None
-        scale = scale if ctx.has[1] else None
-        g = _dense(g.float() if g.dtype != torch.float32 else g)
+        g = _grad_f32(g)
         B, T, C = x.shape
-        nb = ctypes.c_size_t()
-        _lib.check(_lib.lib().smx_dwconv3_workspace_bytes(B, T, C, ctypes.byref(nb)))
-        ws = _workspace(x.device, int(nb.value))
+        ws = _workspace(x.device, _query("smx_dwconv3_workspace_bytes", B, T, C))
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         gb = torch.empty_like(bias) if bias is not None and ctx.needs_input_grad[2] else None
         gs = torch.empty_like(scale) if scale is not None and ctx.needs_input_grad[3] else None
-        with _on_device(x.device):
-            _lib.check(_lib.lib().smx_dwconv3_backward(g.data_ptr(), x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(scale),
-                                                       _ptr(gx), _ptr(gw), _ptr(gb), _ptr(gs), ws.data_ptr(), ws.numel(),
-                                                       B, T, C, _stream(x.device)))
+        _call(x.device, "smx_dwconv3_backward", g.data_ptr(), x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(scale), _ptr(gx),
+              _ptr(gw), _ptr(gb), _ptr(gs), *_ws_arg(ws), B, T, C, _stream(x.device))
         return gx, gw, gb, gs
 
 
@@ -1176,19 +1139,19 @@ def causal_dwconv3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     layout: shift right by one and drop the last position, depthwise `nn.Conv1d(C, C, 3, padding=1, groups=C)` with
     `weight` (C, 1, 3) or (C, 3) and `bias` (C), times `scale` (B, C) (the time gate) -- no transposes, one launch;
     differentiable in x, weight, bias and scale (fixed-order sums)."""
-    _require_gpu_f32("x", x)
-    _require_gpu_f32("weight", weight)
+    _require("x", x)
+    _require("weight", weight)
     if x.dim() != 3:
         raise ValueError(f"expected (B, T, C), got {tuple(x.shape)}")
     B, T, C = x.shape
     if weight.numel() != 3 * C or weight.shape[0] != C:
         raise ValueError(f"weight must be (C, 1, 3) or (C, 3) with C = {C}, got {tuple(weight.shape)}")
     if bias is not None:
-        _require_gpu_f32("bias", bias)
+        _require("bias", bias)
         if tuple(bias.shape) != (C,):
             raise ValueError(f"bias must be (C,) = ({C},)")
     if scale is not None:
-        _require_gpu_f32("scale", scale)
+        _require("scale", scale)
         if tuple(scale.shape) != (B, C):
             raise ValueError(f"scale must be (B, C) = ({B}, {C})")
     if x.numel() == 0:
@@ -1204,10 +1167,9 @@ class _SpectralLN(torch.autograd.Function):
     def forward(ctx, z, gamma, beta, eps, planar):
         B, Fq, C = z.shape
         out = torch.empty((2, B, Fq, C), dtype=torch.float32, device=z.device) if planar else torch.empty_like(z)
-        with _on_device(z.device):
-            _lib.check(_lib.lib().smx_spectral_ln_forward(
-                torch.view_as_real(z).data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps),
-                (out if planar else torch.view_as_real(out)).data_ptr(), int(planar), B, Fq, C, _stream(z.device)))
+        _call(z.device, "smx_spectral_ln_forward", torch.view_as_real(z).data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+              float(eps), (out if planar else torch.view_as_real(out)).data_ptr(), int(planar), B, Fq, C,
+              _stream(z.device))
         ctx.eps, ctx.planar = float(eps), bool(planar)
         ctx.save_for_backward(z, gamma, beta)
         return out
@@ -1217,15 +1179,14 @@ class _SpectralLN(torch.autograd.Function):
     def backward(ctx, g):
         z, gamma, beta = ctx.saved_tensors
         B, Fq, C = z.shape
-        g = _dense(g.float() if ctx.planar and g.dtype != torch.float32 else g) if ctx.planar else _dense(g.to(torch.complex64))
+        g = _grad_f32(g) if ctx.planar else _grad_c64(g)
         gz = torch.empty_like(z) if ctx.needs_input_grad[0] else None
         gg = torch.empty_like(gamma) if ctx.needs_input_grad[1] else None
         gb = torch.empty_like(beta) if ctx.needs_input_grad[2] else None
-        with _on_device(z.device):
-            _lib.check(_lib.lib().smx_spectral_ln_backward(
-                (g if ctx.planar else torch.view_as_real(g)).data_ptr(), torch.view_as_real(z).data_ptr(),
-                gamma.data_ptr(), beta.data_ptr(), ctx.eps, None if gz is None else torch.view_as_real(gz).data_ptr(),
-                _ptr(gg), _ptr(gb), int(ctx.planar), B, Fq, C, _stream(z.device)))
+        _call(z.device, "smx_spectral_ln_backward", (g if ctx.planar else torch.view_as_real(g)).data_ptr(),
+              torch.view_as_real(z).data_ptr(), gamma.data_ptr(), beta.data_ptr(), ctx.eps,
+              None if gz is None else torch.view_as_real(gz).data_ptr(), _ptr(gg), _ptr(gb), int(ctx.planar), B, Fq, C,
+              _stream(z.device))
         return gz, gg, gb, None, None
 
 
@@ -1237,9 +1198,8 @@ class _PlanarCmul(torch.autograd.Function):
     def forward(ctx, h, f_re, f_im):
         _, B, Fq, C = h.shape
         out = torch.empty_like(h)
-        with _on_device(h.device):
-            _lib.check(_lib.lib().smx_planar_cmul_forward(h.data_ptr(), f_re.data_ptr(), f_im.data_ptr(), out.data_ptr(),
-                                                          B, Fq, C, _stream(h.device)))
+        _call(h.device, "smx_planar_cmul_forward", h.data_ptr(), f_re.data_ptr(), f_im.data_ptr(), out.data_ptr(), B, Fq, C,
+              _stream(h.device))
         ctx.save_for_backward(h, f_re, f_im)
         return out
 
@@ -1248,13 +1208,12 @@ class _PlanarCmul(torch.autograd.Function):
     def backward(ctx, g):
         h, f_re, f_im = ctx.saved_tensors
         _, B, Fq, C = h.shape
-        g = _dense(g.float() if g.dtype != torch.float32 else g)
+        g = _grad_f32(g)
         gh = torch.empty_like(h) if ctx.needs_input_grad[0] else None
         gr = torch.empty_like(f_re) if ctx.needs_input_grad[1] else None
         gi = torch.empty_like(f_im) if ctx.needs_input_grad[2] else None
-        with _on_device(h.device):
-            _lib.check(_lib.lib().smx_planar_cmul_backward(g.data_ptr(), h.data_ptr(), f_re.data_ptr(), f_im.data_ptr(),
-                                                           _ptr(gh), _ptr(gr), _ptr(gi), B, Fq, C, _stream(h.device)))
+        _call(h.device, "smx_planar_cmul_backward", g.data_ptr(), h.data_ptr(), f_re.data_ptr(), f_im.data_ptr(), _ptr(gh),
+              _ptr(gr), _ptr(gi), B, Fq, C, _stream(h.device))
         return gh, gr, gi
 
 
@@ -1265,21 +1224,19 @@ class _AddPlanar(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, p):
         y = torch.empty_like(a)
-        with _on_device(a.device):
-            _lib.check(_lib.lib().smx_planar_add(torch.view_as_real(a).data_ptr(), p.data_ptr(),
-                                                 torch.view_as_real(y).data_ptr(), a.numel(), _stream(a.device)))
+        _call(a.device, "smx_planar_add", torch.view_as_real(a).data_ptr(), p.data_ptr(), torch.view_as_real(y).data_ptr(),
+              a.numel(), _stream(a.device))
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        g = _dense(g.to(torch.complex64))
+        g = _grad_c64(g)
         gp = None
         if ctx.needs_input_grad[1]:
             gp = torch.empty((2,) + tuple(g.shape), dtype=torch.float32, device=g.device)
-            with _on_device(g.device):
-                _lib.check(_lib.lib().smx_planar_split(torch.view_as_real(g).data_ptr(), gp.data_ptr(), g.numel(),
-                                                       _stream(g.device)))
+            _call(g.device, "smx_planar_split", torch.view_as_real(g).data_ptr(), gp.data_ptr(), g.numel(),
+                  _stream(g.device))
         return (g if ctx.needs_input_grad[0] else None), gp
 
 
@@ -1292,23 +1249,18 @@ class _SpectralGate(torch.autograd.Function):
     def forward(ctx, x, a, u, p, q, m, reference_gain_grad):
         B, Fq, C = x.shape
         y = torch.empty_like(x)
-        with _on_device(x.device):
-            _lib.check(_lib.lib().smx_spectral_gate_forward(x.data_ptr(), a.data_ptr(), _ptr(u), _ptr(p), _ptr(q), _ptr(m),
-                                                            y.data_ptr(), B, Fq, C, _stream(x.device)))
-        ctx.has = tuple(t is not None for t in (u, p, q, m))
+        _call(x.device, "smx_spectral_gate_forward", x.data_ptr(), a.data_ptr(), _ptr(u), _ptr(p), _ptr(q), _ptr(m),
+              y.data_ptr(), B, Fq, C, _stream(x.device))
         ctx.reference_gain_grad = bool(reference_gain_grad)
-        e = x.new_empty(0, dtype=torch.float32)
-        ctx.save_for_backward(x, a, *(t if t is not None else e for t in (u, p, q, m)))
+        ctx.save_for_backward(x, a, u, p, q, m)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        import ctypes
         x, a, u, p, q, m = ctx.saved_tensors
-        u, p, q, m = (t if h else None for t, h in zip((u, p, q, m), ctx.has))
         B, Fq, C = x.shape
-        g = _dense(g.to(torch.complex64))
+        g = _grad_c64(g)
         need = ctx.needs_input_grad
         gx = torch.empty_like(x) if need[0] else None
         want_u = u is not None and need[2]
@@ -1317,13 +1269,9 @@ class _SpectralGate(torch.autograd.Function):
         rc = (torch.empty(B, C, dtype=torch.float32, device=x.device)
               if (q is not None and need[4]) or (want_u and not plain) else None)
         rp = torch.empty(B, C, dtype=torch.float32, device=x.device) if plain else None
-        nb = ctypes.c_size_t()
-        _lib.check(_lib.lib().smx_spectral_gate_workspace_bytes(B, Fq, C, ctypes.byref(nb)))
-        ws = _workspace(x.device, int(nb.value))
-        with _on_device(x.device):
-            _lib.check(_lib.lib().smx_spectral_gate_backward(g.data_ptr(), x.data_ptr(), a.data_ptr(), _ptr(u), _ptr(p),
-                                                             _ptr(q), _ptr(m), _ptr(gx), _ptr(s1), _ptr(rc), _ptr(rp),
-                                                             ws.data_ptr(), ws.numel(), B, Fq, C, _stream(x.device)))
+        ws = _workspace(x.device, _query("smx_spectral_gate_workspace_bytes", B, Fq, C))
+        _call(x.device, "smx_spectral_gate_backward", g.data_ptr(), x.data_ptr(), a.data_ptr(), _ptr(u), _ptr(p), _ptr(q),
+              _ptr(m), _ptr(gx), _ptr(s1), _ptr(rc), _ptr(rp), *_ws_arg(ws), B, Fq, C, _stream(x.device))
         ga = gu = gp = gq = None
         if need[1]:
             ga = s1 if p is None and m is None else s1 * (p if m is None else m if p is None else p * m)      # :111
@@ -1347,14 +1295,13 @@ def spectral_gate(x: torch.Tensor, a: torch.Tensor, u: Optional[torch.Tensor] = 
     constant), each optional.  Differentiable in x, a, u, p and q.  `reference_gain_grad=True` gives u the gradient
     `FrequencyConvFunc.backward` writes by hand (reference fft_lm/frequency_native.py:115: `Re(grad * x * k)` summed, no
     conjugate) instead of the autograd one.  The channel count must be even."""
-    if x.dtype != torch.complex64 or not x.is_cuda or x.dim() != 3:
-        raise TypeError("x must be a (B, F, C) complex64 tensor on a ROCm device")
+    _require("x", x, _C64, what="a (B, F, C) complex64 tensor", dim=3, typed=False)
     B, Fq, C = x.shape
     if a.dtype != torch.complex64 or tuple(a.shape) != (Fq,):
         raise ValueError(f"a must be complex64 (F,) = ({Fq},), got {a.dtype} {tuple(a.shape)}")
     for name, t, shape in (("u", u, (C,)), ("p", p, (Fq,)), ("q", q, (B, C)), ("m", m, (Fq,))):
         if t is not None:
-            _require_gpu_f32(name, t)
+            _require(name, t)
             if tuple(t.shape) != shape:
                 raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
     if C % 2:
@@ -1366,7 +1313,10 @@ def spectral_gate(x: torch.Tensor, a: torch.Tensor, u: Optional[torch.Tensor] = 
                                reference_gain_grad)
 
 
-_MIX_WS_BYTES = None
+@functools.lru_cache(None)
+def _mix_ws_bytes() -> int:
+    """a constant of the library, asked once"""
+    return _query("smx_mix_workspace_bytes")
 
 
 class _MixPaths(torch.autograd.Function):
@@ -1376,9 +1326,8 @@ class _MixPaths(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r, a, b, c, w, c3):
         out = torch.empty_like(r)
-        with _on_device(r.device):
-            _lib.check(_lib.lib().smx_mix_forward(r.data_ptr(), a.data_ptr(), b.data_ptr(), _ptr(c), w.data_ptr(), float(c3),
-                                                  out.data_ptr(), r.numel(), _stream(r.device)))
+        _call(r.device, "smx_mix_forward", r.data_ptr(), a.data_ptr(), b.data_ptr(), _ptr(c), w.data_ptr(), float(c3),
+              out.data_ptr(), r.numel(), _stream(r.device))
         ctx.c3 = float(c3)
         ctx.has_c = c is not None
         ctx.save_for_backward(a, b, w)
@@ -1387,24 +1336,16 @@ class _MixPaths(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        import ctypes
         a, b, w = ctx.saved_tensors
-        g = _dense(g.float() if g.dtype != torch.float32 else g)
+        g = _grad_f32(g)
         need = ctx.needs_input_grad
         ga = torch.empty_like(a) if need[1] else None
         gb = torch.empty_like(b) if need[2] else None
         gc = torch.empty_like(a) if ctx.has_c and need[3] else None
         gw = torch.empty_like(w) if need[4] else None
-        global _MIX_WS_BYTES
-        if _MIX_WS_BYTES is None:                        # a constant of the library
-            nb = ctypes.c_size_t()
-            _lib.check(_lib.lib().smx_mix_workspace_bytes(ctypes.byref(nb)))
-            _MIX_WS_BYTES = int(nb.value)
-        ws = _workspace(a.device, _MIX_WS_BYTES)
-        with _on_device(a.device):
-            _lib.check(_lib.lib().smx_mix_backward(g.data_ptr(), a.data_ptr(), b.data_ptr(), w.data_ptr(), ctx.c3, _ptr(ga),
-                                                   _ptr(gb), _ptr(gc), _ptr(gw), ws.data_ptr(), ws.numel(), a.numel(),
-                                                   _stream(a.device)))
+        ws = _workspace(a.device, _mix_ws_bytes())
+        _call(a.device, "smx_mix_backward", g.data_ptr(), a.data_ptr(), b.data_ptr(), w.data_ptr(), ctx.c3, _ptr(ga),
+              _ptr(gb), _ptr(gc), _ptr(gw), *_ws_arg(ws), a.numel(), _stream(a.device))
         return (g if need[0] else None), ga, gb, gc, gw, None
 
 
@@ -1413,7 +1354,7 @@ def mix_paths(r: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: Optional[tor
     """`r + w[0] * a + w[1] * b + c3 * c` for float32 tensors of one shape (element count a multiple of 4) and two learned
     scalars `w` (2,) in device memory; differentiable in r, a, b, c and w."""
     for name, t in (("r", r), ("a", a), ("b", b), ("w", w)) + ((("c", c),) if c is not None else ()):
-        _require_gpu_f32(name, t)
+        _require(name, t)
     if a.shape != r.shape or b.shape != r.shape or (c is not None and c.shape != r.shape) or tuple(w.shape) != (2,):
         raise ValueError("mix_paths: r, a, b, c must share one shape and w must be (2,)")
     if r.numel() == 0 or r.numel() % 4:
@@ -1423,9 +1364,9 @@ def mix_paths(r: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: Optional[tor
 
 def planar_cmul(h: torch.Tensor, f_re: torch.Tensor, f_im: torch.Tensor) -> torch.Tensor:
     """(2, B, F, C) planes times the complex factor (f_re + i f_im)[f, c]."""
-    _require_gpu_f32("h", h)
-    _require_gpu_f32("f_re", f_re)
-    _require_gpu_f32("f_im", f_im)
+    _require("h", h)
+    _require("f_re", f_re)
+    _require("f_im", f_im)
     if h.dim() != 4 or h.shape[0] != 2 or tuple(f_re.shape) != tuple(h.shape[2:]) or f_re.shape != f_im.shape:
         raise ValueError(f"expected h (2, B, F, C) and factors (F, C), got {tuple(h.shape)}, {tuple(f_re.shape)}")
     return _PlanarCmul.apply(_dense(h), _dense(f_re), _dense(f_im))
@@ -1433,9 +1374,8 @@ def planar_cmul(h: torch.Tensor, f_re: torch.Tensor, f_im: torch.Tensor) -> torc
 
 def add_planar(a: torch.Tensor, p: torch.Tensor) -> torch.Tensor:
     """a + (p[0] + i p[1]) for a complex64 `a` and float32 planes p (2, *a.shape)."""
-    if a.dtype != torch.complex64 or not a.is_cuda:
-        raise TypeError("a must be a complex64 tensor on a ROCm device")
-    _require_gpu_f32("p", p)
+    _require("a", a, _C64, what="a complex64 tensor", typed=False)
+    _require("p", p)
     if tuple(p.shape) != (2,) + tuple(a.shape):
         raise ValueError(f"p must be (2, {tuple(a.shape)}), got {tuple(p.shape)}")
     return _AddPlanar.apply(_dense(a), _dense(p))
@@ -1450,12 +1390,11 @@ def spectral_layer_norm(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor
     """Magnitudes of z (B, F, C) complex64 normalised across the channels per (batch row, bin), scaled by gamma (F, C),
     shifted by beta (F, C), phases kept (reference fft_lm/frequency_native.py:203-239); differentiable in all three.
     planar: return (2, B, F, C) float32 planes (real, imaginary) instead of a complex tensor."""
-    if not z.is_cuda:
-        raise RuntimeError(f"z is on {z.device}: the MI355X path has no CPU implementation")
+    _require("z", z, None, _ANY_PATH, typed=False)
     if z.dtype != torch.complex64 or z.dim() != 3:
         raise TypeError(f"z must be a (B, F, C) complex64 tensor, got {z.dtype} {tuple(z.shape)}")
-    _require_gpu_f32("gamma", gamma)
-    _require_gpu_f32("beta", beta)
+    _require("gamma", gamma)
+    _require("beta", beta)
     B, Fq, C = z.shape
     if tuple(gamma.shape) != (Fq, C) or tuple(beta.shape) != (Fq, C):
         raise ValueError(f"gamma and beta must be (F, C) = ({Fq}, {C})")
@@ -1472,9 +1411,8 @@ class _PhaseFilter(torch.autograd.Function):
     def forward(ctx, m, p, k, n_fft):
         D = m.numel()
         w = torch.empty((2, D, k), dtype=torch.float32, device=m.device)
-        with _on_device(m.device):
-            _lib.check(_lib.lib().smx_phase_filter(m.data_ptr(), p.data_ptr(), D, k, n_fft, w[0].data_ptr(),
-                                                   w[1].data_ptr(), _stream(m.device)))
+        _call(m.device, "smx_phase_filter", m.data_ptr(), p.data_ptr(), D, k, n_fft, w[0].data_ptr(), w[1].data_ptr(),
+              _stream(m.device))
         ctx.k, ctx.n_fft = k, n_fft
         ctx.save_for_backward(m, p)
         return w[0], w[1]
@@ -1489,17 +1427,15 @@ class _PhaseFilter(torch.autograd.Function):
         gm = torch.empty_like(m) if ctx.needs_input_grad[0] else None
         gp = torch.empty_like(p) if ctx.needs_input_grad[1] else None
         if gm is not None or gp is not None:
-            with _on_device(m.device):
-                _lib.check(_lib.lib().smx_phase_filter_backward(m.data_ptr(), p.data_ptr(), g_re.data_ptr(),
-                                                                g_im.data_ptr(), D, k, ctx.n_fft, k, _ptr(gm), _ptr(gp),
-                                                                _stream(m.device)))
+            _call(m.device, "smx_phase_filter_backward", m.data_ptr(), p.data_ptr(), g_re.data_ptr(), g_im.data_ptr(), D, k,
+                  ctx.n_fft, k, _ptr(gm), _ptr(gp), _stream(m.device))
         return gm, gp, None, None
 
 
 def phase_filter(m: torch.Tensor, p: torch.Tensor, k: int, n_fft: int):
     """(w_re, w_im), each (D, k): c_f m[d] exp(i p[d]) with torch.fft.irfft's Hermitian weights c_f."""
-    _require_gpu_f32("magnitude", m)
-    _require_gpu_f32("phase", p)
+    _require("magnitude", m)
+    _require("phase", p)
     if m.dim() != 1 or m.shape != p.shape:
         raise ValueError("magnitude and phase must be 1-D tensors of the same length")
     return _PhaseFilter.apply(_dense(m), _dense(p), int(k), int(n_fft))
@@ -1514,22 +1450,16 @@ class _ConvResponse(torch.autograd.Function):
         fb = n_fft // 2 + 1
         h = torch.empty((2, fb), dtype=torch.float32, device=kernel.device)
         _prepare(kernel.device, n_fft)
-        with _on_device(kernel.device):
-            _lib.check(_lib.lib().smx_conv_response(n_fft, kernel.numel(), kernel.data_ptr(), _ptr(gate_logits),
-                                                    _ptr(mask), h[0].data_ptr(), h[1].data_ptr(),
-                                                    _stream(kernel.device)))
+        _call(kernel.device, "smx_conv_response", n_fft, kernel.numel(), kernel.data_ptr(), _ptr(gate_logits), _ptr(mask),
+              h[0].data_ptr(), h[1].data_ptr(), _stream(kernel.device))
         ctx.n_fft = n_fft
-        ctx.has = (gate_logits is not None, mask is not None)
-        e = kernel.new_empty(0)
-        ctx.save_for_backward(kernel, gate_logits if gate_logits is not None else e, mask if mask is not None else e)
+        ctx.save_for_backward(kernel, gate_logits, mask)
         return h[0], h[1]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_re, g_im):
         kernel, logits, mask = ctx.saved_tensors
-        logits = logits if ctx.has[0] else None
-        mask = mask if ctx.has[1] else None
         n = ctx.n_fft
         fb = n // 2 + 1
         g_re = torch.zeros(fb, device=kernel.device) if g_re is None else _dense(g_re.float())
@@ -1537,10 +1467,9 @@ class _ConvResponse(torch.autograd.Function):
         gk = torch.empty_like(kernel) if ctx.needs_input_grad[0] else None
         gl = torch.empty_like(logits) if (logits is not None and ctx.needs_input_grad[1]) else None
         if gk is not None or gl is not None:
-            with _on_device(kernel.device):
-                _lib.check(_lib.lib().smx_conv_response_backward(
-                    n, kernel.numel(), 0 if logits is None else logits.numel(), kernel.data_ptr(), _ptr(logits),
-                    _ptr(mask), g_re.data_ptr(), g_im.data_ptr(), _ptr(gk), _ptr(gl), _stream(kernel.device)))
+            _call(kernel.device, "smx_conv_response_backward", n, kernel.numel(), 0 if logits is None else logits.numel(),
+                  kernel.data_ptr(), _ptr(logits), _ptr(mask), g_re.data_ptr(), g_im.data_ptr(), _ptr(gk), _ptr(gl),
+                  _stream(kernel.device))
         return gk, gl, None, None
 
 
@@ -1548,14 +1477,14 @@ def conv_response(kernel: torch.Tensor, gate_logits: Optional[torch.Tensor], mas
                   n_fft: int):
     """(Re H, Im H) of the causal kernel's n_fft-point response times sigmoid(gate_logits) and mask (each may be
     None); gate_logits may be longer than n_fft // 2 + 1 (the reference sizes it for its longest sequence)."""
-    _require_gpu_f32("kernel", kernel)
+    _require("kernel", kernel)
     fb = n_fft // 2 + 1
     if gate_logits is not None:
-        _require_gpu_f32("gate_logits", gate_logits)
+        _require("gate_logits", gate_logits)
         if gate_logits.dim() != 1 or gate_logits.numel() < fb:
             raise ValueError(f"gate_logits needs at least n_fft // 2 + 1 = {fb} entries")
     if mask is not None:
-        _require_gpu_f32("mask", mask)
+        _require("mask", mask)
         if tuple(mask.shape) != (fb,):
             raise ValueError(f"mask must have n_fft // 2 + 1 = {fb} entries")
     if kernel.dim() != 1 or kernel.numel() > n_fft:
@@ -1572,21 +1501,20 @@ def rank_one_conv(x: torch.Tensor, h_re: torch.Tensor, h_im: torch.Tensor,
     x may be fp32, bf16 or fp16; y and grad_x come back in x's dtype, while h_re, h_im and scale stay fp32.  All
     arithmetic is fp32: the result is the fp32 op's on x.float(), rounded once to x's dtype -- by the kernel's stores
     where the plan has native 2-byte rows (_lib.conv_io_supported), by `.to(dtype)` after the fp32 op elsewhere."""
-    _require_gpu_io("x", x)
-    _require_gpu_f32("h_re", h_re)
-    _require_gpu_f32("h_im", h_im)
+    _require("x", x, _ACT)
+    _require("h_re", h_re)
+    _require("h_im", h_im)
     B, R, D = x.shape
     fb = n_fft // 2 + 1
     if tuple(h_re.shape) != (fb,) or tuple(h_im.shape) != (fb,):
         raise ValueError(f"h_re / h_im must have n_fft // 2 + 1 = {fb} entries")
     if scale is not None:
-        _require_gpu_f32("scale", scale)
+        _require("scale", scale)
         if tuple(scale.shape) != (B, D):
             raise ValueError(f"scale must be (B, D) = ({B}, {D})")
     if not conv_supported(B, R, D, n_fft):
         raise ValueError(f"rank_one_conv does not take (B={B}, rows={R}, D={D}, n_fft={n_fft}); use spectral_filter")
-    if x.dtype != torch.float32 and not _conv_io_cache.get((B, R, D, n_fft, x.dtype),
-                                                           lambda: _lib.conv_io_supported(B, R, D, n_fft, _IO[x.dtype])):
+    if x.dtype != torch.float32 and not _half_native(x, _conv_io_cache, (B, R, D, n_fft), _lib.conv_io_supported):
         return rank_one_conv(x.float(), h_re, h_im, scale, n_fft).to(x.dtype)
     # _dense: contiguous and 16-byte aligned -- a view with a storage offset is copied before it reaches the library
     return _RankOneConv.apply(_dense(x), _dense(h_re), _dense(h_im), _dense(scale), int(n_fft),
@@ -1595,23 +1523,15 @@ def rank_one_conv(x: torch.Tensor, h_re: torch.Tensor, h_im: torch.Tensor,
 
 # ---- row lines of EnhancedSpectralBlock (reference fft_tensor/spectral_enhancements.py:278-333), smx_enh.hip -------
 
-_enh_supported_cache: dict = {}
-
-
+@functools.lru_cache(None)
 def enh_supported(D: int) -> bool:
-    """Even D <= 1024: the row kernels of the enhanced block hold a row (the gate row: 2D) in one wavefront."""
-    D = int(D)
-    v = _enh_supported_cache.get(D)
-    if v is None:
-        v = _enh_supported_cache[D] = bool(_lib.lib().smx_enh_supported(D))
-    return v
+    """Even D <= 1024: the row kernels of the enhanced block hold a row (the gate row: 2D) in one wavefront.
+    (A property of the library, not of the plan options: remembered per D, not in an options-keyed _Memo.)"""
+    return bool(_lib.lib().smx_enh_supported(int(D)))
 
 
 def _enh_workspace(dev: torch.device, B: int, T: int, D: int) -> torch.Tensor:
-    import ctypes
-    nb = ctypes.c_size_t()
-    _lib.check(_lib.lib().smx_enh_workspace_bytes(B, T, D, ctypes.byref(nb)))
-    return _workspace(dev, int(nb.value))
+    return _workspace(dev, _query("smx_enh_workspace_bytes", B, T, D))
 
 
 def _grad_buf(t: Optional[torch.Tensor], needed: bool) -> Optional[torch.Tensor]:
@@ -1622,7 +1542,7 @@ def _g(g: Optional[torch.Tensor], like: torch.Tensor) -> torch.Tensor:
     """An upstream gradient autograd left undefined (output unused) is zero."""
     if g is None:
         return torch.zeros_like(like)
-    return _dense(g.float() if g.dtype != torch.float32 else g)
+    return _grad_f32(g)
 
 
 class _RopeNorm(torch.autograd.Function):
@@ -1636,11 +1556,9 @@ class _RopeNorm(torch.autograd.Function):
         x1 = torch.empty_like(x)
         h2 = torch.empty_like(x) if norm else None
         stats = torch.empty((2, B, T, 2), dtype=torch.float32, device=x.device) if norm else None
-        with _on_device(x.device):
-            _lib.check(_lib.lib().smx_rope_norm_forward(
-                x.data_ptr(), rot.data_ptr(), rot_rows, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(eps1),
-                float(eps2), x1.data_ptr(), _ptr(h2), _ptr(stats), B, T, D, int(norm), float(dropout_p), _ptr(rng),
-                _stream(x.device)))
+        _call(x.device, "smx_rope_norm_forward", x.data_ptr(), rot.data_ptr(), rot_rows, _ptr(w1), _ptr(b1), _ptr(w2),
+              _ptr(b2), float(eps1), float(eps2), x1.data_ptr(), _ptr(h2), _ptr(stats), B, T, D, int(norm),
+              float(dropout_p), _ptr(rng), _stream(x.device))
         ctx.meta = (rot_rows, norm, dropout_p, rng)
         ctx.save_for_backward(x if norm else None, rot, w1, b1, w2, stats)
         if not norm:
@@ -1652,7 +1570,7 @@ class _RopeNorm(torch.autograd.Function):
     def backward(ctx, g1, gh2=None):
         x, rot, w1, b1, w2, stats = ctx.saved_tensors
         rot_rows, norm, dropout_p, rng = ctx.meta
-        g1 = _g(g1, x) if norm else _dense(g1.float() if g1.dtype != torch.float32 else g1)
+        g1 = _g(g1, x) if norm else _grad_f32(g1)
         B, T, D = g1.shape
         nig = ctx.needs_input_grad
         gx = torch.empty_like(g1)
@@ -1660,11 +1578,9 @@ class _RopeNorm(torch.autograd.Function):
         gb2 = torch.empty(D, dtype=torch.float32, device=g1.device) if (norm and nig[6]) else None
         ws = _enh_workspace(g1.device, B, T, D) if norm else None
         gh2 = _g(gh2, g1) if norm else None
-        with _on_device(g1.device):
-            _lib.check(_lib.lib().smx_rope_norm_backward(
-                g1.data_ptr(), _ptr(gh2), _ptr(x), rot.data_ptr(), rot_rows, _ptr(w1), _ptr(b1), _ptr(w2),
-                _ptr(stats), gx.data_ptr(), _ptr(gw1), _ptr(gb1), _ptr(gw2), _ptr(gb2), _ptr(ws),
-                0 if ws is None else ws.numel(), B, T, D, int(norm), float(dropout_p), _ptr(rng), _stream(g1.device)))
+        _call(g1.device, "smx_rope_norm_backward", g1.data_ptr(), _ptr(gh2), _ptr(x), rot.data_ptr(), rot_rows, _ptr(w1),
+              _ptr(b1), _ptr(w2), _ptr(stats), gx.data_ptr(), _ptr(gw1), _ptr(gb1), _ptr(gw2), _ptr(gb2), *_ws_arg(ws),
+              B, T, D, int(norm), float(dropout_p), _ptr(rng), _stream(g1.device))
         return gx, None, None, gw1, gb1, gw2, gb2, None, None, None, None, None
 
 
@@ -1677,10 +1593,8 @@ class _ResidualNorm(torch.autograd.Function):
         rng = drop_state.next() if dropout_p > 0.0 else None
         x2, h3 = torch.empty_like(x1), torch.empty_like(x1)
         stats = torch.empty((B, T, 2), dtype=torch.float32, device=x1.device)
-        with _on_device(x1.device):
-            _lib.check(_lib.lib().smx_residual_norm_forward(
-                x1.data_ptr(), p.data_ptr(), _ptr(w3), _ptr(b3), float(eps), x2.data_ptr(), h3.data_ptr(),
-                stats.data_ptr(), B, T, D, float(dropout_p), _ptr(rng), _stream(x1.device)))
+        _call(x1.device, "smx_residual_norm_forward", x1.data_ptr(), p.data_ptr(), _ptr(w3), _ptr(b3), float(eps),
+              x2.data_ptr(), h3.data_ptr(), stats.data_ptr(), B, T, D, float(dropout_p), _ptr(rng), _stream(x1.device))
         ctx.meta = (dropout_p, rng)
         ctx.save_for_backward(x2, w3, b3, stats)
         return x2, h3
@@ -1697,11 +1611,9 @@ class _ResidualNorm(torch.autograd.Function):
         gp = torch.empty_like(x2) if dropout_p > 0.0 else None      # without dropout grad_p is grad_x1 itself
         gw3, gb3 = _grad_buf(w3, nig[2]), _grad_buf(b3, nig[3])
         ws = _enh_workspace(x2.device, B, T, D)
-        with _on_device(x2.device):
-            _lib.check(_lib.lib().smx_residual_norm_backward(
-                g2.data_ptr(), gh3.data_ptr(), x2.data_ptr(), _ptr(w3), stats.data_ptr(), gx1.data_ptr(), _ptr(gp),
-                _ptr(gw3), _ptr(gb3), ws.data_ptr(), ws.numel(), B, T, D, float(dropout_p), _ptr(rng),
-                _stream(x2.device)))
+        _call(x2.device, "smx_residual_norm_backward", g2.data_ptr(), gh3.data_ptr(), x2.data_ptr(), _ptr(w3),
+              stats.data_ptr(), gx1.data_ptr(), _ptr(gp), _ptr(gw3), _ptr(gb3), *_ws_arg(ws), B, T, D, float(dropout_p),
+              _ptr(rng), _stream(x2.device))
         return gx1, (gp if gp is not None else gx1), gw3, gb3, None, None, None
 
 
@@ -1715,10 +1627,8 @@ class _GateBlend(torch.autograd.Function):
         rng = drop_state.next() if dropout_p > 0.0 else None
         x3 = torch.empty_like(v)
         stats = torch.empty((B, T, 2), dtype=torch.float32, device=v.device)
-        with _on_device(v.device):
-            _lib.check(_lib.lib().smx_gate_blend_forward(
-                a.data_ptr(), v.data_ptr(), _ptr(x2), _ptr(wg), _ptr(bg), float(eps), x3.data_ptr(), stats.data_ptr(),
-                B, T, D, float(dropout_p), _ptr(rng), _stream(v.device)))
+        _call(v.device, "smx_gate_blend_forward", a.data_ptr(), v.data_ptr(), _ptr(x2), _ptr(wg), _ptr(bg), float(eps),
+              x3.data_ptr(), stats.data_ptr(), B, T, D, float(dropout_p), _ptr(rng), _stream(v.device))
         ctx.meta = (dropout_p, rng)
         ctx.save_for_backward(a, v, wg, bg, stats)
         return x3
@@ -1734,11 +1644,9 @@ class _GateBlend(torch.autograd.Function):
         ga, gv = torch.empty_like(a), torch.empty_like(v)
         gwg, gbg = _grad_buf(wg, nig[3]), _grad_buf(bg, nig[4])
         ws = _enh_workspace(v.device, B, T, D)
-        with _on_device(v.device):
-            _lib.check(_lib.lib().smx_gate_blend_backward(
-                g3.data_ptr(), a.data_ptr(), v.data_ptr(), _ptr(wg), _ptr(bg), stats.data_ptr(), ga.data_ptr(),
-                gv.data_ptr(), _ptr(gwg), _ptr(gbg), ws.data_ptr(), ws.numel(), B, T, D, float(dropout_p), _ptr(rng),
-                _stream(v.device)))
+        _call(v.device, "smx_gate_blend_backward", g3.data_ptr(), a.data_ptr(), v.data_ptr(), _ptr(wg), _ptr(bg),
+              stats.data_ptr(), ga.data_ptr(), gv.data_ptr(), _ptr(gwg), _ptr(gbg), *_ws_arg(ws), B, T, D,
+              float(dropout_p), _ptr(rng), _stream(v.device))
         return ga, gv, (g3 if nig[2] else None), gwg, gbg, None, None, None
 
 
@@ -1752,7 +1660,7 @@ def _rotation_rows(rotation: torch.Tensor, D: int):
 
 
 def _check_rows(x: torch.Tensor, D: int) -> None:
-    _require_gpu_f32("x", x)
+    _require("x", x)
     if x.dim() != 3 or x.shape[-1] != D:
         raise ValueError(f"expected (B, T, {D}), got {tuple(x.shape)}")
     if not enh_supported(D):
@@ -1800,7 +1708,7 @@ def gate_blend(a: torch.Tensor, v: torch.Tensor, x2: Optional[torch.Tensor], wg,
     the blend alone, GatedSpectralUnit.forward after its Linears)."""
     B, T, D = v.shape
     _check_rows(v, D)
-    _require_gpu_f32("a", a)
+    _require("a", a)
     if tuple(a.shape) != (B, T, 2 * D):
         raise ValueError(f"a must be (B, T, 2D) = ({B}, {T}, {2 * D}), got {tuple(a.shape)}")
     if x2 is not None:
@@ -1821,10 +1729,7 @@ def _ema_mode(mode: str) -> int:
 
 
 def _ema_ws(dev: torch.device, B: int, S: int, F: int):
-    import ctypes
-    nb = ctypes.c_size_t()
-    _lib.check(_lib.lib().smx_ema_workspace_bytes(B, S, F, ctypes.byref(nb)))
-    return _workspace(dev, int(nb.value))
+    return _workspace(dev, _query("smx_ema_workspace_bytes", B, S, F))
 
 
 class _EmaScan(torch.autograd.Function):
@@ -1835,31 +1740,27 @@ class _EmaScan(torch.autograd.Function):
     def forward(ctx, chunks, rho_logit, theta_raw, init, mode):
         B, S, F = chunks.shape
         out = torch.empty((B, F), dtype=torch.complex64, device=chunks.device)
-        with _on_device(chunks.device):
-            _lib.check(_lib.lib().smx_ema_scan_forward(chunks.data_ptr(), _ptr(init), rho_logit.data_ptr(),
-                                                       theta_raw.data_ptr(), out.data_ptr(), mode, B, S, F,
-                                                       _stream(chunks.device)))
-        ctx.mode, ctx.has_init = mode, init is not None
-        ctx.save_for_backward(chunks, rho_logit, theta_raw, init if init is not None else chunks.new_empty(0))
+        _call(chunks.device, "smx_ema_scan_forward", chunks.data_ptr(), _ptr(init), rho_logit.data_ptr(),
+              theta_raw.data_ptr(), out.data_ptr(), mode, B, S, F, _stream(chunks.device))
+        ctx.mode = mode
+        ctx.save_for_backward(chunks, rho_logit, theta_raw, init)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
         chunks, rho_logit, theta_raw, init = ctx.saved_tensors
-        init = init if ctx.has_init else None
         B, S, F = chunks.shape
-        g = _dense(g.to(torch.complex64))
+        g = _grad_c64(g)
         need = ctx.needs_input_grad
         gx = torch.empty_like(chunks) if need[0] else None
         gr = torch.empty_like(rho_logit) if need[1] else None
         gt = torch.empty_like(theta_raw) if need[2] and ctx.mode == 0 else None
-        gi = torch.empty_like(g) if ctx.has_init and need[3] else None
+        gi = torch.empty_like(g) if init is not None and need[3] else None
         ws = _ema_ws(g.device, B, S, F)
-        with _on_device(g.device):
-            _lib.check(_lib.lib().smx_ema_scan_backward(g.data_ptr(), chunks.data_ptr(), _ptr(init), rho_logit.data_ptr(),
-                                                        theta_raw.data_ptr(), _ptr(gx), _ptr(gi), _ptr(gr), _ptr(gt),
-                                                        ws.data_ptr(), ws.numel(), ctx.mode, B, S, F, _stream(g.device)))
+        _call(g.device, "smx_ema_scan_backward", g.data_ptr(), chunks.data_ptr(), _ptr(init), rho_logit.data_ptr(),
+              theta_raw.data_ptr(), _ptr(gx), _ptr(gi), _ptr(gr), _ptr(gt), *_ws_arg(ws), ctx.mode, B, S, F,
+              _stream(g.device))
         return gx, gr, gt, gi, None
 
 
@@ -1872,9 +1773,8 @@ class _EmaScanTokens(torch.autograd.Function):
         B, T = tokens.shape
         out = torch.empty((B, L // 2 + 1), dtype=torch.complex64, device=tokens.device)
         ctx.args = (tokens.data_ptr(), tokens.element_size(), tokens.stride(0))
-        with _on_device(tokens.device):
-            _lib.check(_lib.lib().smx_ema_tokens_forward(*ctx.args, None, rho_logit.data_ptr(), theta_raw.data_ptr(),
-                                                         out.data_ptr(), mode, B, T, L, _stream(tokens.device)))
+        _call(tokens.device, "smx_ema_tokens_forward", *ctx.args, None, rho_logit.data_ptr(), theta_raw.data_ptr(),
+              out.data_ptr(), mode, B, T, L, _stream(tokens.device))
         ctx.mode, ctx.L = mode, L
         ctx.save_for_backward(tokens, rho_logit, theta_raw)
         return out
@@ -1885,20 +1785,18 @@ class _EmaScanTokens(torch.autograd.Function):
         tokens, rho_logit, theta_raw = ctx.saved_tensors
         B, T = tokens.shape
         L = ctx.L
-        g = _dense(g.to(torch.complex64))
+        g = _grad_c64(g)
         gr = torch.empty_like(rho_logit) if ctx.needs_input_grad[2] else None
         gt = torch.empty_like(theta_raw) if ctx.needs_input_grad[3] and ctx.mode == 0 else None
         ws = _ema_ws(g.device, B, T // L, L // 2 + 1)
-        with _on_device(g.device):
-            _lib.check(_lib.lib().smx_ema_tokens_backward(g.data_ptr(), *ctx.args, None, rho_logit.data_ptr(),
-                                                          theta_raw.data_ptr(), None, _ptr(gr), _ptr(gt), ws.data_ptr(),
-                                                          ws.numel(), ctx.mode, B, T, L, _stream(g.device)))
+        _call(g.device, "smx_ema_tokens_backward", g.data_ptr(), *ctx.args, None, rho_logit.data_ptr(),
+              theta_raw.data_ptr(), None, _ptr(gr), _ptr(gt), *_ws_arg(ws), ctx.mode, B, T, L, _stream(g.device))
         return None, None, gr, gt, None
 
 
 def _ema_params(F: int, rho_logit: torch.Tensor, theta_raw: torch.Tensor):
     for name, p in (("rho_logit", rho_logit), ("theta_raw", theta_raw)):
-        _require_gpu_f32(name, p)
+        _require(name, p)
         if tuple(p.shape) != (F,):
             raise ValueError(f"{name} must be (F,) = ({F},), got {tuple(p.shape)}")
     return _dense(rho_logit), _dense(theta_raw)
@@ -1910,8 +1808,7 @@ def ema_scan(chunks: torch.Tensor, rho_logit: torch.Tensor, theta_raw: torch.Ten
     (None: zeros): one launch forward, one scan launch and a small fixed-order sum backward; differentiable in chunks,
     rho_logit, theta_raw (None in polar mode, where it takes no part) and init."""
     m = _ema_mode(mode)
-    if not (isinstance(chunks, torch.Tensor) and chunks.is_cuda and chunks.dtype == torch.complex64 and chunks.dim() == 3):
-        raise TypeError("chunks must be a (B, S, F) complex64 tensor on a ROCm device")
+    _require("chunks", chunks, _C64, what="a (B, S, F) complex64 tensor", dim=3)
     B, S, F = chunks.shape
     rho_logit, theta_raw = _ema_params(F, rho_logit, theta_raw)
     if init is not None and not (init.is_cuda and init.dtype == torch.complex64 and tuple(init.shape) == (B, F)):
@@ -1930,9 +1827,7 @@ def ema_scan_tokens(tokens: torch.Tensor, chunk_len: int, rho_logit: torch.Tenso
     L = int(chunk_len)
     if not 2 <= L <= 64:
         raise ValueError(f"chunk_len must be in 2..64, got {L}")
-    if not (isinstance(tokens, torch.Tensor) and tokens.is_cuda and tokens.dim() == 2
-            and tokens.dtype in (torch.uint8, torch.int64)):
-        raise TypeError("tokens must be a (B, T) uint8 or int64 tensor on a ROCm device")
+    _require("tokens", tokens, (torch.uint8, torch.int64), what="a (B, T) uint8 or int64 tensor", dim=2)
     rho_logit, theta_raw = _ema_params(L // 2 + 1, rho_logit, theta_raw)
     if tokens.shape[0] == 0:
         return torch.empty((0, L // 2 + 1), dtype=torch.complex64, device=tokens.device)

@@ -25,6 +25,7 @@ import torch
 
 from . import _lib
 from .fixed_spectral import FixedSpectralBlock, cutoff_mask, next_pow2
+from .functional import _call, _ptr, _stream
 
 
 def stream_taps(block: FixedSpectralBlock, n_fft: int, chunk: int, cutoff=None) -> torch.Tensor:
@@ -167,10 +168,6 @@ def _state(name: str, t, dtype, shape=None) -> None:
         raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 def stream_push(h: torch.Tensor, ln: torch.nn.LayerNorm, ring: torch.Tensor, sum: torch.Tensor,
                 pos: torch.Tensor) -> torch.Tensor:
     """smx_stream_push: ring[b, (pos[b] + n) % T] = ln(h[b, n]) for the chunk h (Bt, chunk, C), the window sum (hi, lo)
@@ -184,10 +181,8 @@ def stream_push(h: torch.Tensor, ln: torch.nn.LayerNorm, ring: torch.Tensor, sum
         raise ValueError(f"h must be ({Bt}, chunk, {C}), got {tuple(h.shape)}")
     pooled = torch.empty((Bt, C), dtype=torch.float32, device=h.device)
     w, b = _dense_f32(ln.weight, "ln.weight"), _dense_f32(ln.bias, "ln.bias")
-    with torch.cuda.device(h.device):
-        _lib.check(_lib.lib().smx_stream_push(h.data_ptr(), _ptr(w), _ptr(b), ln.eps, ring.data_ptr(), sum.data_ptr(),
-                                              pos.data_ptr(), pooled.data_ptr(), Bt, T, C, h.shape[1],
-                                              torch._C._cuda_getCurrentRawStream(h.device.index)))
+    _call(h.device, "smx_stream_push", h.data_ptr(), _ptr(w), _ptr(b), ln.eps, ring.data_ptr(), sum.data_ptr(),
+          pos.data_ptr(), pooled.data_ptr(), Bt, T, C, h.shape[1], _stream(h.device))
     return pooled
 
 
@@ -205,11 +200,9 @@ def stream_conv(h: torch.Tensor, ring: torch.Tensor, pos: torch.Tensor, taps: to
         raise ValueError(f"taps must hold K + 2 chunk - 2 = {int(kernel_len) + 2 * h.shape[1] - 2} floats")
     w, b = _dense_f32(ffn_ln.weight, "ffn_ln.weight"), _dense_f32(ffn_ln.bias, "ffn_ln.bias")
     h_out, ff_in = torch.empty_like(h), torch.empty_like(h)
-    with torch.cuda.device(h.device):
-        _lib.check(_lib.lib().smx_stream_conv(h.data_ptr(), ring.data_ptr(), pos.data_ptr(), taps.data_ptr(),
-                                              scale.data_ptr(), _ptr(w), _ptr(b), ffn_ln.eps, h_out.data_ptr(),
-                                              ff_in.data_ptr(), Bt, T, int(kernel_len), C, h.shape[1],
-                                              torch._C._cuda_getCurrentRawStream(h.device.index)))
+    _call(h.device, "smx_stream_conv", h.data_ptr(), ring.data_ptr(), pos.data_ptr(), taps.data_ptr(), scale.data_ptr(),
+          _ptr(w), _ptr(b), ffn_ln.eps, h_out.data_ptr(), ff_in.data_ptr(), Bt, T, int(kernel_len), C, h.shape[1],
+          _stream(h.device))
     return h_out, ff_in
 
 

@@ -15,15 +15,11 @@ from torch.autograd.function import once_differentiable
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import _lib
-from .functional import _require_gpu_f32, _stream, spectral_mix
+from .functional import _C64, _call, _require, _stream, spectral_mix
 
 
 def _require_gpu_c64(name: str, t: torch.Tensor) -> None:
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} is on {t.device}: this path has no CPU implementation")
-    if t.dtype != torch.complex64:
-        raise TypeError(f"{name} must be complex64, got {t.dtype}")
+    _require(name, t, _C64, "this path has no CPU implementation", typed=False)
 
 
 class WirtingerGradient(Function):
@@ -44,9 +40,7 @@ class WirtingerGradient(Function):
         w = weight_complex.resolve_conj().contiguous()
         out = torch.empty_like(x)
         batch, inner = x.shape[0], w.numel()
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().smx_cmul(x.data_ptr(), w.data_ptr(), out.data_ptr(), batch, inner,
-                                           0, _stream(x.device)))
+        _call(x.device, "smx_cmul", x.data_ptr(), w.data_ptr(), out.data_ptr(), batch, inner, 0, _stream(x.device))
         ctx.save_for_backward(x, w)
         return out
 
@@ -58,12 +52,9 @@ class WirtingerGradient(Function):
         batch, inner = x.shape[0], w.numel()
         grad_x = torch.empty_like(x)
         grad_w = torch.empty_like(w)
-        with torch.cuda.device(x.device):
-            s = _stream(x.device)
-            _lib.check(_lib.lib().smx_cmul(g.data_ptr(), w.data_ptr(), grad_x.data_ptr(), batch,
-                                           inner, 1, s))
-            _lib.check(_lib.lib().smx_cmul_grad_w(x.data_ptr(), g.data_ptr(), grad_w.data_ptr(),
-                                                  batch, inner, s))
+        s = _stream(x.device)
+        _call(x.device, "smx_cmul", g.data_ptr(), w.data_ptr(), grad_x.data_ptr(), batch, inner, 1, s)
+        _call(x.device, "smx_cmul_grad_w", x.data_ptr(), g.data_ptr(), grad_w.data_ptr(), batch, inner, s)
         return grad_x, grad_w
 
 
@@ -110,7 +101,7 @@ class _FilterFn(Function):
     def forward(ctx, x_freq, w_real, w_imag):
         _require_gpu_c64("x_freq", x_freq)
         for name, w in (("weight.real", w_real), ("weight.imag", w_imag)):
-            _require_gpu_f32(name, w)
+            _require(name, w)
             if w.device != x_freq.device:
                 raise RuntimeError(f"{name} is on {w.device} but x_freq is on {x_freq.device}")
             if w.dim() != 2 or w.shape[0] != x_freq.shape[2] or w.shape != w_real.shape:
@@ -121,10 +112,8 @@ class _FilterFn(Function):
         B, N, D = x.shape
         F = w_real.shape[1]
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().smx_wfilter_forward(
-                x.data_ptr(), w_real.data_ptr(), w_imag.data_ptr(), out.data_ptr(), B, N, D, F, 0,
-                _stream(x.device)))
+        _call(x.device, "smx_wfilter_forward", x.data_ptr(), w_real.data_ptr(), w_imag.data_ptr(), out.data_ptr(),
+              B, N, D, F, 0, _stream(x.device))
         ctx.save_for_backward(x, w_real, w_imag)
         return out
 
@@ -139,18 +128,16 @@ class _FilterFn(Function):
         B, N, D = x.shape
         F = w_real.shape[1]
         gx = gwr = gwi = None
-        with torch.cuda.device(x.device):
-            s = _stream(x.device)
-            if ctx.needs_input_grad[0]:
-                gx = torch.empty_like(x)
-                _lib.check(_lib.lib().smx_wfilter_forward(
-                    g.data_ptr(), w_real.data_ptr(), w_imag.data_ptr(), gx.data_ptr(), B, N, D, F, 1,
-                    s))
-            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-                gwr = torch.empty_like(w_real)
-                gwi = torch.empty_like(w_imag)
-                _lib.check(_lib.lib().smx_wfilter_grad_w(
-                    x.data_ptr(), g.data_ptr(), gwr.data_ptr(), gwi.data_ptr(), B, N, D, F, s))
+        s = _stream(x.device)
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            _call(x.device, "smx_wfilter_forward", g.data_ptr(), w_real.data_ptr(), w_imag.data_ptr(), gx.data_ptr(),
+                  B, N, D, F, 1, s)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gwr = torch.empty_like(w_real)
+            gwi = torch.empty_like(w_imag)
+            _call(x.device, "smx_wfilter_grad_w", x.data_ptr(), g.data_ptr(), gwr.data_ptr(), gwi.data_ptr(),
+                  B, N, D, F, s)
         return gx, gwr, gwi
 
 
