@@ -606,6 +606,42 @@ int smx_ema_tokens_backward(const float* g, const void* tokens, int token_bytes,
                             float* grad_theta_raw, void* workspace, size_t workspace_bytes, int mode, int B, int T, int L,
                             void* stream);
 
+/* The word-structure heads of fft_lm's bicameral trainer (fft_lm/phase_clock.py, fft_lm/segmentation_head.py).
+ *   smx_word_targets  both target functions of byte tokens (B, T) in ONE launch without a host synchronisation, replacing
+ *                     the per-byte `.item()` walk of fft_lm/phase_clock.py:83-113 (generate_phase_targets) and the
+ *                     per-position op loop of fft_lm/segmentation_head.py:77-97 (get_word_boundaries).  tokens as in
+ *                     smx_ema_tokens_* (token_bytes 1 = uint8 or 8 = int64, row_stride elements between rows, >= T); an
+ *                     int64 value outside 0..255 is an ordinary word byte.
+ *                       phase (B, T, 2), or NULL: with P = {32..47} u {58..64}, a word is a maximal run of non-P bytes
+ *                         inside the row; position q of a word of length n gets (cos, sin)(pi q / (n - 1)) (n = 1: (1, 0)),
+ *                         formed by sincospif(q / (n - 1)): a word start is exactly (1, 0); a byte of P gets (0, 0).
+ *                         10 and 13, 91..96 and 123..126 are word bytes here.
+ *                       boundary (B, T), or NULL: 1 where byte t + 1 is in S = P u {91..96} u {123..126} u {10, 13} and at
+ *                         t = T - 1, else 0.
+ *                     One workgroup per row: the delimiter bits of the row in LDS, a forward max-scan (last delimiter
+ *                     before a 64-position word) and a backward min-scan (first one after it) over them, then the fill.
+ *                     1 <= T <= 65536, B T < 2^31.  No atomics, no flags, no second launch.
+ *   smx_head_*        the O-neuron row head, O = 1 or 2, replacing nn.Linear(d_model, 2) of fft_lm/phase_clock.py:53,65 and
+ *                     nn.Linear(d_model, 1) of fft_lm/segmentation_head.py:43,55 over all R = B T rows of width C, float32:
+ *                       y[r, o] = sum_e h[r, e] w[o, e] + b[o]           (b may be NULL)
+ *                     one wavefront per row, the weight rows in registers.  Backward, one launch and the fixed-order
+ *                     column sum of the LayerNorm gradients: grad_h[r, :] = sum_o g[r, o] w[o, :], grad_w[o, e] =
+ *                     sum_r g[r, o] h[r, e], grad_b[o] = sum_r g[r, o] -- bitwise reproducible; each of grad_h, grad_w,
+ *                     grad_b may be NULL (all NULL: nothing is enqueued).  h, grad_h: 16-byte aligned; C a width of the
+ *                     LayerNorm row kernels (smx_head_supported(C, O) = smx_block_supported(C) and O in {1, 2}).
+ *                     Workspace from smx_head_workspace_bytes, 256-byte aligned.
+ * NULL required pointers, both target outputs NULL, token_bytes other than 1 or 8, misaligned int64 tokens,
+ * row_stride < T, B, T or R <= 0, T > 65536: SMX_ERR_INVALID; O other than 1 or 2 or an unsupported C:
+ * SMX_ERR_UNSUPPORTED; a missing, short or unaligned workspace: SMX_ERR_WORKSPACE.  Nothing is enqueued then, nothing is
+ * ever allocated, the host is never synchronised. */
+int smx_word_targets(const void* tokens, int token_bytes, long long row_stride, float* phase, float* boundary, int B,
+                     int T, void* stream);
+int smx_head_supported(int C, int O);
+int smx_head_workspace_bytes(long long R, int C, int O, size_t* out);
+int smx_head_forward(const float* h, const float* w, const float* b, float* y, long long R, int C, int O, void* stream);
+int smx_head_backward(const float* g, const float* h, const float* w, float* grad_h, float* grad_w, float* grad_b,
+                      void* workspace, size_t workspace_bytes, long long R, int C, int O, void* stream);
+
 /* Overlap-save chunk generation: one chunk step of a FixedSpectralBlock at inference as two row-kernel launches
  * around the block's gate_ctx GEMV (which stays the caller's), replacing the per-chunk op sequence of
  * scripts/generate_chunked_overlap_save.py:101-172 (LayerNorm of the chunk, a torch.cat of the whole (Bt, T, C) window,

@@ -8,7 +8,8 @@ from .spectral_layers import HybridSpectralAttention, SpectralMixingLayer, Spect
 from .wirtinger_ops import (ComplexParameter, WirtingerGradient, WirtingerSpectralFilter,
                             spectral_mix_with_filter)
 from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft, rfft_bins, seq_fft,
-                         spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens)
+                         spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens, narrow_head,
+                         word_targets)
 from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
@@ -17,6 +18,8 @@ from .fixed_spectral import FixedSpectralBlock, FixedSpectralLM, FrequencyConvFu
 from .frequency_native import BicameralBlock, FrequencyNativeBlock, PhaseShift, SpectralFFN, SpectralLayerNorm
 from .spectral_ssm import EMAConfig, SpectralEMA
 from .chunk_head import ChunkLM, vectorized_windows
+from .phase_clock import PhaseClockChunkLM, PhaseClockHead, compute_phase_clock_loss, generate_phase_targets
+from .segmentation_head import SegmentationHead, SegmentedChunkLM, compute_segmented_loss, get_word_boundaries
 from .streaming import (LayerStream, StreamStates, generate_chunked, init_layer_states, stream_taps,
                         update_backbone_chunk)
 from .distributed import GradSync, attach_grad_sync, all_reduce_grads, shard_batch
@@ -32,5 +35,7 @@ __all__ = [
     "SpectralLayerNorm", "EMAConfig", "SpectralEMA", "ChunkLM", "vectorized_windows", "ema_scan", "ema_scan_tokens",
     "GradSync", "attach_grad_sync", "all_reduce_grads", "shard_batch", "FixedSpectralLM", "LMConfig", "StreamStates",
     "LayerStream", "stream_taps", "init_layer_states", "update_backbone_chunk", "generate_chunked",
+    "PhaseClockHead", "PhaseClockChunkLM", "generate_phase_targets", "compute_phase_clock_loss", "SegmentationHead",
+    "SegmentedChunkLM", "get_word_boundaries", "compute_segmented_loss", "word_targets", "narrow_head",
 ]
 __version__ = "0.2.0"

@@ -2130,6 +2130,63 @@ int smx_ema_tokens_backward(const float* g, const void* tokens, int token_bytes,
                  workspace_bytes, stream);
 }
 
+// ---- word-structure heads: targets (smx_ema.hip) and the O-neuron row head (smx_block.hip) ----------------------------------
+int smx_word_targets(const void* tokens, int token_bytes, long long row_stride, float* phase, float* boundary, int B,
+                     int T, void* stream) {
+  if (B <= 0 || T <= 0) return fail(SMX_ERR_INVALID, "shape must be positive: B=%d T=%d", B, T);
+  if (T > WT_MAX_T) return fail(SMX_ERR_INVALID, "T must be at most %d, got %d", WT_MAX_T, T);
+  if ((long long)B * T >= (1ll << 31)) return fail(SMX_ERR_INVALID, "B*T too large");
+  if (token_bytes != 1 && token_bytes != 8) return fail(SMX_ERR_INVALID, "token_bytes must be 1 (uint8) or 8 (int64)");
+  if (!tokens) return fail(SMX_ERR_INVALID, "tokens must be non-NULL");
+  if (!phase && !boundary) return fail(SMX_ERR_INVALID, "phase and boundary are both NULL");
+  if (row_stride < T) return fail(SMX_ERR_INVALID, "row_stride must be at least T");
+  if (token_bytes == 8 && ((uintptr_t)tokens & 7)) return fail(SMX_ERR_INVALID, "int64 tokens must be 8-byte aligned");
+  if (((uintptr_t)phase & 7) || ((uintptr_t)boundary & 3))
+    return fail(SMX_ERR_INVALID, "phase must be 8-byte aligned and boundary 4-byte aligned");
+  HIP_TRY(launch_word_targets(tokens, token_bytes == 1 ? 1 : 2, row_stride, phase, boundary, B, T, (hipStream_t)stream));
+  return SMX_OK;
+}
+
+static int head_check(long long R, int C, int O) {
+  if (R <= 0 || C <= 0) return fail(SMX_ERR_INVALID, "shape must be positive: R=%lld C=%d", R, C);
+  if (O != 1 && O != 2) return fail(SMX_ERR_UNSUPPORTED, "the row head has O = 1 or 2 outputs, got %d", O);
+  if (!ln_supported(C)) return fail(SMX_ERR_UNSUPPORTED, "LayerNorm width D=%d is not supported", C);
+  if (R * C >= (1ll << 40)) return fail(SMX_ERR_INVALID, "R*C too large");
+  return SMX_OK;
+}
+static size_t head_need(long long R, int C) { return SYNC_BYTES + al(head_part_w_bytes(R, C)) + al(head_part_b_bytes(R)); }
+int smx_head_supported(int C, int O) { return (O == 1 || O == 2) && ln_supported(C) ? 1 : 0; }
+int smx_head_workspace_bytes(long long R, int C, int O, size_t* out) {
+  if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
+  if (int rc = head_check(R, C, O)) return rc;
+  *out = head_need(R, C);
+  return SMX_OK;
+}
+int smx_head_forward(const float* h, const float* w, const float* b, float* y, long long R, int C, int O, void* stream) {
+  if (int rc = head_check(R, C, O)) return rc;
+  if (!h || !w || !y) return fail(SMX_ERR_INVALID, "h, w, y must be non-NULL");
+  if (((uintptr_t)h | (uintptr_t)w) & 15) return fail(SMX_ERR_INVALID, "h and w must be 16-byte aligned");
+  if (((uintptr_t)b | (uintptr_t)y) & 3) return fail(SMX_ERR_INVALID, "b and y must be 4-byte aligned");
+  HIP_TRY(launch_head_fwd(h, w, b, y, R, C, O, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_head_backward(const float* g, const float* h, const float* w, float* grad_h, float* grad_w, float* grad_b,
+                      void* workspace, size_t workspace_bytes, long long R, int C, int O, void* stream) {
+  if (int rc = head_check(R, C, O)) return rc;
+  if (!g || (grad_w && !h) || (grad_h && !w))
+    return fail(SMX_ERR_INVALID, "g, h (with grad_w), w (with grad_h) must be non-NULL");
+  if (((uintptr_t)h | (uintptr_t)w | (uintptr_t)grad_h) & 15)
+    return fail(SMX_ERR_INVALID, "h, w and grad_h must be 16-byte aligned");
+  if (((uintptr_t)g | (uintptr_t)grad_w | (uintptr_t)grad_b) & 3)
+    return fail(SMX_ERR_INVALID, "g, grad_w and grad_b must be 4-byte aligned");
+  if (grad_h && (grad_h == h || grad_h == g)) return fail(SMX_ERR_INVALID, "grad_h must not alias h or g");
+  if (int rc = need_ws(workspace, workspace_bytes, head_need(R, C), "smx_head_workspace_bytes")) return rc;
+  char* part_w = (char*)workspace + SYNC_BYTES;
+  HIP_TRY(launch_head_bwd(g, h, w, grad_h, grad_w, grad_b, (float*)part_w, (float*)(part_w + al(head_part_w_bytes(R, C))),
+                          R, C, O, (hipStream_t)stream));
+  return SMX_OK;
+}
+
 // ---- overlap-save chunk generation (smx_stream.hip) -----------------------------------------------------------------------
 static int stream_check(const char* fn, int Bt, int T, int K, int C, int chunk, std::initializer_list<const void*> ptrs) {
   if (Bt < 1 || Bt > (1 << 24)) return fail(SMX_ERR_INVALID, "%s: Bt must be in 1..2^24, got %d", fn, Bt);

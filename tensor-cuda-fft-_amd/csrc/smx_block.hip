@@ -10,7 +10,9 @@
 //                   (2-byte rows, IO != 0: grad_h stays f32 in a scratch of its own, x / g are read and grad_x is
 //                   written in the IO type -- not in place, the same arithmetic, one rounding at the store);
 //   * k_ln_colsum   fixed-order reduction of those partials (bitwise reproducible);
-//   * k_ln_apply, k_add_rows   unfused fallback used with the split / direct transform paths.
+//   * k_ln_apply, k_add_rows   unfused fallback used with the split / direct transform paths;
+//   * k_head_fwd, k_head_bwd   the 1- or 2-neuron head of fft_lm's word-structure models over all B T rows: the same row
+//                   walk, its parameter-gradient partials in the slab layout k_ln_colsum reduces.
 // One wavefront per row, lane l holds elements (l + 64 c) VEC + [0, VEC), c < CH, in registers:
 // every global access is a full-wave contiguous segment and a row is read exactly once.
 // Vec, wave_sum, the LayerNorm-backward accumulation, the (VEC, CH) dispatch and the launch geometry
@@ -372,6 +374,112 @@ bool ln_dispatch(int D, Fn f) {
   return D % 4 == 0 ? row_dispatch<4, 16>(D, f) : row_dispatch<1, 16, 4>(D, f);
 }
 
+// ---- the O-neuron head, O = 1 or 2 (reference fft_lm/phase_clock.py:53,65, fft_lm/segmentation_head.py:43,55) ---------
+// A Linear with one or two output columns over all B T rows is a row reduction bound by the read of h: one wavefront per
+// row, the O weight rows held in registers across the wave's row walk, one wave sum per output.
+template <int VEC, int CH, int O>
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_head_fwd(const float* __restrict__ h, const float* __restrict__ w,
+                                                             const float* __restrict__ b, float* __restrict__ y,
+                                                             long long rows, int D) {
+  constexpr int R = CH <= 2 ? 2 : 1;          // rows in flight per wavefront (as k_ln_stats)
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  Vec<VEC> wr[O][CH];
+  float bias[O];
+#pragma unroll
+  for (int o = 0; o < O; ++o) {
+    row_load_cached(wr[o], w + (size_t)o * D, D, lane, 0.f);
+    bias[o] = b ? b[o] : 0.f;
+  }
+  const long long step = (long long)gridDim.x * ROW_WAVES;
+  for (long long row0 = (long long)blockIdx.x * ROW_WAVES + wv; row0 < rows; row0 += R * step) {
+    Vec<VEC> hv[R][CH];
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      const long long row = row0 + q * step;
+      if (row < rows) row_load(hv[q], h + (size_t)row * D, D, lane);
+      else zero(hv[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      const long long row = row0 + q * step;
+#pragma unroll
+      for (int o = 0; o < O; ++o) {
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < CH; ++c)
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) s = fmaf(hv[q][c].v[i], wr[o][c].v[i], s);
+        s = wave_sum(s);
+        if (lane == 0 && row < rows) y[row * O + o] = s + bias[o];
+      }
+    }
+  }
+}
+
+// grad_h[r, :] = sum_o g[r, o] w[o, :] (gh null: skipped), and per block the partials of grad_w[o, e] = sum_r g[r, o]
+// h[r, e] in part_w's (2, D) slab (row 1 is zero for O = 1) and of grad_b[o] = sum_r g[r, o] in part_b's pair: what
+// k_ln_colsum adds over the blocks in a fixed order.  A null part_w skips the read of h, a null part_b the sums of g.
+template <int VEC, int CH, int O>
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_head_bwd(const float* __restrict__ g, const float* __restrict__ h,
+                                                             const float* __restrict__ w, float* __restrict__ gh,
+                                                             float* __restrict__ part_w, float* __restrict__ part_b,
+                                                             long long rows, int D) {
+  __shared__ float red[ROW_WAVES][2][64 * VEC];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  Vec<VEC> wr[O][CH], acc[2][CH];
+#pragma unroll
+  for (int o = 0; o < O; ++o) row_load_cached(wr[o], gh ? w + (size_t)o * D : nullptr, D, lane, 0.f);
+  zero(acc[0]);
+  zero(acc[1]);
+  float gb[2] = {0.f, 0.f};
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows;
+       row += (long long)gridDim.x * ROW_WAVES) {
+    float gv[O];
+#pragma unroll
+    for (int o = 0; o < O; ++o) {
+      gv[o] = g[row * O + o];
+      gb[o] += gv[o];
+    }
+    const size_t off = (size_t)row * D;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int e = (lane + 64 * c) * VEC;
+      if (e < D) {
+        if (part_w) {
+          Vec<VEC> hv;
+          hv.load(h + off + e);
+#pragma unroll
+          for (int o = 0; o < O; ++o)
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) acc[o][c].v[i] = fmaf(gv[o], hv.v[i], acc[o][c].v[i]);
+        }
+        if (gh) {
+          Vec<VEC> ov;
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) {
+            float s = gv[0] * wr[0][c].v[i];
+            if constexpr (O == 2) s = fmaf(gv[1], wr[1][c].v[i], s);
+            ov.v[i] = s;
+          }
+          ov.store(gh + off + e);
+        }
+      }
+    }
+  }
+  if (part_w) block_partials(acc[0], acc[1], part_w + (size_t)blockIdx.x * 2 * D, D, 0, D, red, lane, wv);
+  if (part_b) {                               // waves are added in index order
+    if (lane == 0) { red[wv][0][0] = gb[0]; red[wv][1][0] = gb[1]; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+      for (int w2 = 0; w2 < ROW_WAVES; ++w2) { a0 += red[w2][0][0]; a1 += red[w2][1][0]; }
+      part_b[(size_t)blockIdx.x * 2] = a0;
+      part_b[(size_t)blockIdx.x * 2 + 1] = a1;
+    }
+  }
+}
+
 }  // namespace
 
 int ln_num_blocks(long long rows) {
@@ -470,6 +578,37 @@ hipError_t launch_ln_bwd_io(const float* gh, const void* x, const void* g, void*
   else launch_ln_bwd_t<2>(gh, x, g, dx, stats, gamma, part, rows, D, s);
   if (hipError_t e = hipGetLastError()) return e;
   return launch_ln_colsum(part, ln_num_blocks(rows), D, g_gamma, g_beta, s);
+}
+
+size_t head_part_w_bytes(long long R, int C) { return (size_t)ln_num_blocks(R) * 2 * C * sizeof(float); }
+size_t head_part_b_bytes(long long R) { return (size_t)ln_num_blocks(R) * 2 * sizeof(float); }
+
+hipError_t launch_head_fwd(const float* h, const float* w, const float* b, float* y, long long R, int C, int O,
+                           hipStream_t s) {
+  if (!ln_supported(C) || (O != 1 && O != 2)) return hipErrorInvalidValue;
+  ln_dispatch(C, [&](auto vec, auto ch) {
+    constexpr int V = decltype(vec)::value, H = decltype(ch)::value;
+    if (O == 1) row_launch(k_head_fwd<V, H, 1>, R, s, h, w, b, y, R, C);
+    else row_launch(k_head_fwd<V, H, 2>, R, s, h, w, b, y, R, C);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_head_bwd(const float* g, const float* h, const float* w, float* grad_h, float* grad_w, float* grad_b,
+                           float* part_w, float* part_b, long long R, int C, int O, hipStream_t s) {
+  if (!ln_supported(C) || (O != 1 && O != 2)) return hipErrorInvalidValue;
+  if (!grad_h && !grad_w && !grad_b) return hipSuccess;
+  float* pw = grad_w ? part_w : nullptr;
+  float* pb = grad_b ? part_b : nullptr;
+  ln_dispatch(C, [&](auto vec, auto ch) {
+    constexpr int V = decltype(vec)::value, H = decltype(ch)::value;
+    if (O == 1) row_launch(k_head_bwd<V, H, 1>, R, s, g, h, w, grad_h, pw, pb, R, C);
+    else row_launch(k_head_bwd<V, H, 2>, R, s, g, h, w, grad_h, pw, pb, R, C);
+  });
+  if (hipError_t e = hipGetLastError()) return e;
+  const int nblk = ln_num_blocks(R);
+  if (hipError_t e = launch_ln_colsum(pw, nblk, C, grad_w, grad_w && O == 2 ? grad_w + C : nullptr, s)) return e;
+  return launch_ln_colsum(pb, nblk, 1, grad_b, grad_b && O == 2 ? grad_b + 1 : nullptr, s);
 }
 
 }  // namespace smx

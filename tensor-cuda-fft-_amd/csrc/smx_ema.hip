@@ -22,6 +22,9 @@
 // 2 byte - 255 (minus the chunk's first one for f > 0, which changes nothing because the twiddles of a bin f > 0
 // sum to zero): the DC and Nyquist bins are exact integer sums, and a run of equal bytes gives an exact zero in every
 // bin f > 0 -- where the kernel then takes u = 1.
+//
+// Also here, because the byte-token loader is: k_word_targets, the word-structure targets of the same tokens (phase
+// clock and boundary labels of fft_lm/phase_clock.py, fft_lm/segmentation_head.py) as one launch.
 #include "smx_kernels.h"
 
 namespace smx {
@@ -352,6 +355,107 @@ hipError_t launch_ema_bwd(const EmaSrc& src, bool polar, const cf* g, const cf* 
   if (g_rho || g_th)
     hipLaunchKernelGGL(k_ema_param_sum, dim3((src.F + EMA_BLOCK - 1) / EMA_BLOCK), dim3(EMA_BLOCK), 0, s, part, g_rho,
                        g_th, src.B, src.F);
+  return hipGetLastError();
+}
+
+// ---- word-structure targets of byte tokens -------------------------------------------------------------------------------
+// Both target functions of the bicameral trainer's heads in one launch (reference fft_lm/phase_clock.py:68-115,
+// fft_lm/segmentation_head.py:58-99).  The two delimiter sets differ on purpose: the phase clock breaks words at space
+// and the punctuation 33..47, 58..64 only, the boundary label also at brackets, braces and newlines.  A token is
+// compared as a number, so an int64 value outside 0..255 is a word byte.
+template <typename V> SMX_HD bool is_phase_delim(V v) { return (v >= 32 && v <= 47) || (v >= 58 && v <= 64); }
+template <typename V> SMX_HD bool is_boundary_delim(V v) {
+  return is_phase_delim(v) || (v >= 91 && v <= 96) || (v >= 123 && v <= 126) || v == 10 || v == 13;
+}
+
+// One workgroup per row.  A position needs the start and the end of its word, and a word may span the row:
+//   A  bits[w] = the phase-delimiter bits of positions 64 w .. 64 w + 63 (one ballot per wavefront; positions past T
+//      count as delimiters, so a word ends at T at the latest);
+//   B  thread i owns the words [i WPT, (i + 1) WPT): its highest and lowest delimiter, an inclusive max-scan forward
+//      and min-scan backward over the WT_BLOCK summaries, then before[w] = last delimiter in front of word w (-1: none)
+//      and after[w] = first delimiter behind it;
+//   C  the fill: a position looks at its own 64-bit word first and at before / after only when that has no delimiter on
+//      the side in question.
+template <int SRC>
+__global__ __launch_bounds__(WT_BLOCK) void k_word_targets(const void* __restrict__ tokens, long long row_stride,
+                                                           cf* __restrict__ phase, float* __restrict__ boundary, int T) {
+  typedef typename EmaTok<SRC>::type TOK;
+  constexpr int MAXW = WT_MAX_T / 64, NONE = 0x7fffffff;
+  __shared__ unsigned long long bits[MAXW];
+  __shared__ int before[MAXW], after[MAXW];
+  __shared__ int smax[WT_BLOCK], smin[WT_BLOCK];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const TOK* row = (const TOK*)tokens + (size_t)blockIdx.x * (size_t)row_stride;
+  const size_t o = (size_t)blockIdx.x * (size_t)T;
+  if (boundary)
+    for (int t = tid; t < T; t += WT_BLOCK) boundary[o + t] = (t == T - 1 || is_boundary_delim(row[t + 1])) ? 1.f : 0.f;
+  if (!phase) return;
+  const int NW = (T + 63) >> 6;
+  for (int base = 0; base < NW * 64; base += WT_BLOCK) {                  // A
+    const int p = base + tid;
+    const bool d = p >= T || is_phase_delim(row[p]);
+    const unsigned long long m = __ballot(d);
+    if (lane == 0 && (p >> 6) < NW) bits[p >> 6] = m;
+  }
+  __syncthreads();
+  const int WPT = (NW + WT_BLOCK - 1) / WT_BLOCK;                         // B
+  const int w0 = min(tid * WPT, NW), w1 = min(w0 + WPT, NW);
+  int hi = -1, lo = NONE;
+  for (int w = w0; w < w1; ++w) {
+    const unsigned long long m = bits[w];
+    if (m) {
+      hi = w * 64 + 63 - __builtin_clzll(m);
+      if (lo == NONE) lo = w * 64 + __builtin_ctzll(m);
+    }
+  }
+  smax[tid] = hi;
+  smin[tid] = lo;
+  __syncthreads();
+  for (int d = 1; d < WT_BLOCK; d <<= 1) {
+    const int a = tid >= d ? smax[tid - d] : -1;
+    const int b = tid + d < WT_BLOCK ? smin[tid + d] : NONE;
+    __syncthreads();
+    smax[tid] = max(smax[tid], a);
+    smin[tid] = min(smin[tid], b);
+    __syncthreads();
+  }
+  int run = tid ? smax[tid - 1] : -1;
+  for (int w = w0; w < w1; ++w) {
+    before[w] = run;
+    const unsigned long long m = bits[w];
+    if (m) run = w * 64 + 63 - __builtin_clzll(m);
+  }
+  run = tid + 1 < WT_BLOCK ? smin[tid + 1] : NONE;
+  for (int w = w1 - 1; w >= w0; --w) {
+    after[w] = run;
+    const unsigned long long m = bits[w];
+    if (m) run = w * 64 + __builtin_ctzll(m);
+  }
+  __syncthreads();
+  for (int t = tid; t < T; t += WT_BLOCK) {                               // C
+    const int w = t >> 6, bit = t & 63;
+    const unsigned long long m = bits[w];
+    cf out = mk(0.f, 0.f);
+    if (!((m >> bit) & 1ull)) {
+      const unsigned long long below = m & ((1ull << bit) - 1ull);
+      const unsigned long long above = bit == 63 ? 0ull : m & (~0ull << (bit + 1));
+      const int last = below ? w * 64 + 63 - __builtin_clzll(below) : before[w];
+      const int next = min(above ? w * 64 + __builtin_ctzll(above) : after[w], T);
+      const int s = last + 1, n = next - s, q = t - s;
+      float sn = 0.f, cs = 1.f;
+      if (n > 1) sincospif((float)q / (float)(n - 1), &sn, &cs);          // q == 0: exactly (1, 0)
+      out = mk(cs, sn);
+    }
+    phase[o + t] = out;
+  }
+}
+
+hipError_t launch_word_targets(const void* tokens, int kind, long long row_stride, float* phase, float* boundary, int B,
+                               int T, hipStream_t s) {
+  if (kind == 1)
+    hipLaunchKernelGGL(k_word_targets<1>, dim3(B), dim3(WT_BLOCK), 0, s, tokens, row_stride, (cf*)phase, boundary, T);
+  else
+    hipLaunchKernelGGL(k_word_targets<2>, dim3(B), dim3(WT_BLOCK), 0, s, tokens, row_stride, (cf*)phase, boundary, T);
   return hipGetLastError();
 }
 

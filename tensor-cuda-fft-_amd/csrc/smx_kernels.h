@@ -287,6 +287,12 @@ hipError_t launch_ema(const EmaSrc& src, bool polar, const cf* init, const float
 hipError_t launch_ema_bwd(const EmaSrc& src, bool polar, const cf* g, const cf* init, const float* rho_logit,
                           const float* theta_raw, cf* gx, cf* ginit, float* g_rho, float* g_th, cf* states, float* part,
                           hipStream_t s);
+// Word-structure targets of byte tokens (B, T), one workgroup per row: phase (B, T, 2) and / or boundary (B, T), either
+// may be null.  kind 1 / 2: uint8 / int64 tokens, rows row_stride elements apart.  T <= WT_MAX_T.
+constexpr int WT_MAX_T = 65536;
+constexpr int WT_BLOCK = 256;            // threads per row; thread i owns the 64-position words [i WPT, (i + 1) WPT)
+hipError_t launch_word_targets(const void* tokens, int kind, long long row_stride, float* phase, float* boundary, int B,
+                               int T, hipStream_t s);
 
 // ---- LayerNorm row kernels of the fused block (smx_block.hip) -------------------------------------
 constexpr int ROW_WAVES = 4;             // wavefronts (rows in flight) per block of the kernels sized by ln_num_blocks
@@ -312,6 +318,15 @@ hipError_t launch_ln_bwd_io(const float* gh, const void* x, const void* g, void*
                             const float* gamma, float* part, float* g_gamma, float* g_beta, long long rows, int D,
                             hipStream_t s, int io);
 hipError_t launch_ln_colsum(const float* part, int nblk, int D, float* g_gamma, float* g_beta, hipStream_t s);
+// The O-neuron head (O = 1, 2) over R rows of width C (ln_supported(C)): y[r, o] = sum_e h[r, e] w[o, e] + b[o].
+// Backward: grad_h = g w; block partials of grad_w in part_w (ln_num_blocks(R), 2, C) and of grad_b in part_b
+// (ln_num_blocks(R), 2), both reduced by k_ln_colsum in a fixed order.  Each of grad_h / grad_w / grad_b may be null.
+size_t head_part_w_bytes(long long R, int C);
+size_t head_part_b_bytes(long long R);
+hipError_t launch_head_fwd(const float* h, const float* w, const float* b, float* y, long long R, int C, int O,
+                           hipStream_t s);
+hipError_t launch_head_bwd(const float* g, const float* h, const float* w, float* grad_h, float* grad_w, float* grad_b,
+                           float* part_w, float* part_b, long long R, int C, int O, hipStream_t s);
 
 // ---- row kernels of EnhancedSpectralBlock (smx_enh.hip) --------------------------------------------
 constexpr int ENH_MAX_D = 1024;          // widest row (even) held in one wavefront's registers; the gate row is 2D

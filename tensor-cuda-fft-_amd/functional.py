@@ -1835,3 +1835,125 @@ def ema_scan_tokens(tokens: torch.Tensor, chunk_len: int, rho_logit: torch.Tenso
             or tokens.data_ptr() % tokens.element_size():
         tokens = tokens.contiguous()
     return _EmaScanTokens.apply(tokens, L, rho_logit, theta_raw, m)
+
+
+# ---- word-structure heads of the bicameral trainer: targets and the O-neuron row head (csrc/smx_ema.hip, smx_block.hip) --
+
+def _in_phase_set(v: torch.Tensor) -> torch.Tensor:
+    """P = {32..47} u {58..64}: where the phase clock breaks words (reference fft_lm/phase_clock.py:89)."""
+    return ((v >= 32) & (v <= 47)) | ((v >= 58) & (v <= 64))
+
+
+def _in_boundary_set(v: torch.Tensor) -> torch.Tensor:
+    """S = P u {91..96} u {123..126} u {10, 13}: what ends a word for the boundary label (reference
+    fft_lm/segmentation_head.py:81-92).  The two sets differ on purpose."""
+    return _in_phase_set(v) | ((v >= 91) & (v <= 96)) | ((v >= 123) & (v <= 126)) | (v == 10) | (v == 13)
+
+
+def _word_targets_torch(tokens: torch.Tensor, phase: bool, boundary: bool):
+    """The two target functions as a handful of whole-tensor ops (what CPU tokens run): a cummax / cummin pair for the
+    word of every position, angles in fp64 rounded once."""
+    B, T = tokens.shape
+    v = tokens.to(torch.int64)
+    ph = bd = None
+    if boundary:
+        bd = torch.ones((B, T), dtype=torch.float32, device=v.device)
+        bd[:, :-1] = _in_boundary_set(v[:, 1:]).to(torch.float32)
+    if phase:
+        d = _in_phase_set(v)
+        idx = torch.arange(T, device=v.device).expand(B, T)
+        last = torch.cummax(torch.where(d, idx, torch.full_like(idx, -1)), dim=1).values
+        nxt = torch.cummin(torch.where(d, idx, torch.full_like(idx, T)).flip(1), dim=1).values.flip(1)
+        start = last + 1
+        ang = (idx - start).double() / (nxt - start - 1).clamp(min=1).double() * torch.pi
+        ph = torch.stack((torch.cos(ang), torch.sin(ang)), dim=-1).to(torch.float32)
+        ph = torch.where(d[..., None], torch.zeros_like(ph), ph)
+    return ph, bd
+
+
+def word_targets(tokens: torch.Tensor, phase: bool = True, boundary: bool = True):
+    """(phase, boundary) of byte tokens (B, T), uint8 or int64, each None when not asked for, on the tokens' device:
+    phase (B, T, 2) fp32, the phase-clock targets of fft_lm.phase_clock.generate_phase_targets -- position q of a word of
+    n bytes at (cos, sin)(pi q / (n - 1)), delimiters at (0, 0) -- and boundary (B, T) fp32, the labels of
+    fft_lm.segmentation_head.get_word_boundaries.  On a ROCm device both come from ONE launch with no host
+    synchronisation (T <= 65536); CPU tokens take the same functions as whole-tensor torch ops.  Not differentiable."""
+    if not (isinstance(tokens, torch.Tensor) and tokens.dtype in (torch.uint8, torch.int64) and tokens.dim() == 2):
+        raise TypeError("tokens must be a (B, T) uint8 or int64 tensor")
+    if not (phase or boundary):
+        raise ValueError("word_targets: neither phase nor boundary asked for")
+    B, T = tokens.shape
+    dev = tokens.device
+    if not tokens.is_cuda or B == 0 or T == 0:
+        if B == 0 or T == 0:
+            return (torch.zeros((B, T, 2), dtype=torch.float32, device=dev) if phase else None,
+                    torch.zeros((B, T), dtype=torch.float32, device=dev) if boundary else None)
+        return _word_targets_torch(tokens, phase, boundary)
+    if tokens.shape[1] > 1 and tokens.stride(1) != 1 or tokens.stride(0) < tokens.shape[1] \
+            or tokens.data_ptr() % tokens.element_size():
+        tokens = tokens.contiguous()
+    ph = torch.empty((B, T, 2), dtype=torch.float32, device=dev) if phase else None
+    bd = torch.empty((B, T), dtype=torch.float32, device=dev) if boundary else None
+    _call(dev, "smx_word_targets", tokens.data_ptr(), tokens.element_size(), tokens.stride(0), _ptr(ph), _ptr(bd), B, T,
+          _stream(dev))
+    return ph, bd
+
+
+@functools.lru_cache(None)
+def head_supported(C: int, O: int) -> bool:
+    """O in {1, 2} and C a width of the LayerNorm row kernels.  (A property of the library, remembered per (C, O).)"""
+    return bool(_lib.lib().smx_head_supported(int(C), int(O)))
+
+
+@functools.lru_cache(None)
+def _head_ws_bytes(R: int, C: int, O: int) -> int:
+    """smx_head_workspace_bytes: a function of the shape alone, remembered per shape (one host call less per step)."""
+    return _query("smx_head_workspace_bytes", R, C, O)
+
+
+class _NarrowHead(torch.autograd.Function):
+    """y = h w^T + b over (R, C) rows with O = 1 or 2 outputs (reference fft_lm/phase_clock.py:65,
+    fft_lm/segmentation_head.py:55) through smx_head_forward / _backward: only the gradients autograd asks for are formed."""
+
+    @staticmethod
+    def forward(ctx, h, w, b):
+        R, C = h.shape
+        O = w.shape[0]
+        y = torch.empty((R, O), dtype=torch.float32, device=h.device)
+        _call(h.device, "smx_head_forward", h.data_ptr(), w.data_ptr(), _ptr(b), y.data_ptr(), R, C, O,
+              _stream(h.device))
+        ctx.has_bias = b is not None
+        ctx.save_for_backward(h, w)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        h, w = ctx.saved_tensors
+        R, C = h.shape
+        O = w.shape[0]
+        nig = ctx.needs_input_grad
+        gh = torch.empty_like(h) if nig[0] else None
+        gw = torch.empty_like(w) if nig[1] else None
+        gb = torch.empty(O, dtype=torch.float32, device=h.device) if ctx.has_bias and nig[2] else None
+        if gh is None and gw is None and gb is None:
+            return None, None, None
+        g = _grad_f32(g)
+        ws = _workspace(h.device, _head_ws_bytes(R, C, O))
+        _call(h.device, "smx_head_backward", g.data_ptr(), h.data_ptr(), w.data_ptr(), _ptr(gh), _ptr(gw), _ptr(gb),
+              *_ws_arg(ws), R, C, O, _stream(h.device))
+        return gh, gw, gb
+
+
+def narrow_head(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.linear(h, weight, bias) for a weight of one or two rows: (..., C) -> (..., O).  Native -- one wavefront per
+    row, the backward bitwise reproducible -- when h is an fp32 tensor on a ROCm device with fp32 parameters, C is a width
+    of the LayerNorm row kernels (head_supported) and autocast is off; F.linear everywhere else (CPU, bf16 / fp16,
+    under torch.autocast, other widths)."""
+    O, C = weight.shape
+    native = (h.is_cuda and h.dtype == torch.float32 and weight.dtype == torch.float32 and weight.device == h.device
+              and (bias is None or (bias.dtype == torch.float32 and bias.device == h.device))
+              and h.shape[-1] == C and h.numel() > 0 and not torch.is_autocast_enabled() and head_supported(C, O))
+    if not native:
+        return torch.nn.functional.linear(h, weight, bias)
+    y = _NarrowHead.apply(_dense(h.reshape(-1, C)), _dense(weight), _dense(bias))
+    return y.view(*h.shape[:-1], O)
