@@ -642,6 +642,48 @@ int smx_head_forward(const float* h, const float* w, const float* b, float* y, l
 int smx_head_backward(const float* g, const float* h, const float* w, float* grad_h, float* grad_w, float* grad_b,
                       void* workspace, size_t workspace_bytes, long long R, int C, int O, void* stream);
 
+/* Softmax cross-entropy over the rows of a logits matrix: the two nn.functional.cross_entropy calls of compute_dual_loss,
+ * fft_lm/dual_head.py:176-188 (256-way char loss; 50257-way token loss with ignore_index = 0), each logit read once per
+ * direction and nothing of size R x V written in the forward.
+ *   logits (R, V) float32, rows row_stride >= V elements apart; targets (R) int64; reduction SMX_XENT_MEAN / _SUM / _NONE.
+ *   forward, for every row r with t_r != ignore_index:
+ *       lse[r]  = log sum_j exp(x[r, j]), held as the pair (m, d) = (max_j x[r, j], log sum_j exp(x[r, j] - m))
+ *       l[r]    = lse[r] - x[r, t_r] = d - (x[r, t_r] - m)
+ *     lse (R, 2) floats is kept for the backward: m + d is the log-sum-exp, and the two stay apart because their sum
+ *     rounded to one float loses d beside a large |m| (logits of 1e30: exp(x - lse) would be 1 where it is 1 / n);
+ *     count[0] = number of rows that are not ignored, as a float (exact below 2^24
+ *     rows); loss = sum_r l[r] / count (MEAN), sum_r l[r] (SUM): one float, or l itself (NONE): R floats.  An ignored
+ *     row is not read: its l[r] and its lse pair are 0.
+ *   backward: grad[r, j] = (exp((x[r, j] - m) - d) - [j == t_r]) s_r, grad (R, V) dense, with s_r = g[0] / count[0]
+ *     (MEAN), g[0] (SUM), g[r] (NONE): g and count are read from device memory by the kernel, no scalar crosses to the
+ *     host.  An ignored row is not read and its gradient row is written as zeros (never multiplied: with every row ignored
+ *     the mean is 0 / 0 = NaN and the gradient is all zeros).
+ *   Edge semantics: -inf entries are ordinary (the loss is finite when any entry is finite); a row with +inf, or with
+ *     -inf only, has a NaN loss.  DIFFERENCE FROM TORCH: a target outside [0, V) that is not ignore_index -- a device-side
+ *     assert there -- makes that row's loss and its whole gradient row NaN here; the row is counted, and no address is
+ *     ever formed from the target.
+ *   Kernels: V a LayerNorm row width (V <= 4096 with V % 4 == 0, V <= 1024 otherwise): one wavefront per row, the row in
+ *     registers; its 16-byte chunks need logits, grad and row_stride * 4 to be multiples of 16 bytes -- otherwise the
+ *     call takes the one-element-per-lane instance (V <= 1024) or the streaming kernels, never a misaligned vector access.
+ *     Every other V up to 2^31 - 1: one workgroup of 256 threads per row, a running (max, sum) per thread merged in a
+ *     fixed order, scalar head up to 16-byte alignment, 16-byte body, scalar tail; row offsets are 64-bit.
+ *   The sum over rows: one (sum, count) partial per workgroup in the workspace, added in index order by a second,
+ *     one-workgroup launch: no atomics, no flags, bitwise reproducible.  smx_xent_supported(V) = V >= 1.
+ * NULL required pointers, R <= 0, V <= 0, row_stride < V, an unknown reduction, pointers that are not 4-byte (targets:
+ * 8-byte) aligned: SMX_ERR_INVALID; a missing, short or unaligned workspace (smx_xent_workspace_bytes, 256-byte aligned;
+ * forward only): SMX_ERR_WORKSPACE.  Nothing is enqueued then, nothing is ever allocated, the host is never synchronised. */
+#define SMX_XENT_MEAN 0
+#define SMX_XENT_SUM 1
+#define SMX_XENT_NONE 2
+int smx_xent_supported(int V);
+int smx_xent_workspace_bytes(long long R, int V, size_t* out);
+int smx_xent_forward(const float* logits, long long row_stride, const long long* targets, long long ignore_index,
+                     int reduction, float* loss, float* lse, float* count, void* workspace, size_t workspace_bytes,
+                     long long R, int V, void* stream);
+int smx_xent_backward(const float* g, const float* logits, long long row_stride, const long long* targets,
+                      long long ignore_index, int reduction, const float* lse, const float* count, float* grad,
+                      long long R, int V, void* stream);
+
 /* Overlap-save chunk generation: one chunk step of a FixedSpectralBlock at inference as two row-kernel launches
  * around the block's gate_ctx GEMV (which stays the caller's), replacing the per-chunk op sequence of
  * scripts/generate_chunked_overlap_save.py:101-172 (LayerNorm of the chunk, a torch.cat of the whole (Bt, T, C) window,

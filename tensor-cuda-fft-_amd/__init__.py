@@ -9,7 +9,7 @@ from .wirtinger_ops import (ComplexParameter, WirtingerGradient, WirtingerSpectr
                             spectral_mix_with_filter)
 from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft, rfft_bins, seq_fft,
                          spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens, narrow_head,
-                         word_targets)
+                         word_targets, cross_entropy)
 from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
@@ -20,6 +20,7 @@ from .spectral_ssm import EMAConfig, SpectralEMA
 from .chunk_head import ChunkLM, vectorized_windows
 from .phase_clock import PhaseClockChunkLM, PhaseClockHead, compute_phase_clock_loss, generate_phase_targets
 from .segmentation_head import SegmentationHead, SegmentedChunkLM, compute_segmented_loss, get_word_boundaries
+from .dual_head import DualHead, TokenAwareChunkLM, compute_dual_loss, get_gpt2_tokenizer, get_token_ids_fast
 from .streaming import (LayerStream, StreamStates, generate_chunked, init_layer_states, stream_taps,
                         update_backbone_chunk)
 from .distributed import GradSync, attach_grad_sync, all_reduce_grads, shard_batch
@@ -37,5 +38,6 @@ __all__ = [
     "LayerStream", "stream_taps", "init_layer_states", "update_backbone_chunk", "generate_chunked",
     "PhaseClockHead", "PhaseClockChunkLM", "generate_phase_targets", "compute_phase_clock_loss", "SegmentationHead",
     "SegmentedChunkLM", "get_word_boundaries", "compute_segmented_loss", "word_targets", "narrow_head",
+    "DualHead", "TokenAwareChunkLM", "get_token_ids_fast", "compute_dual_loss", "get_gpt2_tokenizer", "cross_entropy",
 ]
 __version__ = "0.2.0"

@@ -142,6 +142,10 @@ _SIGS = {
     "smx_head_workspace_bytes": (_I, [_LL, _I, _I, ctypes.POINTER(_SZ)]),
     "smx_head_forward": (_I, [_P] * 4 + [_LL, _I, _I, _P]),
     "smx_head_backward": (_I, [_P] * 7 + [_SZ, _LL, _I, _I, _P]),
+    "smx_xent_supported": (_I, [_I]),
+    "smx_xent_workspace_bytes": (_I, [_LL, _I, ctypes.POINTER(_SZ)]),
+    "smx_xent_forward": (_I, [_P, _LL, _P, _LL, _I] + [_P] * 4 + [_SZ, _LL, _I, _P]),
+    "smx_xent_backward": (_I, [_P, _P, _LL, _P, _LL, _I] + [_P] * 3 + [_LL, _I, _P]),
     "smx_stream_supported": (_I, [_I] * 4),
     "smx_stream_push": (_I, [_P] * 3 + [ctypes.c_float] + [_P] * 4 + [_I] * 4 + [_P]),
     "smx_stream_conv": (_I, [_P] * 7 + [ctypes.c_float] + [_P] * 2 + [_I] * 5 + [_P]),

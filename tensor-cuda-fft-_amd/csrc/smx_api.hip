@@ -2187,6 +2187,55 @@ int smx_head_backward(const float* g, const float* h, const float* w, float* gra
   return SMX_OK;
 }
 
+// ---- softmax cross-entropy (smx_block.hip) -----------------------------------------------------------------------------------
+static int xent_check(long long R, int V) {
+  if (R <= 0 || V <= 0) return fail(SMX_ERR_INVALID, "shape must be positive: R=%lld V=%d", R, V);
+  if (R >= (1ll << 31)) return fail(SMX_ERR_INVALID, "R too large");
+  return SMX_OK;
+}
+static int xent_check_args(const char* fn, long long R, int V, long long row_stride, int reduction) {
+  if (int rc = xent_check(R, V)) return rc;
+  if (row_stride < V) return fail(SMX_ERR_INVALID, "%s: row_stride must be at least V", fn);
+  if (reduction != SMX_XENT_MEAN && reduction != SMX_XENT_SUM && reduction != SMX_XENT_NONE)
+    return fail(SMX_ERR_INVALID, "%s: reduction must be SMX_XENT_MEAN, _SUM or _NONE, got %d", fn, reduction);
+  return SMX_OK;
+}
+static size_t xent_need(long long R) { return SYNC_BYTES + al((size_t)xent_num_blocks(R) * 2 * sizeof(float)); }
+int smx_xent_supported(int V) { return V >= 1 ? 1 : 0; }
+int smx_xent_workspace_bytes(long long R, int V, size_t* out) {
+  if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
+  if (int rc = xent_check(R, V)) return rc;
+  *out = xent_need(R);
+  return SMX_OK;
+}
+int smx_xent_forward(const float* logits, long long row_stride, const long long* targets, long long ignore_index,
+                     int reduction, float* loss, float* lse, float* count, void* workspace, size_t workspace_bytes,
+                     long long R, int V, void* stream) {
+  if (int rc = xent_check_args("smx_xent_forward", R, V, row_stride, reduction)) return rc;
+  if (!logits || !targets || !loss || !lse || !count)
+    return fail(SMX_ERR_INVALID, "logits, targets, loss, lse, count must be non-NULL");
+  if ((((uintptr_t)logits | (uintptr_t)loss | (uintptr_t)lse | (uintptr_t)count) & 3) || ((uintptr_t)targets & 7))
+    return fail(SMX_ERR_INVALID, "logits, loss, lse, count must be 4-byte aligned and targets 8-byte aligned");
+  if (int rc = need_ws(workspace, workspace_bytes, xent_need(R), "smx_xent_workspace_bytes")) return rc;
+  HIP_TRY(launch_xent_fwd(logits, row_stride, targets, ignore_index, reduction, loss, lse, count,
+                          (float*)((char*)workspace + SYNC_BYTES), R, V, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_xent_backward(const float* g, const float* logits, long long row_stride, const long long* targets,
+                      long long ignore_index, int reduction, const float* lse, const float* count, float* grad,
+                      long long R, int V, void* stream) {
+  if (int rc = xent_check_args("smx_xent_backward", R, V, row_stride, reduction)) return rc;
+  if (!g || !logits || !targets || !lse || !count || !grad)
+    return fail(SMX_ERR_INVALID, "g, logits, targets, lse, count, grad must be non-NULL");
+  if ((((uintptr_t)g | (uintptr_t)logits | (uintptr_t)lse | (uintptr_t)count | (uintptr_t)grad) & 3) ||
+      ((uintptr_t)targets & 7))
+    return fail(SMX_ERR_INVALID, "g, logits, lse, count, grad must be 4-byte aligned and targets 8-byte aligned");
+  if (grad == logits) return fail(SMX_ERR_INVALID, "grad must not alias logits");
+  HIP_TRY(launch_xent_bwd(g, logits, row_stride, targets, ignore_index, reduction, lse, count, grad, R, V,
+                          (hipStream_t)stream));
+  return SMX_OK;
+}
+
 // ---- overlap-save chunk generation (smx_stream.hip) -----------------------------------------------------------------------
 static int stream_check(const char* fn, int Bt, int T, int K, int C, int chunk, std::initializer_list<const void*> ptrs) {
   if (Bt < 1 || Bt > (1 << 24)) return fail(SMX_ERR_INVALID, "%s: Bt must be in 1..2^24, got %d", fn, Bt);

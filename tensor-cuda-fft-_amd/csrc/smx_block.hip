@@ -12,7 +12,11 @@
 //   * k_ln_colsum   fixed-order reduction of those partials (bitwise reproducible);
 //   * k_ln_apply, k_add_rows   unfused fallback used with the split / direct transform paths;
 //   * k_head_fwd, k_head_bwd   the 1- or 2-neuron head of fft_lm's word-structure models over all B T rows: the same row
-//                   walk, its parameter-gradient partials in the slab layout k_ln_colsum reduces.
+//                   walk, its parameter-gradient partials in the slab layout k_ln_colsum reduces;
+//   * k_xent_fwd, k_xent_bwd   softmax cross-entropy over rows of logits of a LayerNorm row width, the same row walk;
+//     k_xent_fwd_stream, k_xent_bwd_stream   the same for any wider row (the 50257-way token loss of fft_lm's dual head):
+//                   one workgroup per row, a running (max, sum) per thread; k_xent_finish adds the per-block (sum, count)
+//                   partials of either in a fixed order.
 // One wavefront per row, lane l holds elements (l + 64 c) VEC + [0, VEC), c < CH, in registers:
 // every global access is a full-wave contiguous segment and a row is read exactly once.
 // Vec, wave_sum, the LayerNorm-backward accumulation, the (VEC, CH) dispatch and the launch geometry
@@ -480,6 +484,346 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void k_head_bwd(const float* __rest
   }
 }
 
+// ---- softmax cross-entropy (reference fft_lm/dual_head.py:176-188) ----------------------------------------------------
+// Bound by the read of the logits (forward) and by that read plus the write of the gradient (backward).  A row's
+// target is uniform over the wavefront resp. workgroup that owns the row, so the test for an ignored row skips the row's
+// loads without divergence.  Exponentials are __expf of an argument <= 0 (relative error about 1e-7 |arg|).
+constexpr float XENT_NINF = -__builtin_huge_valf();
+
+// Maximum over the 64 lanes, returned in every lane: wave_sum's DPP steps, a lane without a source keeping its own value
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_keep(float v) {
+  const int w = __builtin_bit_cast(int, v);
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(w, w, CTRL, ROW_MASK, 0xf, false));
+}
+__device__ __forceinline__ float wave_max(float v) {
+  v = fmaxf(v, dpp_keep<0x111, 0xf>(v));
+  v = fmaxf(v, dpp_keep<0x112, 0xf>(v));
+  v = fmaxf(v, dpp_keep<0x114, 0xf>(v));
+  v = fmaxf(v, dpp_keep<0x118, 0xf>(v));      // lane 15 of each row holds the row maximum
+  v = fmaxf(v, dpp_keep<0x142, 0xa>(v));
+  v = fmaxf(v, dpp_keep<0x143, 0xc>(v));      // lane 63 holds the maximum
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
+// The reference point of a (max, sum) pair: the maximum, or 0 while everything seen is -inf, so that no exponent is
+// ever formed as -inf - -inf.  exp(m - xent_ref(M)) rescales a sum kept relative to m <= M (0 for m = -inf).
+__device__ __forceinline__ float xent_ref(float m) { return m == XENT_NINF ? 0.f : m; }
+
+// One element of the gradient from the row's (m, d) = (max, log sum exp(x - max)): the pair is kept apart because
+// m + d rounded to one float loses d beside a large |m|, and exp(x - lse) would then be 1 where it is 1 / n.
+__device__ __forceinline__ float xent_grad(float v, float m, float d, float sc, bool hit) {
+  return (__expf((v - m) - d) - (hit ? 1.f : 0.f)) * sc;
+}
+
+// s_r of the backward; NaN for a target outside [0, V)
+__device__ __forceinline__ float xent_scale(const float* g, const float* count, long long row, int reduction, bool in_range) {
+  if (!in_range) return __builtin_nanf("");
+  return reduction == XENT_NONE ? g[row] : reduction == XENT_MEAN ? g[0] / count[0] : g[0];
+}
+
+// One (sum, count) pair per block from the per-wave pairs, waves added in index order.
+__device__ __forceinline__ void xent_block_partial(float sum, float cnt, float* part, float (*red)[2], int lane, int wv,
+                                                   int waves) {
+  if (lane == 0) { red[wv][0] = sum; red[wv][1] = cnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float a0 = 0.f, a1 = 0.f;
+    for (int w2 = 0; w2 < waves; ++w2) { a0 += red[w2][0]; a1 += red[w2][1]; }
+    part[(size_t)blockIdx.x * 2] = a0;
+    part[(size_t)blockIdx.x * 2 + 1] = a1;
+  }
+}
+
+// Register rows: one wavefront per row, the row in Vec<VEC>[CH], the padding at -inf.
+template <int VEC, int CH>
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_xent_fwd(const float* __restrict__ x, long long stride,
+                                                             const long long* __restrict__ tg, long long ignore,
+                                                             float* __restrict__ loss_rows, float* __restrict__ lse,
+                                                             float* __restrict__ part, long long rows, int V) {
+  __shared__ float red[ROW_WAVES][2];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  float acc = 0.f, cnt = 0.f;
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows; row += (long long)gridDim.x * ROW_WAVES) {
+    const long long t = tg[row];
+    if (t == ignore) {
+      if (lane == 0) {
+        lse[2 * row] = lse[2 * row + 1] = 0.f;
+        if (loss_rows) loss_rows[row] = 0.f;
+      }
+      continue;
+    }
+    const float* p = x + row * stride;
+    Vec<VEC> xv[CH];
+    float m = XENT_NINF;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int e = (lane + 64 * c) * VEC;
+      if (e < V) xv[c].load(p + e);
+      else
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) xv[c].v[i] = XENT_NINF;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) m = fmaxf(m, xv[c].v[i]);
+    }
+    m = wave_max(m);
+    const float ref = xent_ref(m);
+    float s = 0.f, xt = 0.f;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int e = (lane + 64 * c) * VEC;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        s += __expf(xv[c].v[i] - ref);
+        if ((long long)(e + i) == t) xt = xv[c].v[i];
+      }
+    }
+    s = wave_sum(s);
+    xt = wave_sum(xt);                         // one lane holds the target's logit, the others 0
+    const float d = logf(s);
+    const float lr = (t >= 0 && t < V) ? d - (xt - m) : __builtin_nanf("");
+    acc += lr;
+    cnt += 1.f;
+    if (lane == 0) {
+      lse[2 * row] = m;
+      lse[2 * row + 1] = d;
+      if (loss_rows) loss_rows[row] = lr;
+    }
+  }
+  xent_block_partial(acc, cnt, part, red, lane, wv, ROW_WAVES);
+}
+
+template <int VEC, int CH>
+__global__ __launch_bounds__(64 * ROW_WAVES) void k_xent_bwd(const float* __restrict__ g, const float* __restrict__ x,
+                                                             long long stride, const long long* __restrict__ tg,
+                                                             long long ignore, int reduction,
+                                                             const float* __restrict__ lse, const float* __restrict__ count,
+                                                             float* __restrict__ grad, long long rows, int V) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (long long row = (long long)blockIdx.x * ROW_WAVES + wv; row < rows; row += (long long)gridDim.x * ROW_WAVES) {
+    const long long t = tg[row];
+    const bool live = t != ignore;
+    const float* p = x + row * stride;
+    float* q = grad + row * (long long)V;
+    float m = 0.f, d = 0.f, sc = 0.f;
+    if (live) {
+      m = lse[2 * row];
+      d = lse[2 * row + 1];
+      sc = xent_scale(g, count, row, reduction, t >= 0 && t < V);
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int e = (lane + 64 * c) * VEC;
+      if (e < V) {
+        Vec<VEC> v;
+        if (live) {
+          v.load(p + e);
+#pragma unroll
+          for (int i = 0; i < VEC; ++i)
+            v.v[i] = xent_grad(v.v[i], m, d, sc, (long long)(e + i) == t);
+        } else {
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) v.v[i] = 0.f;
+        }
+        v.store(q + e);
+      }
+    }
+  }
+}
+
+// Streaming rows: one workgroup per row, workgroups walking the rows.  A row starts at any 4-byte address: elements
+// [0, head) up to the first 16-byte boundary one per thread, then nvec 16-byte chunks, thread i taking chunks i, i + 256,
+// ..., then the last V - head - 4 nvec < 4 elements one per thread.
+struct XentSpan {
+  int head, nvec, tail0;                      // tail0: index of the first tail element
+};
+__device__ __forceinline__ XentSpan xent_span(const float* p, int V) {
+  XentSpan sp;
+  const int to_align = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2;
+  sp.head = to_align < V ? to_align : V;
+  sp.nvec = (V - sp.head) >> 2;
+  sp.tail0 = sp.head + 4 * sp.nvec;
+  return sp;
+}
+
+// (m, s) += one element / one chunk: s stays relative to xent_ref(m)
+__device__ __forceinline__ void xent_add(float& m, float& s, float v) {
+  const float mn = fmaxf(m, v);
+  const float ref = xent_ref(mn);
+  s = s * __expf(m - ref) + __expf(v - ref);
+  m = mn;
+}
+__device__ __forceinline__ void xent_add4(float& m, float& s, const f32x4 w) {
+  const float mn = fmaxf(fmaxf(m, fmaxf(w.x, w.y)), fmaxf(w.z, w.w));
+  const float ref = xent_ref(mn);
+  s = s * __expf(m - ref) + ((__expf(w.x - ref) + __expf(w.y - ref)) + (__expf(w.z - ref) + __expf(w.w - ref)));
+  m = mn;
+}
+__device__ __forceinline__ float xent_pick(const f32x4 w, int j, long long t, float xt) {
+  const long long d = t - j;
+  return d == 0 ? w.x : d == 1 ? w.y : d == 2 ? w.z : d == 3 ? w.w : xt;
+}
+
+__global__ __launch_bounds__(XENT_BLOCK) void k_xent_fwd_stream(const float* __restrict__ x, long long stride,
+                                                                const long long* __restrict__ tg, long long ignore,
+                                                                float* __restrict__ loss_rows, float* __restrict__ lse,
+                                                                float* __restrict__ part, long long rows, int V) {
+  constexpr int WAVES = XENT_BLOCK / 64;
+  __shared__ float red[WAVES][3];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float acc = 0.f, cnt = 0.f;                 // thread 0's are the block's
+  for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
+    const long long t = tg[row];
+    if (t == ignore) {
+      if (tid == 0) {
+        lse[2 * row] = lse[2 * row + 1] = 0.f;
+        if (loss_rows) loss_rows[row] = 0.f;
+      }
+      continue;
+    }
+    const float* p = x + row * stride;
+    const XentSpan sp = xent_span(p, V);
+    float m = XENT_NINF, s = 0.f, xt = 0.f;
+    if (tid < sp.head) {
+      const float v = __builtin_nontemporal_load(p + tid);
+      xent_add(m, s, v);
+      if (tid == t) xt = v;
+    }
+    const f32x4* pv = reinterpret_cast<const f32x4*>(p + sp.head);
+    int i = tid;
+    for (; i + 3 * XENT_BLOCK < sp.nvec; i += 4 * XENT_BLOCK) {      // four chunks in flight
+      f32x4 w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) w[u] = __builtin_nontemporal_load(pv + i + u * XENT_BLOCK);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        xent_add4(m, s, w[u]);
+        xt = xent_pick(w[u], sp.head + 4 * (i + u * XENT_BLOCK), t, xt);
+      }
+    }
+    for (; i < sp.nvec; i += XENT_BLOCK) {
+      const f32x4 w = __builtin_nontemporal_load(pv + i);
+      xent_add4(m, s, w);
+      xt = xent_pick(w, sp.head + 4 * i, t, xt);
+    }
+    if (tid < V - sp.tail0) {
+      const float v = __builtin_nontemporal_load(p + sp.tail0 + tid);
+      xent_add(m, s, v);
+      if (sp.tail0 + tid == t) xt = v;
+    }
+    // threads -> wave -> workgroup, each step relative to the wider maximum, waves in index order
+    const float mw = wave_max(m);
+    const float sw = wave_sum(s * __expf(m - xent_ref(mw)));
+    const float xw = wave_sum(xt);
+    __syncthreads();                          // the previous row's reads of red are done
+    if (lane == 0) { red[wv][0] = mw; red[wv][1] = sw; red[wv][2] = xw; }
+    __syncthreads();
+    float mb = red[0][0];
+#pragma unroll
+    for (int w2 = 1; w2 < WAVES; ++w2) mb = fmaxf(mb, red[w2][0]);
+    const float ref = xent_ref(mb);
+    float sb = 0.f, xb = 0.f;
+#pragma unroll
+    for (int w2 = 0; w2 < WAVES; ++w2) {
+      sb += red[w2][1] * __expf(red[w2][0] - ref);
+      xb += red[w2][2];
+    }
+    const float d = logf(sb);
+    const float lr = (t >= 0 && t < V) ? d - (xb - mb) : __builtin_nanf("");
+    acc += lr;
+    cnt += 1.f;
+    if (tid == 0) {
+      lse[2 * row] = mb;
+      lse[2 * row + 1] = d;
+      if (loss_rows) loss_rows[row] = lr;
+    }
+  }
+  if (tid == 0) {
+    part[(size_t)blockIdx.x * 2] = acc;
+    part[(size_t)blockIdx.x * 2 + 1] = cnt;
+  }
+}
+
+// The gradient row is dense, so its 16-byte boundaries need not be the logits row's: the span is the gradient row's
+// (every store aligned), and the logits are read as 16-byte chunks only where the two rows are co-aligned.
+__global__ __launch_bounds__(XENT_BLOCK) void k_xent_bwd_stream(const float* __restrict__ g, const float* __restrict__ x,
+                                                                long long stride, const long long* __restrict__ tg,
+                                                                long long ignore, int reduction,
+                                                                const float* __restrict__ lse,
+                                                                const float* __restrict__ count, float* __restrict__ grad,
+                                                                long long rows, int V) {
+  const int tid = threadIdx.x;
+  for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
+    const long long t = tg[row];
+    const bool live = t != ignore;
+    const float* p = x + row * stride;
+    float* q = grad + row * (long long)V;
+    const XentSpan sp = xent_span(q, V);
+    const bool co = (((uintptr_t)p ^ (uintptr_t)q) & 15u) == 0;
+    float m = 0.f, d = 0.f, sc = 0.f;
+    if (live) {
+      m = lse[2 * row];
+      d = lse[2 * row + 1];
+      sc = xent_scale(g, count, row, reduction, t >= 0 && t < V);
+    }
+    if (tid < sp.head)
+      __builtin_nontemporal_store(live ? xent_grad(__builtin_nontemporal_load(p + tid), m, d, sc, tid == t) : 0.f, q + tid);
+    f32x4* qv = reinterpret_cast<f32x4*>(q + sp.head);
+    for (int i = tid; i < sp.nvec; i += XENT_BLOCK) {
+      const int j = sp.head + 4 * i;
+      f32x4 w;
+      if (!live) {
+        w.x = w.y = w.z = w.w = 0.f;
+      } else {
+        if (co) {
+          w = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + j));
+        } else {
+          w.x = __builtin_nontemporal_load(p + j);
+          w.y = __builtin_nontemporal_load(p + j + 1);
+          w.z = __builtin_nontemporal_load(p + j + 2);
+          w.w = __builtin_nontemporal_load(p + j + 3);
+        }
+        const long long dt = t - j;
+        w.x = xent_grad(w.x, m, d, sc, dt == 0);
+        w.y = xent_grad(w.y, m, d, sc, dt == 1);
+        w.z = xent_grad(w.z, m, d, sc, dt == 2);
+        w.w = xent_grad(w.w, m, d, sc, dt == 3);
+      }
+      __builtin_nontemporal_store(w, qv + i);
+    }
+    if (tid < V - sp.tail0) {
+      const int j = sp.tail0 + tid;
+      __builtin_nontemporal_store(live ? xent_grad(__builtin_nontemporal_load(p + j), m, d, sc, j == t) : 0.f, q + j);
+    }
+  }
+}
+
+// loss[0] = sum of the partial sums (/ the count for the mean), count[0] = sum of the partial counts: thread i adds
+// partials [i per, (i + 1) per) in order, the wave sum adds the threads, thread 0 the waves: one fixed order.
+__global__ __launch_bounds__(XENT_BLOCK) void k_xent_finish(const float* __restrict__ part, int nblk, int reduction,
+                                                            float* __restrict__ loss, float* __restrict__ count) {
+  __shared__ float red[XENT_BLOCK / 64][2];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int per = (nblk + XENT_BLOCK - 1) / XENT_BLOCK;
+  float a0 = 0.f, a1 = 0.f;
+  for (int b = tid * per; b < nblk && b < (tid + 1) * per; ++b) {
+    a0 += part[2 * (size_t)b];
+    a1 += part[2 * (size_t)b + 1];
+  }
+  a0 = wave_sum(a0);
+  a1 = wave_sum(a1);
+  if (lane == 0) { red[wv][0] = a0; red[wv][1] = a1; }
+  __syncthreads();
+  if (tid == 0) {
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+    for (int w2 = 0; w2 < XENT_BLOCK / 64; ++w2) { s0 += red[w2][0]; s1 += red[w2][1]; }
+    count[0] = s1;
+    if (reduction == XENT_MEAN) loss[0] = s0 / s1;
+    else if (reduction == XENT_SUM) loss[0] = s0;
+  }
+}
+
 }  // namespace
 
 int ln_num_blocks(long long rows) {
@@ -609,6 +953,56 @@ hipError_t launch_head_bwd(const float* g, const float* h, const float* w, float
   const int nblk = ln_num_blocks(R);
   if (hipError_t e = launch_ln_colsum(pw, nblk, C, grad_w, grad_w && O == 2 ? grad_w + C : nullptr, s)) return e;
   return launch_ln_colsum(pb, nblk, 1, grad_b, grad_b && O == 2 ? grad_b + 1 : nullptr, s);
+}
+
+// ---- softmax cross-entropy ---------------------------------------------------------------------------------------------
+int xent_num_blocks(long long R) { return (int)(R < 1 ? 1 : R > LN_MAX_BLOCKS ? LN_MAX_BLOCKS : R); }
+
+namespace {
+
+// The kernel family of a call: f(VEC, CH) for register rows -- Vec<4> chunks only where every row of logits and grad
+// (null in the forward) starts on a 16-byte boundary, else the one-element-per-lane instances while they reach V --
+// and false for the streaming rows.
+template <typename Fn>
+bool xent_dispatch(int V, const float* logits, long long row_stride, const float* grad, Fn f) {
+  const bool rows16 = (((uintptr_t)logits | (uintptr_t)grad) & 15) == 0 && row_stride % 4 == 0;
+  if (V % 4 == 0 && V <= LN_MAX_D && rows16) return row_dispatch<4, 16>(V, f);
+  if (V <= LN_MAX_D_ODD) return row_dispatch<1, 16, 4>(V, f);
+  return false;
+}
+
+}  // namespace
+
+hipError_t launch_xent_fwd(const float* logits, long long row_stride, const long long* targets, long long ignore_index,
+                           int reduction, float* loss, float* lse, float* count, float* part, long long R, int V,
+                           hipStream_t s) {
+  float* loss_rows = reduction == XENT_NONE ? loss : nullptr;
+  int nblk = ln_num_blocks(R);
+  const bool reg = xent_dispatch(V, logits, row_stride, nullptr, [&](auto vec, auto ch) {
+    row_launch(k_xent_fwd<decltype(vec)::value, decltype(ch)::value>, R, s, logits, row_stride, targets, ignore_index,
+               loss_rows, lse, part, R, V);
+  });
+  if (!reg) {
+    nblk = xent_num_blocks(R);
+    hipLaunchKernelGGL(k_xent_fwd_stream, dim3(nblk), dim3(XENT_BLOCK), 0, s, logits, row_stride, targets, ignore_index,
+                       loss_rows, lse, part, R, V);
+  }
+  if (hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL(k_xent_finish, dim3(1), dim3(XENT_BLOCK), 0, s, (const float*)part, nblk, reduction, loss, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_xent_bwd(const float* g, const float* logits, long long row_stride, const long long* targets,
+                           long long ignore_index, int reduction, const float* lse, const float* count, float* grad,
+                           long long R, int V, hipStream_t s) {
+  const bool reg = xent_dispatch(V, logits, row_stride, grad, [&](auto vec, auto ch) {
+    row_launch(k_xent_bwd<decltype(vec)::value, decltype(ch)::value>, R, s, g, logits, row_stride, targets, ignore_index,
+               reduction, lse, count, grad, R, V);
+  });
+  if (!reg)
+    hipLaunchKernelGGL(k_xent_bwd_stream, dim3(xent_num_blocks(R)), dim3(XENT_BLOCK), 0, s, g, logits, row_stride, targets,
+                       ignore_index, reduction, lse, count, grad, R, V);
+  return hipGetLastError();
 }
 
 }  // namespace smx

@@ -327,6 +327,23 @@ hipError_t launch_head_fwd(const float* h, const float* w, const float* b, float
                            hipStream_t s);
 hipError_t launch_head_bwd(const float* g, const float* h, const float* w, float* grad_h, float* grad_w, float* grad_b,
                            float* part_w, float* part_b, long long R, int C, int O, hipStream_t s);
+// Softmax cross-entropy over R rows of V fp32 logits, rows row_stride elements apart, int64 targets (reference
+// fft_lm/dual_head.py:176-188).  Forward: lse[r] = (m, d) = (max_j x[r, j], log sum_j exp(x[r, j] - m)), a pair of floats
+// whose sum is the row's log-sum-exp, the row loss d - (x[r, t_r] - m) (into loss_rows when reduction is XENT_NONE), one (sum, count) partial per block in part (xent_num_blocks(R) pairs), then one
+// workgroup adds the partials in index order into loss[0] (mean / sum) and count[0].  Backward: grad (R, V) dense =
+// (exp((x - m) - d) - [j == t]) s_r, s_r from g and count in device memory.  A row whose target is ignore_index is not read:
+// its loss, lse and gradient row are zeros.  A target outside [0, V) makes its row's loss and gradient NaN.
+// Register rows (one wavefront a row) for ln_supported(V), as Vec<4> only where logits, grad and row_stride keep every
+// row 16-byte aligned; streaming rows (one workgroup a row, any alignment) for every other V.
+constexpr int XENT_MEAN = 0, XENT_SUM = 1, XENT_NONE = 2;
+constexpr int XENT_BLOCK = 256;          // threads of a streaming row's workgroup and of the finishing workgroup
+int xent_num_blocks(long long R);        // most (sum, count) partials either family writes for R rows
+hipError_t launch_xent_fwd(const float* logits, long long row_stride, const long long* targets, long long ignore_index,
+                           int reduction, float* loss, float* lse, float* count, float* part, long long R, int V,
+                           hipStream_t s);
+hipError_t launch_xent_bwd(const float* g, const float* logits, long long row_stride, const long long* targets,
+                           long long ignore_index, int reduction, const float* lse, const float* count, float* grad,
+                           long long R, int V, hipStream_t s);
 
 // ---- row kernels of EnhancedSpectralBlock (smx_enh.hip) --------------------------------------------
 constexpr int ENH_MAX_D = 1024;          // widest row (even) held in one wavefront's registers; the gate row is 2D

@@ -1957,3 +1957,84 @@ def narrow_head(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
         return torch.nn.functional.linear(h, weight, bias)
     y = _NarrowHead.apply(_dense(h.reshape(-1, C)), _dense(weight), _dense(bias))
     return y.view(*h.shape[:-1], O)
+
+
+# ---- softmax cross-entropy: the losses of the dual head (csrc/smx_block.hip, k_xent_*) ------------------------------------
+
+_XENT_REDUCTION = {"mean": 0, "sum": 1, "none": 2}
+
+
+@functools.lru_cache(None)
+def _xent_ws_bytes(R: int, V: int) -> int:
+    """smx_xent_workspace_bytes: a function of the shape alone, remembered per shape (one host call less per step)."""
+    return _query("smx_xent_workspace_bytes", R, V)
+
+
+def _xent_rows(logits: torch.Tensor):
+    """(rows, row_stride): `logits` (..., V) as (R, V) rows the kernels read in place -- a view whose last dimension is
+    contiguous and whose rows share one stride of at least V elements -- and a dense copy of anything else."""
+    V = logits.shape[-1]
+    x = logits.reshape(-1, V)               # a view where the leading dimensions share one stride, a dense copy otherwise
+    if (V > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < V) or x.data_ptr() % 4:
+        x = x.contiguous()
+    return x, (x.stride(0) if x.shape[0] > 1 else V)
+
+
+class _CrossEntropy(torch.autograd.Function):
+    """Softmax cross-entropy of (R, V) fp32 rows with int64 targets through smx_xent_forward / _backward: the logits are
+    read once per direction, lse (R, 2) -- the pair (row maximum, log-sum-exp relative to it) -- and the count of live rows
+    stay on the device, the upstream gradient is read there."""
+
+    @staticmethod
+    def forward(ctx, x, row_stride, targets, ignore_index, reduction):
+        R, V = x.shape
+        n_loss = R if reduction == 2 else 1
+        buf = torch.empty(2 * R + 1 + n_loss, dtype=torch.float32, device=x.device)  # lse (R, 2) | count | loss
+        ws = _workspace(x.device, _xent_ws_bytes(R, V))
+        _call(x.device, "smx_xent_forward", x.data_ptr(), row_stride, targets.data_ptr(), ignore_index, reduction,
+              buf.data_ptr() + 4 * (2 * R + 1), buf.data_ptr(), buf.data_ptr() + 8 * R, *_ws_arg(ws), R, V, _stream(x.device))
+        ctx.meta = (row_stride, ignore_index, reduction)
+        ctx.save_for_backward(x, targets, buf)
+        return buf[2 * R + 1:] if reduction == 2 else buf[2 * R + 1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        x, targets, buf = ctx.saved_tensors
+        row_stride, ignore_index, reduction = ctx.meta
+        R, V = x.shape
+        g = _grad_f32(g)
+        grad = torch.empty((R, V), dtype=torch.float32, device=x.device)
+        _call(x.device, "smx_xent_backward", g.data_ptr(), x.data_ptr(), row_stride, targets.data_ptr(), ignore_index,
+              reduction, buf.data_ptr(), buf.data_ptr() + 8 * R, grad.data_ptr(), R, V, _stream(x.device))
+        return grad, None, None, None, None
+
+
+def cross_entropy(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100,
+                  reduction: str = "mean") -> torch.Tensor:
+    """nn.functional.cross_entropy over the LAST dimension: logits (..., V), class-index targets (...); reduction "mean",
+    "sum" or "none" (then of the targets' shape, an ignored position at 0).  Native -- each logit read once forward and
+    once backward, no host synchronisation, bitwise reproducible -- when the logits are fp32 on a ROCm device, the targets
+    int64 on the same device, autocast is off and numel() > 0; F.cross_entropy everywhere else (CPU, bf16 / fp16, under
+    torch.autocast, other target dtypes).  A view whose last dimension is contiguous and whose rows share one stride is
+    read in place; anything else is made dense first.
+    Difference from torch on the native path: a target outside [0, V) that is not `ignore_index` does not raise a
+    device-side assert; that row's loss and its gradient row are NaN (the row counts towards the mean)."""
+    if reduction not in _XENT_REDUCTION:
+        raise ValueError(f"cross_entropy: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+    if logits.dim() < 1 or tuple(targets.shape) != tuple(logits.shape[:-1]):
+        raise ValueError(f"cross_entropy: logits {tuple(logits.shape)} need targets of shape {tuple(logits.shape[:-1])}, "
+                         f"got {tuple(targets.shape)}")
+    V = logits.shape[-1]
+    native = (logits.is_cuda and logits.dtype == torch.float32 and targets.dtype == torch.int64
+              and targets.device == logits.device and logits.numel() > 0 and not torch.is_autocast_enabled())
+    if not native:
+        out = torch.nn.functional.cross_entropy(logits.reshape(-1, V), targets.reshape(-1), ignore_index=ignore_index,
+                                                reduction=reduction)
+        return out.view(targets.shape) if reduction == "none" else out
+    x, row_stride = _xent_rows(logits)
+    out = _CrossEntropy.apply(x, row_stride, targets.reshape(-1).contiguous(), int(ignore_index),
+                              _XENT_REDUCTION[reduction])
+    return out.view(targets.shape) if reduction == "none" else out
