@@ -722,6 +722,40 @@ int smx_stream_conv(const float* h, const float* ring, const int* pos, const flo
                     const float* ln_w, const float* ln_b, float eps, float* h_out, float* ff_in, int Bt, int T, int K,
                     int C, int chunk, void* stream);
 
+/* The byte sampler of generation: one launch for the penalties, bans, temperature, nucleus, top-k and the draw that the
+ * reference spreads over Python loops and about a dozen small ops with several host synchronisations per byte --
+ * fft_lm/train_fixed_full.py:651-701 (generate), scripts/stream_generate_fast.py:146-170 (sample_next),
+ * scripts/generate_chunked_overlap_save.py:39-48 and :283-292 and its siblings.  They are one function of a row of 256
+ * logits; per row r of R, in this order (the reference's results depend on it):
+ *    1  l = logits[r, :]                                     float32, rows row_stride >= 256 elements apart
+ *    2  for every byte b present in recent:  l[b] /= repetition_penalty      (a plain division, for negative logits too)
+ *    3  if presence_penalty or frequency_penalty is not 0:  l[b] -= presence_penalty + frequency_penalty * count[b]
+ *    4  ascii_only: everything but 10 and 32..126 becomes -inf;  ban_cr: 13 becomes -inf
+ *    5  max_run_length > 0, n_recent >= max_run_length and the last max_run_length ids of recent all equal: that byte
+ *       becomes -inf
+ *    6  l /= temperature
+ *    7  top_p < 1: in descending order of l (equal logits by index), the longest prefix whose running softmax sum stays
+ *       <= top_p is kept, at least one entry; the rest becomes -inf.  top_p >= 1: no such step.
+ *    8  top_k > 0: with v the min(top_k, 256)-th largest remaining value, every l < v becomes -inf
+ *    9  p = softmax(l)
+ *   10  ids[r] = the first j, in index order, with sum_{i <= j} p_i > u[r]
+ *   recent: n_recent ids shared by all rows of the call, uint8 or int64 (token_bytes 1 or 8, as smx_word_targets; an
+ *   int64 id outside 0..255 counts for no byte), 0 <= n_recent <= 65536; u (R) float32 uniforms in [0, 1); ids (R)
+ *   int64; probs (R, 256) float32 dense, or NULL: the distribution of step 9.
+ *   Guarantees: p[ids[r]] > 0 always -- where rounding leaves u above the last running sum, the last byte with p > 0 is
+ *   taken; a NaN logit gives an unspecified id in [0, 255] and no fault.  One workgroup of 256 threads per row, every sum
+ *   a block scan in a fixed order: bitwise reproducible, and a row's result does not depend on the other rows.  No
+ *   atomics on global memory, no flags.
+ * smx_sample_supported(V) = (V == 256); any other V: SMX_ERR_UNSUPPORTED.  R <= 0, NULL logits / u / ids (recent with
+ * n_recent > 0), row_stride < 256, token_bytes other than 1 or 8, n_recent outside [0, 65536], misaligned pointers,
+ * temperature or repetition_penalty not positive and finite, a NaN top_p, non-finite penalties, negative top_k or
+ * max_run_length: SMX_ERR_INVALID.  Nothing is enqueued then, nothing is ever allocated, the host is never synchronised. */
+int smx_sample_supported(int V);
+int smx_sample_bytes(const float* logits, long long row_stride, const void* recent, int token_bytes, int n_recent,
+                     float temperature, float top_p, int top_k, float repetition_penalty, float presence_penalty,
+                     float frequency_penalty, int ascii_only, int ban_cr, int max_run_length, const float* u,
+                     long long* ids, float* probs, long long R, int V, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,12 +9,13 @@ from .wirtinger_ops import (ComplexParameter, WirtingerGradient, WirtingerSpectr
                             spectral_mix_with_filter)
 from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft, rfft_bins, seq_fft,
                          spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens, narrow_head,
-                         word_targets, cross_entropy)
+                         word_targets, cross_entropy, sample_bytes)
 from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
 from .frequency_ops import FrequencyAttention
-from .fixed_spectral import FixedSpectralBlock, FixedSpectralLM, FrequencyConvFunc, LMConfig, causal_spectral_conv
+from .fixed_spectral import (FixedSpectralBlock, FixedSpectralLM, FrequencyConvFunc, LMConfig, SampleConfig,
+                             causal_spectral_conv, generate)
 from .frequency_native import BicameralBlock, FrequencyNativeBlock, PhaseShift, SpectralFFN, SpectralLayerNorm
 from .spectral_ssm import EMAConfig, SpectralEMA
 from .chunk_head import ChunkLM, vectorized_windows
@@ -39,5 +40,6 @@ __all__ = [
     "PhaseClockHead", "PhaseClockChunkLM", "generate_phase_targets", "compute_phase_clock_loss", "SegmentationHead",
     "SegmentedChunkLM", "get_word_boundaries", "compute_segmented_loss", "word_targets", "narrow_head",
     "DualHead", "TokenAwareChunkLM", "get_token_ids_fast", "compute_dual_loss", "get_gpt2_tokenizer", "cross_entropy",
+    "sample_bytes", "SampleConfig", "generate",
 ]
 __version__ = "0.2.0"

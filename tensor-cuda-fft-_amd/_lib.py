@@ -149,6 +149,9 @@ _SIGS = {
     "smx_stream_supported": (_I, [_I] * 4),
     "smx_stream_push": (_I, [_P] * 3 + [ctypes.c_float] + [_P] * 4 + [_I] * 4 + [_P]),
     "smx_stream_conv": (_I, [_P] * 7 + [ctypes.c_float] + [_P] * 2 + [_I] * 5 + [_P]),
+    "smx_sample_supported": (_I, [_I]),
+    "smx_sample_bytes": (_I, [_P, _LL, _P, _I, _I, ctypes.c_float, ctypes.c_float, _I] + [ctypes.c_float] * 3
+                         + [_I] * 3 + [_P] * 3 + [_LL, _I, _P]),
 }
 
 

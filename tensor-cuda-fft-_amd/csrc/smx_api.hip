@@ -2270,4 +2270,37 @@ int smx_stream_conv(const float* h, const float* ring, const int* pos, const flo
   return SMX_OK;
 }
 
+// ---- the byte sampler (smx_stream.hip) -------------------------------------------------------------------------------------
+int smx_sample_supported(int V) { return V == SAMPLE_V ? 1 : 0; }
+int smx_sample_bytes(const float* logits, long long row_stride, const void* recent, int token_bytes, int n_recent,
+                     float temperature, float top_p, int top_k, float repetition_penalty, float presence_penalty,
+                     float frequency_penalty, int ascii_only, int ban_cr, int max_run_length, const float* u,
+                     long long* ids, float* probs, long long R, int V, void* stream) {
+  if (R <= 0 || V <= 0) return fail(SMX_ERR_INVALID, "shape must be positive: R=%lld V=%d", R, V);
+  if (V != SAMPLE_V) return fail(SMX_ERR_UNSUPPORTED, "the sampler draws bytes: V must be %d, got %d", SAMPLE_V, V);
+  if (R >= (1ll << 31)) return fail(SMX_ERR_INVALID, "R too large");
+  if (!logits || !u || !ids) return fail(SMX_ERR_INVALID, "logits, u, ids must be non-NULL");
+  if (row_stride < V) return fail(SMX_ERR_INVALID, "row_stride must be at least V");
+  if (token_bytes != 1 && token_bytes != 8) return fail(SMX_ERR_INVALID, "token_bytes must be 1 (uint8) or 8 (int64)");
+  if (n_recent < 0 || n_recent > SAMPLE_MAX_RECENT)
+    return fail(SMX_ERR_INVALID, "n_recent must be in [0, %d], got %d", SAMPLE_MAX_RECENT, n_recent);
+  if (n_recent > 0 && !recent) return fail(SMX_ERR_INVALID, "recent must be non-NULL with n_recent > 0");
+  if (token_bytes == 8 && ((uintptr_t)recent & 7)) return fail(SMX_ERR_INVALID, "int64 recent ids must be 8-byte aligned");
+  if ((((uintptr_t)logits | (uintptr_t)u | (uintptr_t)probs) & 3) || ((uintptr_t)ids & 7))
+    return fail(SMX_ERR_INVALID, "logits, u, probs must be 4-byte aligned and ids 8-byte aligned");
+  if (!(temperature > 0.f) || !std::isfinite(temperature))
+    return fail(SMX_ERR_INVALID, "temperature must be positive and finite, got %g", (double)temperature);
+  if (!(repetition_penalty > 0.f) || !std::isfinite(repetition_penalty))
+    return fail(SMX_ERR_INVALID, "repetition_penalty must be positive and finite, got %g", (double)repetition_penalty);
+  if (std::isnan(top_p)) return fail(SMX_ERR_INVALID, "top_p is NaN");
+  if (!std::isfinite(presence_penalty) || !std::isfinite(frequency_penalty))
+    return fail(SMX_ERR_INVALID, "presence_penalty and frequency_penalty must be finite");
+  if (top_k < 0 || max_run_length < 0) return fail(SMX_ERR_INVALID, "top_k and max_run_length must not be negative");
+  const SampleArgs a{temperature, top_p, repetition_penalty, presence_penalty, frequency_penalty,
+                     top_k, ascii_only != 0, ban_cr != 0, max_run_length};
+  HIP_TRY(launch_sample_bytes(logits, row_stride, recent, token_bytes == 1 ? 1 : 2, n_recent, a, u, ids, probs, R,
+                              (hipStream_t)stream));
+  return SMX_OK;
+}
+
 }  // extern "C"

@@ -386,4 +386,17 @@ hipError_t launch_stream_conv(const float* h, const float* ring, const int* pos,
                               const float* ln_w, const float* ln_b, float eps, float* h_out, float* ff_in, int Bt, int T,
                               int K, int C, int chunk, hipStream_t s);
 
+// ---- the byte sampler of generation (smx_stream.hip, k_sample_bytes) ------------------------------------------
+constexpr int SAMPLE_V = 256;            // the vocabulary: one thread per byte
+constexpr int SAMPLE_MAX_RECENT = 65536;
+struct SampleArgs {
+  float temperature, top_p, rep, presence, frequency;
+  int top_k, ascii_only, ban_cr, max_run;
+};
+// ids[r] (and probs[r, :], nullable) of R rows of SAMPLE_V logits, row_stride floats apart; recent: n_recent ids shared
+// by the rows, kind 1 / 2 = uint8 / int64; u (R) uniforms in [0, 1).  One workgroup per row.
+hipError_t launch_sample_bytes(const float* logits, long long row_stride, const void* recent, int kind, int n_recent,
+                               const SampleArgs& a, const float* u, long long* ids, float* probs, long long R,
+                               hipStream_t s);
+
 }  // namespace smx

@@ -22,6 +22,8 @@
 //                   wavefront order through LDS, and wavefront r finishes row r: residual, scale = gain g_ctx, and the
 //                   FFN's LayerNorm.  The sums do not depend on R or on the batch size: bitwise reproducible.
 // One wavefront per row, lane l holding elements (l + 64 c) VEC + [0, VEC), c < CH (smx_rows.h).
+//
+// Also here, as the other launch of a generated chunk: k_sample_bytes, the byte sampler (at the end of the file).
 #include "smx_kernels.h"
 #include "smx_rows.h"
 
@@ -238,6 +240,168 @@ hipError_t launch_stream_conv(const float* h, const float* ring, const int* pos,
     else if (fits(2)) go(std::integral_constant<int, (2 * V * CHN <= STREAM_ACC_REGS ? 2 : 1)>());
     else go(std::integral_constant<int, 1>());
   });
+  return hipGetLastError();
+}
+
+// ---- the byte sampler: penalties over a recent window, bans, temperature, nucleus, top-k and the draw, one launch ----
+// (reference fft_lm/train_fixed_full.py:651-701, scripts/stream_generate_fast.py:146-170,
+// scripts/generate_chunked_overlap_save.py:39-48, 283-292: all one function of a 256-wide row, include/smx.h.)
+// One workgroup of SAMPLE_V threads per row, thread t owns logit t.  Every sum over the row is a block scan in a fixed
+// order -- a shuffle scan inside each wavefront, the wavefront totals added in wavefront order -- so a row's result
+// does not depend on the other rows of the call or on the run: bitwise reproducible.  The window counts are integer LDS
+// additions (exact in any order).  Nothing in global memory is written but ids[r] and probs[r, :].
+namespace {
+
+constexpr int SAMPLE_WAVES = SAMPLE_V / 64;
+
+struct SampleLds {
+  int cnt[SAMPLE_V];            // occurrences of every byte in the window
+  unsigned key[SAMPLE_V];       // the logits as unsigned keys of one total order (NaN included): the rank is a permutation
+  float srt[SAMPLE_V];          // exp(l - max) in descending order of l
+  float part[SAMPLE_WAVES];     // wavefront totals of the reduction / scan in flight
+  float pick;                   // the top_k-th largest value
+  int run, first, last;
+};
+
+// inclusive scan of v over the workgroup in thread order; *total = the sum of all (the same association for every
+// thread: the wavefront totals added in wavefront order)
+__device__ __forceinline__ float block_scan(float v, SampleLds& sm, float* total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const float o = __shfl_up(v, d, 64);
+    if (lane >= d) v += o;
+  }
+  __syncthreads();                               // the previous user of part[] is done
+  if (lane == 63) sm.part[wv] = v;
+  __syncthreads();
+  float before = 0.f, all = 0.f;
+#pragma unroll
+  for (int w = 0; w < SAMPLE_WAVES; ++w) {
+    if (w == wv) before = all;
+    all += sm.part[w];
+  }
+  *total = all;
+  return wv == 0 ? v : before + v;
+}
+
+__device__ __forceinline__ float block_max(float v, SampleLds& sm) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sm.part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float m = sm.part[0];
+#pragma unroll
+  for (int w = 1; w < SAMPLE_WAVES; ++w) m = fmaxf(m, sm.part[w]);
+  return m;
+}
+
+// descending order of the floats = descending order of these keys; -0 and +0 share a key (equal logits are ordered by
+// index), a NaN sorts above or below everything by its sign: whatever the row holds, the ranks are a permutation
+__device__ __forceinline__ unsigned order_key(float x) {
+  if (x == 0.f) return 0x80000000u;
+  const unsigned b = __float_as_uint(x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+template <typename TOK>
+__global__ __launch_bounds__(SAMPLE_V) void k_sample_bytes(const float* __restrict__ logits, long long row_stride,
+                                                           const TOK* __restrict__ recent, int n_recent, SampleArgs a,
+                                                           const float* __restrict__ u, long long* __restrict__ ids,
+                                                           float* __restrict__ probs) {
+  __shared__ SampleLds sm;
+  const int t = threadIdx.x;
+  const size_t r = blockIdx.x;
+  const float ninf = -__builtin_huge_valf();
+  float l = logits[r * (size_t)row_stride + t];                                          // step 1
+  sm.cnt[t] = 0;
+  if (t == 0) { sm.run = 1; sm.first = SAMPLE_V; sm.last = -1; sm.pick = ninf; }
+  __syncthreads();
+  for (int i = t; i < n_recent; i += SAMPLE_V) {
+    const long long b = (long long)recent[i];
+    if (b >= 0 && b < SAMPLE_V) atomicAdd(&sm.cnt[(int)b], 1);                           // (LDS, integers: exact)
+  }
+  const bool run_on = a.max_run > 0 && n_recent >= a.max_run;
+  long long run_byte = -1;
+  if (run_on) {
+    run_byte = (long long)recent[n_recent - 1];
+    for (int i = t; i < a.max_run; i += SAMPLE_V)
+      if ((long long)recent[n_recent - 1 - i] != run_byte) sm.run = 0;                   // (every writer stores the same 0)
+  }
+  __syncthreads();
+  const int c = sm.cnt[t];
+  if (c > 0) {
+    l = l / a.rep;                                                                       // step 2
+    if (a.presence != 0.f || a.frequency != 0.f) l = l - a.presence - a.frequency * (float)c;   // step 3
+  }
+  if (a.ascii_only && !(t == 10 || (t >= 32 && t <= 126))) l = ninf;                     // step 4
+  if (a.ban_cr && t == 13) l = ninf;
+  if (run_on && sm.run && run_byte == t) l = ninf;                                       // step 5
+  l = l / a.temperature;                                                                 // step 6
+  const bool nucleus = a.top_p < 1.f;
+  const int kk = a.top_k > SAMPLE_V ? SAMPLE_V : a.top_k;
+  if (nucleus || kk > 0) {
+    // the descending rank of l, ties by index: SAMPLE_V broadcast reads of the keys
+    const unsigned key = order_key(l);
+    sm.key[t] = key;
+    __syncthreads();
+    int rank = 0;
+#pragma unroll 8
+    for (int j = 0; j < SAMPLE_V; ++j) {
+      const unsigned kj = sm.key[j];
+      rank += (kj > key || (kj == key && j < t)) ? 1 : 0;
+    }
+    int kept = SAMPLE_V;
+    if (nucleus) {                                                                       // step 7
+      const float m = block_max(l, sm);
+      sm.srt[rank] = expf(l - m);
+      __syncthreads();
+      const float e = sm.srt[t];
+      float sum;
+      block_scan(e, sm, &sum);
+      float unused;
+      const float cdf = block_scan(e / sum, sm, &unused);                                // running sum of the sorted softmax
+      kept = __syncthreads_count(cdf <= a.top_p || t == 0);
+      if (rank >= kept) l = ninf;
+    }
+    if (kk > 0) {                                                                        // step 8
+      if (rank == kk - 1 && kk <= kept) sm.pick = l;      // (past the nucleus: -inf, which is below nothing)
+      __syncthreads();
+      if (l < sm.pick) l = ninf;
+    }
+  }
+  const float m = block_max(l, sm);                                                      // step 9
+  const float e = expf(l - m);
+  float sum;
+  block_scan(e, sm, &sum);
+  const float p = e / sum;
+  float unused;
+  const float cum = block_scan(p, sm, &unused);                                          // step 10
+  if (probs) probs[r * SAMPLE_V + t] = p;
+  // the first index whose running sum exceeds u, among the bytes that can be drawn at all; where rounding leaves u above
+  // the last running sum, the last such byte; a row without any (NaN logits): 0
+  if (p > 0.f) {
+    atomicMax(&sm.last, t);
+    if (cum > u[r]) atomicMin(&sm.first, t);
+  }
+  __syncthreads();
+  if (t == 0) ids[r] = sm.first < SAMPLE_V ? sm.first : (sm.last >= 0 ? sm.last : 0);
+}
+
+}  // namespace
+
+hipError_t launch_sample_bytes(const float* logits, long long row_stride, const void* recent, int kind, int n_recent,
+                               const SampleArgs& a, const float* u, long long* ids, float* probs, long long R,
+                               hipStream_t s) {
+  if (R < 1 || R > 0x7fffffffll || row_stride < SAMPLE_V || n_recent < 0 || n_recent > SAMPLE_MAX_RECENT)
+    return hipErrorInvalidValue;
+  if (kind == 1)
+    hipLaunchKernelGGL(k_sample_bytes<unsigned char>, dim3((unsigned)R), dim3(SAMPLE_V), 0, s, logits, row_stride,
+                       (const unsigned char*)recent, n_recent, a, u, ids, probs);
+  else
+    hipLaunchKernelGGL(k_sample_bytes<long long>, dim3((unsigned)R), dim3(SAMPLE_V), 0, s, logits, row_stride,
+                       (const long long*)recent, n_recent, a, u, ids, probs);
   return hipGetLastError();
 }
 

@@ -21,7 +21,8 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from .functional import _call, _stream, conv_response, conv_supported, hermitian_scale, rank_one_conv, spectral_filter
+from .functional import (_call, _stream, conv_response, conv_supported, hermitian_scale, rank_one_conv, sample_bytes,
+                         spectral_filter)
 
 
 def next_pow2(n: int) -> int:
@@ -275,3 +276,55 @@ class FixedSpectralLM(nn.Module):
         for blk in self.blocks:
             h = blk(h, cutoff=cutoff)
         return self.ln_f(h)
+
+
+@dataclass
+class SampleConfig:
+    """The generation fields of the reference's TrainConfig with its defaults (reference :65-78), and the seq_len
+    `generate` reads beside them."""
+    seq_len: int = 1024
+    temperature: float = 0.8
+    top_p: float = 0.9
+    top_k: int = 0
+    repetition_penalty: float = 1.25
+    repetition_window: int = 256
+    max_run_length: int = 6
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    ban_cr: bool = True
+    ascii_only: bool = True
+    max_new: int = 400
+
+
+@torch.no_grad()
+def generate(model: "FixedSpectralLM", prompt: str, cfg, *, cutoff: "int | None" = None, generator=None) -> str:
+    """The reference's byte-by-byte `generate` (reference :621-704) on the model's device: per emitted byte ONE model
+    forward over the last cfg.seq_len bytes of a device-resident context and ONE sampler call
+    (functional.sample_bytes: a single launch on a ROCm device) -- no logit and no id is read by the host inside the
+    loop, where the reference synchronises several times per byte; the text is decoded once at the end.  `cfg`: a
+    SampleConfig, the reference's TrainConfig or any object with SampleConfig's fields.  The uniforms come from
+    torch.rand on the device (`generator`, or the device's default one), one per byte.
+    Two limits the reference does not have: 1 <= repetition_window <= 65536 (a window of 0 there means the whole
+    text), and max_run_length <= repetition_window (the run is looked for inside the window)."""
+    model.eval()
+    ctx = list(prompt.encode("utf-8", errors="ignore")) or [32]
+    T, window, max_new = int(cfg.seq_len), int(cfg.repetition_window), int(cfg.max_new)
+    max_run = int(cfg.max_run_length or 0)
+    if not 1 <= window <= 65536:
+        raise ValueError(f"generate: repetition_window must be in 1..65536, got {window}")
+    if max_run > window:
+        raise ValueError(f"generate: max_run_length = {max_run} is longer than repetition_window = {window}")
+    dev = model.embed.weight.device
+    n0 = len(ctx)
+    buf = torch.empty(n0 + max(max_new, 0), dtype=torch.long, device=dev)
+    buf[:n0] = torch.tensor(ctx, dtype=torch.long, device=dev)
+    top_p = 1.0 if cfg.top_p is None else float(cfg.top_p)
+    for n in range(n0, n0 + max_new):
+        logits = model(buf[max(0, n - T):n].unsqueeze(0), cutoff=cutoff)[:, -1]
+        u = torch.rand(1, dtype=torch.float32, device=dev, generator=generator)
+        buf[n:n + 1] = sample_bytes(logits, buf[max(0, n - window):n], u, temperature=cfg.temperature, top_p=top_p,
+                                    top_k=int(cfg.top_k or 0), repetition_penalty=cfg.repetition_penalty,
+                                    presence_penalty=cfg.presence_penalty or 0.0,
+                                    frequency_penalty=cfg.frequency_penalty or 0.0, ascii_only=bool(cfg.ascii_only),
+                                    ban_cr=bool(cfg.ban_cr), max_run_length=max_run)
+    return bytes(buf.tolist()).decode("utf-8", errors="replace")

@@ -2038,3 +2038,110 @@ def cross_entropy(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int
     out = _CrossEntropy.apply(x, row_stride, targets.reshape(-1).contiguous(), int(ignore_index),
                               _XENT_REDUCTION[reduction])
     return out.view(targets.shape) if reduction == "none" else out
+
+
+# ---- the byte sampler of generation (csrc/smx_stream.hip, k_sample_bytes) ------------------------------------------------
+
+_SAMPLE_V = 256
+_SAMPLE_MAX_RECENT = 65536
+
+
+def _sample_bytes_torch(l: torch.Tensor, recent: torch.Tensor, u: torch.Tensor, a: dict):
+    """The ten steps of smx_sample_bytes (include/smx.h) on (R, 256) fp32 rows as whole-tensor ops on the rows' device:
+    what CPU logits and 2-byte logits run.  No host read of a tensor value."""
+    dev, ninf = l.device, float("-inf")
+    ar = torch.arange(_SAMPLE_V, device=dev)
+    r = recent.to(torch.int64)
+    ok = (r >= 0) & (r < _SAMPLE_V)
+    cnt = torch.zeros(_SAMPLE_V, dtype=torch.int64, device=dev).scatter_add_(0, r.clamp(0, _SAMPLE_V - 1), ok.to(torch.int64))
+    seen = (cnt > 0).unsqueeze(0)
+    l = torch.where(seen, l / a["rep"], l)
+    if a["presence"] != 0.0 or a["frequency"] != 0.0:
+        l = torch.where(seen, l - a["presence"] - a["frequency"] * cnt.to(torch.float32), l)
+    if a["ascii_only"]:
+        l = l.masked_fill(~((ar == 10) | ((ar >= 32) & (ar <= 126))), ninf)
+    if a["ban_cr"]:
+        l = l.masked_fill(ar == 13, ninf)
+    if a["max_run"] > 0 and r.numel() >= a["max_run"]:
+        tail = r[r.numel() - a["max_run"]:]
+        l = l.masked_fill(((tail == tail[-1]).all() & (ar == tail[-1])).unsqueeze(0), ninf)
+    l = l / a["temperature"]
+    if a["top_p"] < 1.0:
+        sl, si = torch.sort(l, dim=-1, descending=True, stable=True)
+        keep = torch.cumsum(torch.softmax(sl, dim=-1), dim=-1) <= a["top_p"]
+        keep[:, 0] = True
+        kept = ar.unsqueeze(0) < keep.sum(dim=-1, keepdim=True)
+        l = torch.full_like(l, ninf).scatter_(1, si, torch.where(kept, sl, torch.full_like(sl, ninf)))
+    if a["top_k"] > 0:
+        v = torch.topk(l, min(a["top_k"], _SAMPLE_V), dim=-1).values[:, -1:]
+        l = torch.where(l < v, torch.full_like(l, ninf), l)
+    p = torch.softmax(l, dim=-1)
+    live = p > 0
+    hit = (torch.cumsum(p, dim=-1) > u.unsqueeze(1)) & live
+    first = torch.where(hit, ar, _SAMPLE_V).min(dim=-1).values
+    last = torch.where(live, ar, -1).max(dim=-1).values
+    return torch.where(first < _SAMPLE_V, first, last).clamp_(0, _SAMPLE_V - 1), p
+
+
+def sample_bytes(logits: torch.Tensor, recent: Optional[torch.Tensor], u: Optional[torch.Tensor] = None, *,
+                 temperature: float = 1.0, top_p: float = 1.0, top_k: int = 0, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, ascii_only: bool = False,
+                 ban_cr: bool = False, max_run_length: int = 0, generator=None, return_probs: bool = False):
+    """Draw one byte per row of `logits` (..., 256): ids (...) int64, with return_probs=True (ids, probs (..., 256) fp32).
+    The reference's samplers (fft_lm/train_fixed_full.py:651-701, scripts/stream_generate_fast.py:146-170,
+    scripts/generate_chunked_overlap_save.py:39-48, 283-292) as one function, in their order: repetition penalty (a plain
+    division) and presence / frequency penalties over the bytes of `recent`, the ascii_only / ban_cr bans, the
+    max_run_length ban (the last max_run_length ids of `recent` all equal), temperature, nucleus (top_p < 1: the longest
+    prefix of the descending softmax whose running sum stays <= top_p, at least one; top_p >= 1: no such step), top-k
+    (ties kept), softmax, and the first byte whose running probability exceeds u.
+    recent: 1-D uint8 or int64 ids shared by all rows (None or empty: no window), at most 65536, on the logits' device.
+    u: uniforms in [0, 1) of shape logits.shape[:-1]; None draws torch.rand on the device from `generator` -- torch's
+    generator, which a capturing graph registers, as DropoutState does.
+    fp32 logits on a ROCm device run ONE launch (smx_sample_bytes) with no host synchronisation; CPU logits and other
+    dtypes run the same definition as whole-tensor torch ops.  The id drawn always has probability > 0.  Not
+    differentiable."""
+    if not (isinstance(logits, torch.Tensor) and logits.is_floating_point() and logits.dim() >= 1):
+        raise TypeError("sample_bytes: logits must be a floating-point tensor (..., 256)")
+    if logits.shape[-1] != _SAMPLE_V:
+        raise ValueError(f"sample_bytes: the last dimension of logits must be {_SAMPLE_V} (bytes), got {logits.shape[-1]}")
+    dev, lead = logits.device, tuple(logits.shape[:-1])
+    f32 = lambda v: ctypes.c_float(float(v)).value          # both paths compare and divide by the same fp32 values
+    a = {"temperature": f32(temperature), "top_p": f32(top_p), "rep": f32(repetition_penalty),
+         "presence": f32(presence_penalty), "frequency": f32(frequency_penalty), "top_k": int(top_k),
+         "ascii_only": bool(ascii_only), "ban_cr": bool(ban_cr), "max_run": int(max_run_length)}
+    inf = float("inf")
+    if not 0.0 < a["temperature"] < inf:
+        raise ValueError(f"sample_bytes: temperature must be positive and finite, got {temperature}")
+    if not 0.0 < a["rep"] < inf:
+        raise ValueError(f"sample_bytes: repetition_penalty must be positive and finite, got {repetition_penalty}")
+    if a["top_p"] != a["top_p"] or not (abs(a["presence"]) < inf and abs(a["frequency"]) < inf):
+        raise ValueError("sample_bytes: top_p must not be NaN, presence_penalty and frequency_penalty must be finite")
+    if a["top_k"] < 0 or a["max_run"] < 0:
+        raise ValueError("sample_bytes: top_k and max_run_length must not be negative")
+    if recent is None:
+        recent = torch.empty(0, dtype=torch.uint8, device=dev)
+    if not (isinstance(recent, torch.Tensor) and recent.dtype in (torch.uint8, torch.int64) and recent.dim() == 1):
+        raise TypeError("sample_bytes: recent must be a 1-D uint8 or int64 tensor (or None)")
+    if recent.device != dev:
+        raise ValueError(f"sample_bytes: recent is on {recent.device}, logits on {dev}")
+    if recent.numel() > _SAMPLE_MAX_RECENT:
+        raise ValueError(f"sample_bytes: recent holds {recent.numel()} ids, at most {_SAMPLE_MAX_RECENT}")
+    if u is None:
+        u = torch.rand(lead, dtype=torch.float32, device=dev, generator=generator)
+    elif not (isinstance(u, torch.Tensor) and tuple(u.shape) == lead and u.device == dev and u.is_floating_point()):
+        raise ValueError(f"sample_bytes: u must be a floating-point tensor of shape {lead} on {dev}")
+    R = u.numel()
+    if not (logits.is_cuda and logits.dtype == torch.float32 and R > 0):
+        ids, p = _sample_bytes_torch(logits.detach().reshape(-1, _SAMPLE_V).float(), recent, u.reshape(-1).float(), a)
+        return (ids.view(lead), p.view(*lead, _SAMPLE_V)) if return_probs else ids.view(lead)
+    x, row_stride = _xent_rows(logits.detach())
+    u = u.reshape(-1).to(torch.float32).contiguous()
+    if recent.numel() > 1 and recent.stride(0) != 1 or recent.data_ptr() % recent.element_size():
+        recent = recent.contiguous()
+    ids = torch.empty(R, dtype=torch.int64, device=dev)
+    probs = torch.empty((R, _SAMPLE_V), dtype=torch.float32, device=dev) if return_probs else None
+    _call(dev, "smx_sample_bytes", x.data_ptr(), row_stride, recent.data_ptr() if recent.numel() else None,
+          recent.element_size(), recent.numel(), a["temperature"], a["top_p"], a["top_k"], a["rep"], a["presence"],
+          a["frequency"], int(a["ascii_only"]), int(a["ban_cr"]), a["max_run"], u.data_ptr(), ids.data_ptr(), _ptr(probs),
+          R, _SAMPLE_V, _stream(dev))
+    return (ids.view(lead), probs.view(*lead, _SAMPLE_V)) if return_probs else ids.view(lead)

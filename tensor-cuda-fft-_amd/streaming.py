@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .fixed_spectral import FixedSpectralBlock, cutoff_mask, next_pow2
-from .functional import _call, _ptr, _stream
+from .functional import _call, _ptr, _stream, sample_bytes
 
 
 def stream_taps(block: FixedSpectralBlock, n_fft: int, chunk: int, cutoff=None) -> torch.Tensor:
@@ -287,13 +287,67 @@ def _sample_chunk(logits: torch.Tensor, recent: torch.Tensor, temperature: float
     return torch.multinomial(torch.softmax(masked, dim=-1), 1, generator=generator).squeeze(1).clamp_(0, 255)
 
 
+def _native_chunk_step(model, states: StreamStates, win: torch.Tensor, new: torch.Tensor, T: int, temperature: float,
+                       top_p: float, rep: float, generator, update: bool) -> None:
+    """One whole chunk step on static tensors, capturable as it stands: the EMA scan over the window, ema_proj and head,
+    torch.rand, the sampler, the window's shift-and-append and the backbone update.  win (1, max(T, 256)) int64 ends
+    with the T ids of the window; new (chunk) int64 receives the chunk."""
+    chunk, W = model.chunk, win.shape[1]
+    last = states.h_last
+    if model.use_ema and T // model.ema_chunk_len > 0:
+        state = model.ema.scan_tokens(win[:, W - T:], model.ema_chunk_len)
+        last = last + model.ema_proj(torch.view_as_real(state).reshape(1, -1).to(last.dtype))
+    logits = model.head(last.float()).view(chunk, 256)
+    u = torch.rand(chunk, dtype=torch.float32, device=win.device, generator=generator)
+    new.copy_(sample_bytes(logits, win[0, W - 256:], u, temperature=temperature, top_p=top_p, repetition_penalty=rep))
+    win.copy_(torch.cat((win[:, chunk:], new.unsqueeze(0)), dim=1))
+    if update:
+        update_backbone_chunk(model.backbone, states, new.unsqueeze(0))
+
+
+def _generate_native(model, states: StreamStates, buf: torch.Tensor, T: int, n_chunks: int, temperature: float,
+                     top_p: float, rep: float, generator, use_graph: bool) -> None:
+    """generate_chunked's loop with sampler="native": fills buf[0, T:].  The torch sampler penalises the last 256 ids of
+    the text, which is shorter than that while T + c chunk < 256: the static window is then padded on the left with
+    the text's first id -- a duplicate changes no byte's presence, and only presence is penalised here."""
+    chunk, dev = model.chunk, buf.device
+    W = max(T, 256)
+    win = torch.cat((buf[:, :1].repeat(1, W - T), buf[:, :T]), dim=1).contiguous()
+    new = torch.zeros(chunk, dtype=torch.long, device=dev)
+    step = lambda update: _native_chunk_step(model, states, win, new, T, temperature, top_p, rep, generator, update)
+    graph = None
+    for c in range(n_chunks):
+        if use_graph and dev.type == "cuda" and c > 0:                    # chunk 0 ran eagerly: everything is warm
+            if graph is None:
+                graph = torch.cuda.CUDAGraph()
+                if generator is not None:
+                    graph.register_generator_state(generator)
+                with torch.cuda.graph(graph):
+                    step(True)
+            graph.replay()
+        else:
+            step(c + 1 < n_chunks)                                        # nothing reads the state after the last chunk
+        buf[0, T + c * chunk:T + (c + 1) * chunk].copy_(new)              # asynchronous, on the stream of the step
+
+
 @torch.no_grad()
 def generate_chunked(model, prompt: bytes, n_chunks: int, temperature: float = 0.9, top_p: float = 0.9,
-                     rep: float = 1.15, generator=None, use_graph: bool = False, native: bool = True) -> bytes:
+                     rep: float = 1.15, generator=None, use_graph: bool = False, native: bool = True,
+                     sampler: str = "torch") -> bytes:
     """Sample n_chunks chunks of model.chunk bytes after `prompt` (reference :259-299).  The window is the prompt
     padded on the left with spaces to seq_len (or its last seq_len bytes); the result holds that window and the
     generated bytes, as the reference's `generated` list.  Everything stays on the device until the end.
-    use_graph=True captures the backbone update once (after an eager first chunk) and replays it."""
+    use_graph=True captures the backbone update once (after an eager first chunk) and replays it.
+    sampler="torch" (the default) draws with about a dozen eager torch ops and torch.multinomial between two replays.
+    sampler="native" draws with functional.sample_bytes from torch.rand uniforms (one launch on a ROCm device; another
+    random stream than multinomial's), and use_graph=True then captures the WHOLE step once -- EMA scan over a static
+    window, ema_proj and head, torch.rand, the sampler, the window's shift-and-append, the backbone update -- and
+    replays it: between two replays there is only the asynchronous copy of the chunk's ids into the output buffer, and
+    apart from the capture itself no host synchronisation before the final read.  Note: with the native sampler
+    top_p >= 1 means no nucleus step; the torch sampler still applies `cdf <= 1` there (and may drop a tail that
+    rounding lifts above 1)."""
+    if sampler not in ("torch", "native"):
+        raise ValueError(f"sampler must be 'torch' or 'native', got {sampler!r}")
     backbone, chunk = model.backbone, model.chunk
     dev = backbone.embed.weight.device
     T = int(backbone.cfg.seq_len)
@@ -302,6 +356,9 @@ def generate_chunked(model, prompt: bytes, n_chunks: int, temperature: float = 0
     buf = torch.empty((1, T + n_chunks * chunk), dtype=torch.long, device=dev)
     buf[0, :T] = torch.tensor(init, dtype=torch.long, device=dev)
     states = init_layer_states(backbone, buf[:, :T], chunk, native=native)
+    if sampler == "native":
+        _generate_native(model, states, buf, T, n_chunks, temperature, top_p, rep, generator, use_graph)
+        return bytes(buf[0].tolist())
     graph, static_ids = None, torch.zeros((1, chunk), dtype=torch.long, device=dev)
     for c in range(n_chunks):
         n = T + c * chunk
