@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SMX_VERSION 303            /* 0.3.3: smx_spectral_gate_* (0.3.2: smx_diag_clock; conv / cfft workspaces behind the sync area) */
+#define SMX_VERSION 303            /* 0.3.3: smx_spectral_gate_* (0.3.2: smx_diag_clock; conv / cfft workspaces behind the reserved 64 KiB header) */
 
 #define SMX_OK 0
 #define SMX_ERR_INVALID (-1)       /* bad shape / null pointer / misaligned buffer */
@@ -63,7 +63,8 @@ const char* smx_last_error(void);
  * 1 rotated residues, 2 XCD-aware = default, 3 | a << 8 | b << 16 = XCD-aware with the residue rotation
  * (a l2 + b d_tile) mod L, used by tools/rot_scan.py), "round" (workgroups per launch of the streaming
  * kernels, default 512 = one resident round; 0 = a single launch), "force_direct" (0/1), "full8", "fourstep",
- * "fs_bgroups", "fold_gradw", "tiled_dft", "decim16", "conv1", "st_plain" (A/B switches of DESIGN.md), "table_cache_entries" (twiddle-table cache bound).
+ * "fs_bgroups", "tiled_dft", "decim16", "conv1", "st_plain" (A/B switches of DESIGN.md), "table_cache_entries" (twiddle-table cache bound).
+ * "fold_gradw" is RETIRED: still accepted (and counted by smx_options_epoch), without effect on any plan, workspace or result.
  * "st_layout_fwd" / "st_layout_bwd" ("st_layout" sets both): WHICH of a thread's 16 rows per tile are the st_plain
  * write-back rows of the buffer-addressed streaming stores in the forward / backward launches: -2 (default) by the library's
  * rule (4 on the single-launch plan up to 320 MiB of output, else -1: DESIGN.md section 4.6); -1 the first
@@ -82,9 +83,8 @@ int smx_set_option(const char* name, int value);
  * evicted from the cache: a shape "prepared" for stream capture before that may need smx_prepare again. */
 typedef struct smx_options {
   int nsplit, placement, round, force_direct, full8, fourstep, fs_bgroups;
-  int fold_gradw;   /* 0 (default): separate parameter-gradient reduction launch (k_gradw); 1: smx_backward with
-                       SMX_PHASE_ALL on the single-launch plan reduces them inside the transform launch --
-                       bit-identical, measured slower on MI355X, kept as an A/B switch */
+  int fold_gradw;   /* RETIRED, no effect: the parameter gradients are always reduced by a launch of their own
+                       (k_gradw_slab).  The field keeps its place because the layout of this struct is ABI. */
   int decim16;      /* 1 (default): SMX_PATH_DECIM16 is used where it applies; 0: DFT products (A/B, tests) */
   int conv1;        /* 1 (default): smx_conv_* run ONE launch per direction for n_fft = 512, 1024, 2048
                        (k_conv1) from 48 (batch row, 32-channel tile) items on -- as 256-thread
@@ -143,13 +143,9 @@ int smx_forward(const float* x, const float* w_re, const float* w_im, const floa
 #define SMX_PHASE_INVERSE 2
 #define SMX_PHASE_PARAMS 4
 #define SMX_PHASE_ALL 7
-/* With option fold_gradw = 1 and SMX_PHASE_ALL on the single-launch plan (k <= 256) the parameter gradients are
- * reduced INSIDE the transform launch (reduction workgroups appended to its grid), which needs a few flag words of the workspace -- its first
- * 64 KiB are reserved for them in every layout -- to be zero when the launch starts.  The library clears them itself (one small hipMemsetAsync per call) unless the caller
- * ORs SMX_PHASE_SYNC_CLEAN into `phases`, vouching that the last thing that touched this workspace was
- * an smx_forward / smx_block_forward of the same (B, D) that was given the workspace (it leaves those words zero),
- * or a completed smx_backward (it leaves them zero as well), and that nothing else wrote to those 64 KiB.  The Python autograd functions hand
- * forward's workspace to backward and set the flag. */
+/* SMX_PHASE_SYNC_CLEAN: accepted in `phases` and IGNORED (it vouched for flag words of the retired option fold_gradw).
+ * It selects no phase: `phases` = 8 alone is refused like 0.  The first 64 KiB of every workspace layout, once those
+ * flag words, stay reserved: nothing reads or writes them. */
 #define SMX_PHASE_SYNC_CLEAN 8
 int smx_backward(const float* g, const float* xk, const float* w_re, const float* w_im,
                  float* grad_x, float* gw_re, float* gw_im, float* gbias, void* workspace,

@@ -374,19 +374,16 @@ struct Ws {
   size_t wt = 0;                 // (k, D) complex: the filter packed for the unpack phase
   size_t fs = 0;                 // four-step path: [B*ndt][L][16][256] complex tile spectra
   size_t gscp = 0;               // four-step path: partial sums of the row-scale gradient
-  size_t sync = 0;               // SYNC_WORDS counters of the launches that fold the parameter gradients in
   size_t rows = 0;               // band-group plan: a (B, N, D) float copy of the input (masked g; LayerNorm(x) of the block)
 };
 
-// The first SYNC_BYTES of EVERY workspace layout are the sync area (flag words of the launches that fold the
-// parameter-gradient reduction in): the same place whatever the shape, never used as scratch, so the "zero between
-// calls" state survives a workspace that layers of different shapes share.
-constexpr size_t SYNC_BYTES = 65536;
+// The first WS_HEADER_BYTES of EVERY workspace layout are a reserved header that nothing reads or writes (once the
+// flag words of the retired option fold_gradw): every offset below it is pinned, so it stays until it is dropped on purpose.
+constexpr size_t WS_HEADER_BYTES = 65536;
 
 Ws ws_layout(const Plan& p, int B, int N, int D) {
   Ws w;
-  size_t o = SYNC_BYTES;
-  w.sync = 0;
+  size_t o = WS_HEADER_BYTES;
   if (p.path == SMX_PATH_DECIM16) {
     w.slab = o; o += al((size_t)B * p.k * D * sizeof(cf));
     w.gbp = o; o += al((size_t)B * D * sizeof(float));
@@ -531,12 +528,6 @@ void filter_bwd(DecimArgs& a, const float* w_re, const float* w_im, const float*
 void use_tiles(DecimArgs& a, const Plan& p, void* tiles) { a.ws_f = (cf*)tiles; a.nsplit = p.fs_nsplit; a.lc = p.fs_lc; }
 // the same launch without its inverse half: products out, spectrum parked
 DecimArgs no_out(DecimArgs a) { a.out = nullptr; return a; }
-// The fused forward launches leave the workspace's sync area zero when they are given one: a backward call on the same
-// workspace may then skip its own clearing (SMX_PHASE_SYNC_CLEAN).
-void use_sync(DecimArgs& a, const Ws& w, void* workspace, size_t workspace_bytes) {
-  if (ws_usable(workspace, workspace_bytes, w.total) && sync_words(a.g.B, a.g.D) * sizeof(unsigned) <= SYNC_BYTES)
-    a.sync = (unsigned*)((char*)workspace + w.sync);
-}
 
 // The filter in the layout of the unpack phase (FilterArgs::wt).  `ready`: a copy packed by an earlier
 // call with the same weights (backward reusing forward's) -- nothing is launched.  `keep`: caller buffer
@@ -827,7 +818,6 @@ static int forward_impl(const Shape& h, const float* x, const float* w_re, const
       e.rows = 0;
       HIP_TRY(launch_edge_synth_acc((cf*)(ws + w.edge1), y, e, s));
     } else if (p.kind == Kind::Single) {
-      use_sync(a, w, workspace, workspace_bytes);
       HIP_TRY(launch_fused(a, p.nb, 0, s, io));
     } else {
       HIP_TRY(launch_split_a(a, p.nb, false, s, io));
@@ -874,8 +864,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
   DropCfg dc;
   if (int rc = drop_cfg(dropout_p, rng_state, &dc)) return rc;
   if (!g || !w_re || !w_im) return fail(SMX_ERR_INVALID, "g, w_re, w_im must be non-NULL");
-  const bool sync_clean = (phases & SMX_PHASE_SYNC_CLEAN) != 0;
-  phases &= ~SMX_PHASE_SYNC_CLEAN;
+  phases &= ~SMX_PHASE_SYNC_CLEAN;     // accepted and ignored (smx.h)
   if (phases < 1 || phases > 7) return fail(SMX_ERR_INVALID, "phases must be a combination of 1, 2, 4");
   if ((phases & SMX_PHASE_INVERSE) && !grad_x) return fail(SMX_ERR_INVALID, "grad_x is NULL");
   const bool want_w = gw_re || gw_im || gbias;
@@ -936,8 +925,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
       if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F, filter_pack,
                                nullptr, s))
         return rc;
-    int slab_rows = B;          // rows of the gradient slab that launch_gradw_slab sums
-    bool reduce = do_par;       // ... in its own launch
+    int slab_rows = B;          // rows of the gradient slab that launch_gradw_slab sums, always in a launch of its own
     if (p.kind == Kind::Sixteen) {
       if (do_spec) {
         if (p.nsplit > 1) {
@@ -986,25 +974,6 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
       }
       if (do_inv) HIP_TRY(launch_edge_synth_acc(se, grad_x, e, s));
     } else if (do_spec && do_inv && p.kind == Kind::Single) {
-      // Option fold_gradw = 1: one launch for everything -- the parameter-gradient reduction rides behind the
-      // transform workgroups (gradw_tail in smx_decim.hip) instead of a separate k_gradw launch + two kernel
-      // boundaries.  Bit-identical, wait-free for the producers, and MEASURED SLOWER (profiles/r03_fold_gradw_ab.txt:
-      // C2 backward 111.0 -> 115.8 us, C5 290 -> 304 us with the flag words already clean, 4 us more when the
-      // library clears them): the reduction workgroups inherit the transform kernel's footprint (two per CU) and
-      // can only start when transform workgroups retire, so the tail is longer than k_gradw's 7.5 us + boundaries.
-      // Off by default.
-      // (2-byte rows: never -- their kernels hold no gradw_tail; SMX_PHASE_SYNC_CLEAN is then
-      // accepted and has nothing to vouch for)
-      const bool fold = do_par && mode == 1 && p.nb <= 2 && cur_opts().fold_gradw != 0 && io == SMX_IO_F32 &&
-                        sync_words(B, D) * sizeof(unsigned) <= SYNC_BYTES;
-      if (fold) {
-        a.sync = (unsigned*)(ws + w.sync);
-        a.n_cons = gradw_tail_blocks(D, F, true);
-        a.gw_re = gw_re; a.gw_im = gw_im; a.gbias = gbias;
-        a.fa.slab_agent = 1;
-        if (!sync_clean) HIP_TRY(hipMemsetAsync(a.sync, 0, sync_words(B, D) * sizeof(unsigned), s));
-        reduce = false;
-      }
       HIP_TRY(launch_fused(a, p.nb, mode, s, io, oio));
     } else {
       if (do_spec) {
@@ -1017,7 +986,7 @@ static int backward_impl(const Shape& h, const float* g, const float* xk, const 
       }
       if (do_inv) HIP_TRY(launch_split_b(a, p.nb, false, s, oio));
     }
-    if (reduce)
+    if (do_par)
       HIP_TRY(launch_gradw_slab((cf*)(ws + w.slab), (float*)(ws + w.gbp), gw_re, gw_im, gbias, slab_rows, D, F, p.k, s));
     return SMX_OK;
   }
@@ -1086,7 +1055,7 @@ static bool cfft_plan(const Shape& h, Plan* p) {
   *p = tile_plan(h);
   return true;
 }
-static size_t cfft_need(const Plan& p) { return SYNC_BYTES + al((size_t)p.nwg * p.L * EX * sizeof(cf)); }   // the sync area stays untouched (ws_layout)
+static size_t cfft_need(const Plan& p) { return WS_HEADER_BYTES + al((size_t)p.nwg * p.L * EX * sizeof(cf)); }   // behind the reserved header (ws_layout)
 int smx_cfft_workspace_bytes(const smx_shape* shape, size_t* out) {
   if (!shape || !out) return fail(SMX_ERR_INVALID, "NULL argument");
   Shape h{shape->B, shape->rows, shape->D, shape->n_fft / 2 + 1, shape->n_fft, shape->n_fft / 2 + 1};
@@ -1116,7 +1085,7 @@ int smx_cfft_ex(const smx_shape* shape, const float* z, float* out, void* worksp
   a.ws_z = a.ws_zs = a.ws_s = nullptr;
   a.in = z; a.out = nullptr;
   a.fa.xk_out = out;
-  use_tiles(a, p, (char*)workspace + SYNC_BYTES);
+  use_tiles(a, p, (char*)workspace + WS_HEADER_BYTES);
   HIP_TRY(launch_fs_a(a, s));
   HIP_TRY(launch_fs_f(a, 3, s));
   return SMX_OK;
@@ -1146,8 +1115,7 @@ static bool conv_plan(const Shape& h, Plan* p) {
 }
 static ConvWs conv_ws(const Plan& p, const Shape& h) {
   ConvWs w;
-  size_t o = SYNC_BYTES;     // as every layout: the first 64 KiB are the flag words of the folded reductions, never
-                             // scratch -- a layer backward that trusts them (SMX_PHASE_SYNC_CLEAN) may share this buffer
+  size_t o = WS_HEADER_BYTES;     // as every layout: the first 64 KiB are reserved and unused (ws_layout)
   w.save = (size_t)p.nwg * p.L * EX * sizeof(cf);      // (k_conv1: [workgroup][16 L / 2][512], the same bytes;
   if (p.conv1 && p.conv1_nj == 8)                       //  on 16-channel workgroups a ragged last tile rounds up)
     w.save = (size_t)conv1_workgroups(h.B, h.D, 8) * (p.L / 2 * 16) * 256 * sizeof(cf);
@@ -1584,7 +1552,6 @@ static int block_forward_impl(const float* x, const float* ln_w, const float* ln
     if (int rc = pack_filter(a, p, w, workspace, workspace_bytes, w_re, w_im, D, F, nullptr, filter_pack,
                              s))
       return rc;
-    use_sync(a, w, workspace, workspace_bytes);                // left zero for smx_block_backward (SYNC_CLEAN)
     HIP_TRY(launch_fused_block(a, p.nb, s, io));
     return SMX_OK;
   }
@@ -1666,8 +1633,8 @@ static int dw_check(int B, int T, int C) {
     return fail(SMX_ERR_UNSUPPORTED, "smx_dwconv3_*: tensor too large for one launch");
   return SMX_OK;
 }
-// (the workspaces of the small ops lie behind the sync area, as every layout: ws_layout)
-static size_t dw_need(int B, int T, int C) { return SYNC_BYTES + al(dwconv3_workspace_bytes(B, T, C)); }
+// (the workspaces of the small ops lie behind the reserved header, as every layout: ws_layout)
+static size_t dw_need(int B, int T, int C) { return WS_HEADER_BYTES + al(dwconv3_workspace_bytes(B, T, C)); }
 int smx_dwconv3_workspace_bytes(int B, int T, int C, size_t* out) {
   if (!out) return fail(SMX_ERR_INVALID, "out is NULL");
   if (int rc = dw_check(B, T, C)) return rc;
@@ -1691,7 +1658,7 @@ int smx_dwconv3_backward(const float* g, const float* x, const float* w, const f
   if (grad_scale && !scale) return fail(SMX_ERR_INVALID, "grad_scale without scale");
   if (int rc = need_ws(workspace, workspace_bytes, dw_need(B, T, C), "smx_dwconv3_workspace_bytes")) return rc;
   HIP_TRY(launch_dwconv3_bwd(g, x, w, bias, scale, grad_x, grad_w, grad_bias, grad_scale,
-                             (float*)((char*)workspace + SYNC_BYTES), B, T, C, (hipStream_t)stream));
+                             (float*)((char*)workspace + WS_HEADER_BYTES), B, T, C, (hipStream_t)stream));
   return SMX_OK;
 }
 
@@ -1759,7 +1726,7 @@ static int gate_check(int B, int F, int C) {
   if (B > 65535) return fail(SMX_ERR_UNSUPPORTED, "smx_spectral_gate_* takes at most 65535 batch rows");
   return SMX_OK;
 }
-static size_t gate_need(int B, int F, int C) { return SYNC_BYTES + al(gate_workspace_bytes(B, F, C)); }
+static size_t gate_need(int B, int F, int C) { return WS_HEADER_BYTES + al(gate_workspace_bytes(B, F, C)); }
 int smx_spectral_gate_workspace_bytes(int B, int F, int C, size_t* out) {
   if (int rc = gate_check(B, F, C)) return rc;
   if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
@@ -1785,12 +1752,12 @@ int smx_spectral_gate_backward(const float* g, const float* x, const float* a, c
   if (grad_x == g || grad_x == x) return fail(SMX_ERR_INVALID, "grad_x must not alias g or x");
   if (int r = need_ws(workspace, workspace_bytes, gate_need(B, F, C), "smx_spectral_gate_workspace_bytes")) return r;
   HIP_TRY(launch_gate_bwd((const cf*)g, (const cf*)x, (const cf*)a, u, p, q, m, (cf*)grad_x, (cf*)s1, rc, rp,
-                          (cf*)((char*)workspace + SYNC_BYTES), B, F, C, (hipStream_t)stream));
+                          (cf*)((char*)workspace + WS_HEADER_BYTES), B, F, C, (hipStream_t)stream));
   return SMX_OK;
 }
 
 // ---- BicameralBlock's fusion line (smx_time.hip) --------------------------------------------------------------------------
-static size_t mix_need() { return SYNC_BYTES + al(mix_workspace_bytes()); }
+static size_t mix_need() { return WS_HEADER_BYTES + al(mix_workspace_bytes()); }
 int smx_mix_workspace_bytes(size_t* out) {
   if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
   *out = mix_need();
@@ -1815,7 +1782,7 @@ int smx_mix_backward(const float* g, const float* a, const float* b, const float
   if (int rc = mix_check(n, g, a, b, grad_a, grad_b)) return rc;
   if ((uintptr_t)grad_c & 15) return fail(SMX_ERR_INVALID, "tensors must be 16-byte aligned");
   if (int rc = need_ws(workspace, workspace_bytes, mix_need(), "smx_mix_workspace_bytes")) return rc;
-  HIP_TRY(launch_mix_bwd(g, a, b, w, c3, grad_a, grad_b, grad_c, grad_w, (float*)((char*)workspace + SYNC_BYTES), n,
+  HIP_TRY(launch_mix_bwd(g, a, b, w, c3, grad_a, grad_b, grad_c, grad_w, (float*)((char*)workspace + WS_HEADER_BYTES), n,
                          (hipStream_t)stream));
   return SMX_OK;
 }
@@ -1823,7 +1790,7 @@ int smx_mix_backward(const float* g, const float* a, const float* b, const float
 
 // ---- EnhancedSpectralBlock row lines (smx_enh.hip) ----
 int smx_enh_supported(int D) { return enh_supported(D) ? 1 : 0; }
-static size_t enh_need(int B, int T, int D) { return SYNC_BYTES + al(enh_part_floats((long long)B * T, D) * sizeof(float)); }
+static size_t enh_need(int B, int T, int D) { return WS_HEADER_BYTES + al(enh_part_floats((long long)B * T, D) * sizeof(float)); }
 int smx_enh_workspace_bytes(int B, int T, int D, size_t* out) {
   if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
   if (B <= 0 || T <= 0 || D <= 0) return fail(SMX_ERR_INVALID, "shape must be positive: B=%d T=%d D=%d", B, T, D);
@@ -1839,7 +1806,7 @@ static int enh_check(int B, int T, int D, std::initializer_list<const void*> ptr
 }
 static int enh_ws(void* workspace, size_t workspace_bytes, int B, int T, int D, float** part) {
   if (int rc = need_ws(workspace, workspace_bytes, enh_need(B, T, D), "smx_enh_workspace_bytes")) return rc;
-  *part = (float*)((char*)workspace + SYNC_BYTES);
+  *part = (float*)((char*)workspace + WS_HEADER_BYTES);
   return SMX_OK;
 }
 int smx_rope_norm_forward(const float* x, const float* rotation, int rot_rows, const float* ln1_w, const float* ln1_b,
@@ -2064,7 +2031,7 @@ static int ema_tokens_src(const void* tokens, int token_bytes, long long row_str
   *src = EmaSrc{tokens, token_bytes == 1 ? 1 : 2, row_stride, B, S, L / 2 + 1, L};
   return SMX_OK;
 }
-static size_t ema_need(int B, int S, int F) { return SYNC_BYTES + al(ema_states_bytes(B, S, F)) + al(ema_part_bytes(B, F)); }
+static size_t ema_need(int B, int S, int F) { return WS_HEADER_BYTES + al(ema_states_bytes(B, S, F)) + al(ema_part_bytes(B, F)); }
 static int ema_fwd(const EmaSrc& src, int mode, const float* init, const float* rho_logit, const float* theta_raw,
                    float* out, void* stream) {
   if (!rho_logit || !out || (mode == SMX_EMA_ALIGNED && !theta_raw))
@@ -2082,7 +2049,7 @@ static int ema_bwd(const EmaSrc& src, int mode, const float* g, const float* ini
     return fail(SMX_ERR_INVALID, "g, init, grad_chunks, grad_init must be 8-byte aligned");
   if (grad_chunks && grad_chunks == src.ptr) return fail(SMX_ERR_INVALID, "grad_chunks must not alias chunks");
   if (int rc = need_ws(workspace, workspace_bytes, ema_need(src.B, src.S, src.F), "smx_ema_workspace_bytes")) return rc;
-  char* states = (char*)workspace + SYNC_BYTES;
+  char* states = (char*)workspace + WS_HEADER_BYTES;
   HIP_TRY(launch_ema_bwd(src, mode == SMX_EMA_POLAR, (const cf*)g, (const cf*)init, rho_logit, theta_raw, (cf*)grad_chunks,
                          (cf*)grad_init, grad_rho_logit, grad_theta_raw, (cf*)states,
                          (float*)(states + al(ema_states_bytes(src.B, src.S, src.F))), (hipStream_t)stream));
@@ -2154,7 +2121,7 @@ static int head_check(long long R, int C, int O) {
   if (R * C >= (1ll << 40)) return fail(SMX_ERR_INVALID, "R*C too large");
   return SMX_OK;
 }
-static size_t head_need(long long R, int C) { return SYNC_BYTES + al(head_part_w_bytes(R, C)) + al(head_part_b_bytes(R)); }
+static size_t head_need(long long R, int C) { return WS_HEADER_BYTES + al(head_part_w_bytes(R, C)) + al(head_part_b_bytes(R)); }
 int smx_head_supported(int C, int O) { return (O == 1 || O == 2) && ln_supported(C) ? 1 : 0; }
 int smx_head_workspace_bytes(long long R, int C, int O, size_t* out) {
   if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
@@ -2181,7 +2148,7 @@ int smx_head_backward(const float* g, const float* h, const float* w, float* gra
     return fail(SMX_ERR_INVALID, "g, grad_w and grad_b must be 4-byte aligned");
   if (grad_h && (grad_h == h || grad_h == g)) return fail(SMX_ERR_INVALID, "grad_h must not alias h or g");
   if (int rc = need_ws(workspace, workspace_bytes, head_need(R, C), "smx_head_workspace_bytes")) return rc;
-  char* part_w = (char*)workspace + SYNC_BYTES;
+  char* part_w = (char*)workspace + WS_HEADER_BYTES;
   HIP_TRY(launch_head_bwd(g, h, w, grad_h, grad_w, grad_b, (float*)part_w, (float*)(part_w + al(head_part_w_bytes(R, C))),
                           R, C, O, (hipStream_t)stream));
   return SMX_OK;
@@ -2200,7 +2167,7 @@ static int xent_check_args(const char* fn, long long R, int V, long long row_str
     return fail(SMX_ERR_INVALID, "%s: reduction must be SMX_XENT_MEAN, _SUM or _NONE, got %d", fn, reduction);
   return SMX_OK;
 }
-static size_t xent_need(long long R) { return SYNC_BYTES + al((size_t)xent_num_blocks(R) * 2 * sizeof(float)); }
+static size_t xent_need(long long R) { return WS_HEADER_BYTES + al((size_t)xent_num_blocks(R) * 2 * sizeof(float)); }
 int smx_xent_supported(int V) { return V >= 1 ? 1 : 0; }
 int smx_xent_workspace_bytes(long long R, int V, size_t* out) {
   if (!out) return fail(SMX_ERR_INVALID, "out must be non-NULL");
@@ -2218,7 +2185,7 @@ int smx_xent_forward(const float* logits, long long row_stride, const long long*
     return fail(SMX_ERR_INVALID, "logits, loss, lse, count must be 4-byte aligned and targets 8-byte aligned");
   if (int rc = need_ws(workspace, workspace_bytes, xent_need(R), "smx_xent_workspace_bytes")) return rc;
   HIP_TRY(launch_xent_fwd(logits, row_stride, targets, ignore_index, reduction, loss, lse, count,
-                          (float*)((char*)workspace + SYNC_BYTES), R, V, (hipStream_t)stream));
+                          (float*)((char*)workspace + WS_HEADER_BYTES), R, V, (hipStream_t)stream));
   return SMX_OK;
 }
 int smx_xent_backward(const float* g, const float* logits, long long row_stride, const long long* targets,

@@ -77,17 +77,6 @@ struct DecimArgs {
   unsigned drop_thr;    // round(p * 65536); 0 = none
   float drop_scale;     // 65536 / (65536 - drop_thr)
   const unsigned long long* rng;
-  // parameter gradients folded into the backward launch (launch_fused, mode 1): `n_cons` reduction workgroups are
-  // appended to the grid of the (last round of the) transform launch.  They only ever wait for workgroups with
-  // a smaller index -- which the dispatcher has already started -- so nothing can deadlock, whatever else is
-  // resident.  sync[dt * B + b] is raised by transform workgroup (b, dt) once its slab rows have landed; the last
-  // reduction workgroup to finish leaves the area zero again.
-  unsigned* sync;       // sync_words(B, D) words, zero on entry: cleared by the library (hipMemsetAsync) unless the
-                        // caller vouches for it (SMX_PHASE_SYNC_CLEAN); the fused FORWARD launch clears it as well
-  int n_cons;           // reduction workgroups appended (0 = parameter gradients by launch_gradw_slab)
-  float* gw_re;         // (D, F)
-  float* gw_im;         // (D, F)
-  float* gbias;         // (D) or null
   // fused block (launch_fused_block only): in = x, LayerNorm folded into the load, + x at the store
   const cf* ln_stats;   // (B,N) (mean, rstd)
   const float* ln_w;    // (D) or null (= 1)
@@ -113,11 +102,6 @@ static inline void store_layout(DecimArgs& a, int layout) {
   if (layout == 3 || layout == 4) a.st_wsh = 0;
 }
 
-// one flag per transform workgroup + the count of finished reduction workgroups
-static inline size_t sync_words(int B, int D) { return (size_t)B * ((D + DT - 1) / DT) + 1; }
-constexpr int GWT_BINS = 8;        // bins per appended reduction workgroup
-// reduction workgroups launch_fused appends for (D, F): ceil(D/32) * (ceil(F/GWT_BINS) + (bias ? 1 : 0))
-int gradw_tail_blocks(int D, int F, bool bias);
 // sixteen-row decimation (N % 16 == 0, N % 256 != 0, k <= 128 nb): one launch per direction, modes as launch_fused
 hipError_t launch_fused16(const DecimArgs& a, int nb, int mode, hipStream_t s);
 // ... its residue-split form for few (batch row, d-tile) pairs: (A) partial spectra per chunk of tiles, then
@@ -127,8 +111,8 @@ hipError_t launch_split16_a(const DecimArgs& a, int nb, bool drop_in, hipStream_
 hipError_t launch_split16_b(const DecimArgs& a, int nb, bool drop_out, hipStream_t s);
 // fused single-launch path (nsplit == 1)
 // io (here and in launch_split_a / launch_split_b): element type of the rows a.in / a.out point at (SMX_IO_*: 0 f32,
-// 1 bf16, 2 fp16 -- 2-byte rows, everything else f32).  io != 0 exists for modes 0 and 1 without zero-padded rows,
-// band groups (accumulate) or the folded parameter-gradient reduction (n_cons); anything else: hipErrorInvalidValue
+// 1 bf16, 2 fp16 -- 2-byte rows, everything else f32).  io != 0 exists for modes 0 and 1 without zero-padded rows
+// or band groups (accumulate); anything else: hipErrorInvalidValue
 // oio: element type of a.out where it differs from a.in's (-1 = io).  Only (io 2-byte, oio f32, mode 1) exists: the
 // block backward, whose grad_h stays f32 for the LayerNorm backward behind it
 hipError_t launch_fused(const DecimArgs& a, int nb, int mode, hipStream_t s, int io = 0, int oio = -1);

@@ -342,15 +342,13 @@ def forward_raw(x, w_re, w_im, bias, *, conj_w=False, save_spectrum=False, dropo
 
 
 PHASE_SPECTRUM, PHASE_INVERSE, PHASE_PARAMS, PHASE_ALL = 1, 2, 4, 7     # include/smx.h
-PHASE_SYNC_CLEAN = 8
 
 
 def backward_raw(g, xk, w_re, w_im, *, want_x=True, want_w=True, phases=PHASE_ALL, grad_x=None,
-                 flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, sync_clean=False, io=0):
+                 flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, io=0):
     """Runs smx_backward.  Returns (grad_x, flat) where flat = [gw_re | gw_im | gbias] fp32.
     `ws`: workspace of an earlier phase (a call made on another stream must not pick that stream's), or the
-    workspace the forward call of the same autograd node used -- then `sync_clean=True` tells the library that
-    its flag words are zero (include/smx.h, SMX_PHASE_SYNC_CLEAN) and it skips clearing them.
+    workspace the forward call of the same autograd node used.
     io: element type of g and grad_x, as in forward_raw (the parameter gradients stay fp32)."""
     B, N, D = g.shape
     F = w_re.shape[1]
@@ -364,8 +362,6 @@ def backward_raw(g, xk, w_re, w_im, *, want_x=True, want_w=True, phases=PHASE_AL
         ws = _workspace(g.device, _ws_bytes(B, N, D, F))
     if not want_x:
         phases &= ~PHASE_INVERSE
-    if sync_clean:
-        phases |= PHASE_SYNC_CLEAN
     _prepare(g.device, N)
     args = (g.data_ptr(), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(), _ptr(grad_x), _ptr(gw_re), _ptr(gw_im), _ptr(gb),
             *_ws_arg(ws), B, N, D, F, phases, float(dropout_p), _ptr(rng), _ptr(pack), _stream(g.device))
@@ -424,7 +420,7 @@ class _SpectralMix(torch.autograd.Function):
         rng = drop_state.next() if dropout_p > 0.0 else None
         pack = _new_pack(x, w_re) if needs else None         # packed filter, reused by backward
         B, N, D = x.shape
-        # backward runs on forward's workspace: the forward launch leaves its flag words zero (SYNC_CLEAN)
+        # backward runs on forward's workspace
         ws = _workspace(x.device, _ws_bytes(B, N, D, w_re.shape[1]))
         io = _IO[x.dtype]                                    # bf16 / fp16 x: plans with native 2-byte rows only
         y, xk = forward_raw(x, w_re, w_im, bias, save_spectrum=needs, dropout_p=dropout_p, rng=rng,
@@ -454,8 +450,7 @@ class _SpectralMix(torch.autograd.Function):
         sync = ctx.sync if (want_w and ctx.sync is not None and ctx.sync.active()) else None
         dkw = dict(dropout_p=ctx.drop[0], rng=ctx.drop[1], pack=ctx.pack, io=ctx.io)
         if sync is None:
-            gx, flat = backward_raw(g, xk, w_re, w_im, want_x=want_x, want_w=want_w, ws=ctx.ws,
-                                    sync_clean=ctx.ws is not None, **dkw)
+            gx, flat = backward_raw(g, xk, w_re, w_im, want_x=want_x, want_w=want_w, ws=ctx.ws, **dkw)
             if not want_x:
                 gx = None
         else:
@@ -552,8 +547,8 @@ def block_forward_raw(x, ln_w, ln_b, eps, w_re, w_im, bias, *, save=True, dropou
 
 
 def block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, *, phases=PHASE_ALL, grad_x=None,
-                       flat=None, ln_flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, sync_clean=False,
-                       io=0, grad_h=None):
+                       flat=None, ln_flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, io=0,
+                       grad_h=None):
     """Runs smx_block_backward.  Returns (grad_x, flat, ln_flat): flat = [gw_re | gw_im | gbias],
     ln_flat = [g_ln_w | g_ln_b].
     io: element type of g, x and grad_x, as in block_forward_raw (every parameter gradient stays fp32).  A 2-byte io
@@ -570,8 +565,6 @@ def block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, *, phases=PHASE_ALL, g
         grad_h = torch.empty((B, N, D), dtype=torch.float32, device=g.device)
     if ws is None:
         ws = _workspace(g.device, _ws_bytes(B, N, D, F))
-    if sync_clean:
-        phases |= PHASE_SYNC_CLEAN
     _prepare(g.device, N)
     head = (g.data_ptr(), x.data_ptr(), stats.data_ptr(), _ptr(ln_w), _ptr(xk), w_re.data_ptr(), w_im.data_ptr(),
             grad_x.data_ptr(), ln_flat[:D].data_ptr(), ln_flat[D:].data_ptr(), gw_re.data_ptr(), gw_im.data_ptr(),
@@ -627,8 +620,7 @@ class _SpectralBlockMix(torch.autograd.Function):
         if ctx.io and sync is not None:                      # one fp32 grad_h for every phase
             dkw["grad_h"] = torch.empty(g.shape, dtype=torch.float32, device=g.device)
         if sync is None:
-            gx, flat, lnf = block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, ws=ctx.ws,
-                                               sync_clean=ctx.ws is not None, **dkw)
+            gx, flat, lnf = block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, ws=ctx.ws, **dkw)
         else:
             def run(phases, bufs):
                 gx, flat, lnf = bufs or (None, None, None)

@@ -9,13 +9,13 @@
 //
 // Inputs: every value a launcher's selection distinguishes plus one outside each range -- nb 1 2 4 3; mode 0 ... 3
 // for the launchers with modes 0 1 2, 0 ... 5 for the column launches (modes 0 ... 4); io 0 ... 3; oio -1 ... 2; dir 0 1;
-// nj 8 16; rows R < N or not (pad); drop_thr zero or not; accumulate; out null or not; n_cons 0 or 5; ... -- as one cross
+// nj 8 16; rows R < N or not (pad); drop_thr zero or not; accumulate; out null or not; ... -- as one cross
 // product per launcher, with these cuts that keep expected.txt below 256 KiB:
 //   * the grid inputs (a.round 0 / 512; 80 and 1280 workgroups: B = 40, D = 64 with nsplit 1 and 16, or B = 640) are
 //     varied at a few settings of the selection inputs only, the selection inputs at round 0, B = 40, nsplit 1;
 //   * launch_fused: out == NULL only changes the pick of an accumulating launch, so it is crossed with accumulate set;
-//     n_cons > 0 is crossed without dropout (it is refused for 2-byte rows, else extends the grid), with oio = 0 only
-//     where that differs from -1; beside io = 3 or oio = 1, 2 (no instance) pad / drop / acc are set one at a time;
+//     beside io = 3 or oio = 1, 2 (no instance) pad / drop / acc are set one at a time.  The last column (n_cons) was
+//     an input that no longer exists: it prints 0, so the lines keep their text;
 //   * launch_fs_f: fs_bgroups and the row-scale gradient (gsc with gsc_part) only bear on mode 1 -- crossed there at
 //     every L up to 64 and every multiple of 4 above, and with the other modes at L = 8, 18, 48, 64.
 #include <cxxabi.h>
@@ -79,7 +79,6 @@ static DecimArgs args(int B, int D, int N, int R, int nsplit = 1, int round = 0)
   a.ws_z = a.ws_zs = a.ws_s = a.ws_f = dummy<cf>(); a.conv_src = dummy<cf>();
   a.ca.h_re = a.ca.h_im = dummy<float>(); a.ca.xs = dummy<cf>(); a.ca.p_part = a.ca.r_part = dummy<cf>();
   a.drop_scale = 1.f; a.rng = dummy<unsigned long long>();
-  a.sync = dummy<unsigned>(); a.gw_re = a.gw_im = a.gbias = dummy<float>();
   a.ln_stats = dummy<cf>(); a.ln_w = a.ln_b = dummy<float>();
   return a;
 }
@@ -106,29 +105,24 @@ static const GridCase GRIDS[] = {{40, 1, 0}, {40, 1, 512}, {40, 16, 0}, {40, 16,
 
 static void fused() {
   puts("# fused: B round nb mode io oio pad drop acc out n_cons");
-  auto one = [](const GridCase& gc, int nb, int mode, int io, int oio, int pad, int drop, int acc, int out, int ncons) {
+  auto one = [](const GridCase& gc, int nb, int mode, int io, int oio, int pad, int drop, int acc, int out) {
     DecimArgs a = args(gc.B, 64, N0, pad ? N0 / 2 : N0, 1, gc.round);
-    a.drop_thr = drop ? THR : 0; a.accumulate = acc; a.n_cons = ncons;
+    a.drop_thr = drop ? THR : 0; a.accumulate = acc;
     if (!out) a.out = nullptr;
-    IN("fused %d %d %d %d %d %d %d %d %d %d %d", gc.B, gc.round, nb, mode, io, oio, pad, drop, acc, out, ncons);
+    IN("fused %d %d %d %d %d %d %d %d %d %d 0", gc.B, gc.round, nb, mode, io, oio, pad, drop, acc, out);
     call([&] { return launch_fused(a, nb, mode, S, io, oio); });
   };
   for (int nb : NBS) for (int mode : MODES3) for (int io : IOS) for (int oio : OIOS)
     for (int pad = 0; pad < 2; ++pad) for (int drop = 0; drop < 2; ++drop) for (int acc = 0; acc < 2; ++acc) {
       if ((io == 3 || oio > 0) && pad + drop + acc > 1) continue;       // beside a value no instance has: one at a time
-      one(GRIDS[0], nb, mode, io, oio, pad, drop, acc, 1, 0);
+      one(GRIDS[0], nb, mode, io, oio, pad, drop, acc, 1);
     }
   for (int nb : NBS) for (int mode : MODES3) for (int io : IOS) for (int pad = 0; pad < 2; ++pad)
-    for (int drop = 0; drop < 2; ++drop) one(GRIDS[0], nb, mode, io, -1, pad, drop, 1, 0, 0);
-  for (int nb : NBS) for (int mode : MODES3) for (int io : IOS) for (int oio : {-1, 0})
-    for (int pad = 0; pad < 2; ++pad) for (int acc = 0; acc < 2; ++acc) {
-      if (oio == 0 && (io == 0 || io == 3 || pad || acc)) continue;     // (oio = 0 is oio = -1 for f32 rows)
-      one(GRIDS[0], nb, mode, io, oio, pad, 0, acc, 1, 5);
-    }
-  // grid: rounds, the single launch of the four-band instances, the reduction workgroups behind the last round
+    for (int drop = 0; drop < 2; ++drop) one(GRIDS[0], nb, mode, io, -1, pad, drop, 1, 0);
+  // grid: rounds, the single launch of the four-band instances
   for (const GridCase& gc : GRIDS)
     if (gc.nsplit == 1 && &gc != &GRIDS[0])
-      for (int nb : {1, 4}) for (int ncons : {0, 5}) for (int acc = 0; acc < 2; ++acc) one(gc, nb, 1, 0, -1, 0, 0, acc, 1, ncons);
+      for (int nb : {1, 4}) for (int acc = 0; acc < 2; ++acc) one(gc, nb, 1, 0, -1, 0, 0, acc, 1);
 }
 
 static void fused16() {

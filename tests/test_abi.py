@@ -85,7 +85,7 @@ def test_plan_selection(L):
 def test_workspace_sizes(L):
     assert L.workspace_bytes(64, 4096, 256, 128) >= 64 * 128 * 256 * 8     # grad slab at least
     al = lambda v: (v + 255) // 256 * 256
-    # direct plan: the 64 KiB sync area every layout starts with, three (B,k,D) complex spectra, the
+    # direct plan: the reserved 64 KiB header every layout starts with, three (B,k,D) complex spectra, the
     # LayerNorm-gradient partials of the block API
     assert L.workspace_bytes(2, 100, 8, 4) == 65536 + 3 * al(2 * 4 * 8 * 8) + al(50 * 2 * 8 * 4)
     L.set_option("nsplit", 4)
@@ -94,6 +94,24 @@ def test_workspace_sizes(L):
         assert L.workspace_bytes(64, 4096, 256, 128) > 64 * 8 * 4 * 32768
     finally:
         L.set_option("nsplit", 0)
+
+
+def test_retired_fold_gradw_option_is_accepted_and_changes_nothing(L):
+    """fold_gradw (the parameter-gradient reduction inside the backward launch) is retired: the option name and the
+    struct field stay for the ABI, a change still counts as a change of defaults, and no plan or workspace follows it."""
+    lib = L.lib()
+    shapes = [(64, 4096, 256, 128), (8, 1024, 64, 200)]
+    fields = [n for n, _ in L.smx_plan._fields_]
+    answers = lambda: [(tuple(getattr(L.plan(*s), n) for n in fields), L.workspace_bytes(*s)) for s in shapes]
+    assert "fold_gradw" in [n for n, _ in L.smx_options._fields_]
+    assert lib.smx_set_option(b"fold_gradw", 0) == 0
+    before, epoch = answers(), lib.smx_options_epoch()
+    try:
+        assert lib.smx_set_option(b"fold_gradw", 1) == 0
+        assert lib.smx_options_epoch() != epoch
+        assert answers() == before
+    finally:
+        lib.smx_set_option(b"fold_gradw", 0)
 
 
 def test_argument_validation_without_touching_the_gpu(L):

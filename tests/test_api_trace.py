@@ -43,7 +43,7 @@ PLAN_KERNELS = {
     "filter_pack": ["k_pack_w"],
     "row_scale": ["k_fs_gsc"],
     "2-byte rows": ["k_fused<1,", "k_split_a", "k_split_b"],
-    "options": ["memset ws+0", "k_fs_f_grouped"],
+    "options": ["k_gradw_slab", "k_fs_f_grouped"],      # (fold_gradw = 1, retired: the reduction launch of the default)
     "block entries": ["k_fused_blk", "k_ln_stats", "k_ln_apply", "k_add_rows", "k_ln_bwd", "k_ln_bwd_io", "k_ln_colsum"],
     "convolution": ["k_conv1<", "k_fs_conv<", "k_fs_conv_big", "k_conv_grads"],
     "cfft, phase filter, response": ["k_fs_f<4,3>", "k_fs_big", "k_phase_filter", "k_phase_filter_bwd", "k_conv_response",

@@ -166,10 +166,10 @@ def test_rank_one_conv_error_names_the_real_limits(gpu):
 @pytest.mark.parametrize("B,N,D,F", [(64, 4096, 256, 128), (16, 1024, 96, 40), (5, 512, 34, 17), (64, 1024, 512, 256),
                                      (130, 256, 64, 32)])
 def test_parameter_gradients_folded_into_the_backward_launch(gpu, B, N, D, F):
-    """VERDICT r2 #4a (option fold_gradw = 1, off by default -- measured slower, profiles/r03_fold_gradw_ab.txt): the
-    k_gradw reduction rides behind the transform workgroups of the same launch (appended reduction workgroups that
-    only wait for lower-numbered ones).  Same additions in the same order as the separate launch: bit-identical
-    gradients, run after run, and the sync area is left clean (second call equals the first)."""
+    """Compatibility pin of the RETIRED option fold_gradw (once: the k_gradw reduction behind the transform workgroups of
+    the backward launch; measured slower, profiles/r03_fold_gradw_ab.txt; VERDICT r2 #4a).  The option is still accepted
+    and gives the bits of the default -- the reduction is a launch of its own under either value -- run after run, and
+    the oracle's parameter gradients."""
     pkg, lib, fn = _pkg()
     assert lib.plan(B, N, D, F).nsplit == 1
     torch.manual_seed(B + N)
@@ -184,8 +184,8 @@ def test_parameter_gradients_folded_into_the_backward_launch(gpu, B, N, D, F):
             outs.setdefault(fold, []).append((gx.clone(), flat.clone()))
     (gx1, f1), (gx1b, f1b) = outs[1]
     (gx0, f0), = outs[0]
-    assert torch.equal(gx1, gx0) and torch.equal(f1, f0)          # folded == separate launch, bit for bit
-    assert torch.equal(gx1, gx1b) and torch.equal(f1, f1b)        # and reproducible (counters were left at zero)
+    assert torch.equal(gx1, gx0) and torch.equal(f1, f0)          # option set == default, bit for bit
+    assert torch.equal(gx1, gx1b) and torch.equal(f1, f1b)        # and reproducible
     xs, gs = x[:4].cpu().numpy(), g[:4].cpu().numpy()             # a sub-batch against the oracle
     with lib.options(fold_gradw=1):
         _, xk4 = fn.forward_raw(x[:4].contiguous(), wr, wi, bias, save_spectrum=True)
@@ -199,11 +199,11 @@ def test_parameter_gradients_folded_into_the_backward_launch(gpu, B, N, D, F):
 
 @pytest.mark.parametrize("other", ["rank_one_conv", "seq_fft", "dwconv3_backward", "spectral_gate_backward", "mix_backward"])
 def test_sync_area_survives_other_calls_on_the_shared_workspace(gpu, other):
-    """every workspace layout keeps its first 64 KiB for the flag words of the folded
-    parameter-gradient reduction -- the rank-one convolution and the complex sequence FFT used to start their scratch
-    at offset 0.  The autograd functions share ONE per-(device, stream) buffer and the layer's backward trusts the flag
-    words its forward left zero (SYNC_CLEAN): layer forward, then the other op on the same stream, then the layer's
-    backward must give the gradients of the unfolded reduction, bit for bit."""
+    """the autograd functions share ONE per-(device, stream) buffer, and the layer's backward runs on
+    the workspace of its forward.  Other ops interleaved on that buffer must not disturb it: layer forward, then the
+    other op on the same stream, then the layer's backward must give the same gradients, bit for bit, with the retired
+    option fold_gradw set (once the reader of flag words in the first 64 KiB of every layout, which stay reserved and
+    unused) as without it."""
     pkg, lib, fn = _pkg()
     B, N, D = 64, 1024, 256
     torch.manual_seed(7)
@@ -244,7 +244,7 @@ def test_sync_area_survives_other_calls_on_the_shared_workspace(gpu, other):
             return out
 
     ref = run(0)
-    for _ in range(2):                               # twice: the area must also be left clean
+    for _ in range(2):                               # twice: nothing is left behind in the shared buffer
         got = run(1)
         for a, b in zip(got, ref):
             assert torch.equal(a, b)

@@ -26,8 +26,6 @@ def main():
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--full", action="store_true", help="backward with PHASE_ALL (includes k_gradw)")
-    ap.add_argument("--clean", action="store_true", help="backward on a workspace of its own with sync_clean=True "
-                    "(what the autograd functions do: the library skips clearing the flag words)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     csrc = os.path.join(ROOT, "tensor-cuda-fft-_amd", "csrc")
@@ -57,7 +55,6 @@ def main():
         wr = torch.randn(D, F, device=dev); wi = torch.randn(D, F, device=dev); bias = torch.randn(D, device=dev)
         gx = torch.empty_like(g)
         flat = torch.empty(2 * D * F + D, device=dev)
-        wsb = torch.zeros(fn._ws_bytes(B, N, D, F), dtype=torch.uint8, device=dev)
         ph = fn.PHASE_ALL if args.full else (fn.PHASE_SPECTRUM | fn.PHASE_INVERSE)
         ref = None
         res = {n: {"fwd": [], "bwd": []} for n in names}
@@ -82,8 +79,7 @@ def main():
                 for key, f in (("fwd", lambda: fn.forward_raw(x, wr, wi, bias, save_spectrum=True, pack=pack,
                                                               pack_ready=pack is not None)),
                                ("bwd", lambda: fn.backward_raw(g, xk, wr, wi, phases=ph, grad_x=gx, flat=flat,
-                                                               pack=pack, ws=wsb if args.clean else None,
-                                                               sync_clean=args.clean))):
+                                                               pack=pack))):
                     f(); f()
                     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                            for _ in range(args.iters)]
