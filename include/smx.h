@@ -752,6 +752,43 @@ int smx_sample_bytes(const float* logits, long long row_stride, const void* rece
                      float frequency_penalty, int ascii_only, int ban_cr, int max_run_length, const float* u,
                      long long* ids, float* probs, long long R, int V, void* stream);
 
+/* The byte-spectral feature rows of fft_tensor's byte language model: what ByteSpectralEmbedding.forward
+ * (fft_tensor/byte_spectral_model.py:44-102) builds with a Python loop over all T positions -- roll, a full FFT, abs,
+ * angle, a multiply, sin, cos, cat and a pad per position, about ten launches each -- and ByteSpectralEncoder.forward
+ * (fft_tensor/byte_spectral.py:53-108) once per sequence, both up to their projection, as ONE launch.
+ *   tokens (B, T) as in smx_word_targets (token_bytes 1 = uint8 or 8 = int64, row_stride >= T elements between rows); ANY
+ *   int64 value is converted as the reference's .float() does.  s[t] = id[t] / 127.5 - 1, S[f] = sum_t s[t]
+ *   e^{-2 pi i f t / T}.  The spectrum of roll(s, -pos) is S[f] e^{i theta}, theta = 2 pi (f pos mod T) / T, so with
+ *   u = S / |S| column j of out[b, p, :] (pos = p; P = 1: pos = 0) is
+ *       0 <= j <  k     |S[b, j]| bands[j]
+ *       k <= j < 2k     Im(u[b, j - k] e^{i theta})          = sin(angle(spectrum of the rolled row))
+ *      2k <= j < 3k     Re(u[b, j - 2k] e^{i theta})         = cos(...)
+ *      3k <= j < W      0
+ *   cut at W columns.  A bin with S == 0 exactly has sin 0 and cos 1 at every position (torch's angle(0) = 0); nothing is
+ *   ever NaN.  out (B, P, W) float32, P = T (row p is position p: the embedding, k = min(W / 2, T / 2)) or P = 1 (the
+ *   encoder, W = 2 M, k = min(M, T / 2)); bands: at least k floats; mag (B, k), or NULL: |S|, what the backward needs.
+ *   Accuracy: every twiddle, the rotation included, is entry (f t mod T) -- the exact integer -- of one T-entry table
+ *   built by sincospi in double; the row enters as the integers 2 id - 255 (for f > 0 minus the row's mean rounded to an integer,
+ *   which changes no bin, keeps the partial sums small and makes a constant row an exact zero); each bin is summed over slices with four interleaved
+ *   accumulators and the slices joined pairwise.
+ *   One launch, no host synchronisation, capturable; a workgroup recomputes its row's k bins from the bytes in LDS and
+ *   writes a chunk of positions (16, more once B alone fills the chip; T > 512: at least T / 32) as 16-byte vectors when
+ *   W % 4 == 0.
+ *   smx_byte_supported(T, k, W) = 1 <= T <= 4096, 0 <= k <= min(T / 2, 2048), 1 <= W <= 4096 (no HIP call).
+ *   smx_byte_grad_bands  grad_bands[f] = sum_b sum_p g[b, p, f] mag[b, f] for f < min(k, W), 0 for min(k, W) <= f <
+ *   n_bands; g (B, P, W) dense.  Two plain launches: per (b, 64 rows) partials in the workspace
+ *   (smx_byte_workspace_bytes, 256-byte aligned), then their sum in index order: no atomics, bitwise reproducible.
+ * B, T, W, P <= 0 or k < 0, token_bytes other than 1 or 8, P other than 1 or T, k > T / 2, NULL required pointers,
+ * row_stride < T, misaligned int64 tokens, out not 16-byte aligned, n_bands < max(1, min(k, W)): SMX_ERR_INVALID; a size
+ * outside smx_byte_supported: SMX_ERR_UNSUPPORTED; a missing or short workspace: SMX_ERR_WORKSPACE.  Nothing is enqueued
+ * then, nothing is ever allocated, the host is never synchronised. */
+int smx_byte_supported(int T, int k, int W);
+int smx_byte_features(const void* tokens, int token_bytes, long long row_stride, const float* bands, float* out,
+                      float* mag, int B, int T, int k, int W, int P, void* stream);
+int smx_byte_workspace_bytes(int B, int P, int W, int k, size_t* out);
+int smx_byte_grad_bands(const float* g, const float* mag, float* grad_bands, int n_bands, void* workspace,
+                        size_t workspace_bytes, int B, int P, int W, int k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ from .wirtinger_ops import (ComplexParameter, WirtingerGradient, WirtingerSpectr
                             spectral_mix_with_filter)
 from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft, rfft_bins, seq_fft,
                          spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens, narrow_head,
-                         word_targets, cross_entropy, sample_bytes)
+                         word_targets, cross_entropy, sample_bytes, byte_features)
 from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
@@ -24,6 +24,7 @@ from .segmentation_head import SegmentationHead, SegmentedChunkLM, compute_segme
 from .dual_head import DualHead, TokenAwareChunkLM, compute_dual_loss, get_gpt2_tokenizer, get_token_ids_fast
 from .streaming import (LayerStream, StreamStates, generate_chunked, init_layer_states, stream_taps,
                         update_backbone_chunk)
+from .byte_spectral import ByteSpectralEmbedding, ByteSpectralEncoder, SpectralLanguageModel
 from .distributed import GradSync, attach_grad_sync, all_reduce_grads, shard_batch
 
 __all__ = [
@@ -40,6 +41,7 @@ __all__ = [
     "PhaseClockHead", "PhaseClockChunkLM", "generate_phase_targets", "compute_phase_clock_loss", "SegmentationHead",
     "SegmentedChunkLM", "get_word_boundaries", "compute_segmented_loss", "word_targets", "narrow_head",
     "DualHead", "TokenAwareChunkLM", "get_token_ids_fast", "compute_dual_loss", "get_gpt2_tokenizer", "cross_entropy",
-    "sample_bytes", "SampleConfig", "generate",
+    "sample_bytes", "SampleConfig", "generate", "ByteSpectralEmbedding", "ByteSpectralEncoder", "SpectralLanguageModel",
+    "byte_features",
 ]
 __version__ = "0.2.0"

@@ -152,6 +152,10 @@ _SIGS = {
     "smx_sample_supported": (_I, [_I]),
     "smx_sample_bytes": (_I, [_P, _LL, _P, _I, _I, ctypes.c_float, ctypes.c_float, _I] + [ctypes.c_float] * 3
                          + [_I] * 3 + [_P] * 3 + [_LL, _I, _P]),
+    "smx_byte_supported": (_I, [_I] * 3),
+    "smx_byte_features": (_I, [_P, _I, _LL, _P, _P, _P] + [_I] * 5 + [_P]),
+    "smx_byte_workspace_bytes": (_I, [_I] * 4 + [ctypes.POINTER(_SZ)]),
+    "smx_byte_grad_bands": (_I, [_P, _P, _P, _I, _P, _SZ] + [_I] * 4 + [_P]),
 }
 
 

@@ -587,6 +587,9 @@ DirectArgs direct_args(const Plan& p, const Tables& t, const Shape& h) {
 
 }  // namespace
 
+// what an entry point defined in another unit (smx_byte.hip) reports through smx_last_error()
+int smx::api_fail(int code, const char* text) { return fail(code, "%s", text); }
+
 extern "C" {
 
 int smx_version(void) { return SMX_VERSION; }

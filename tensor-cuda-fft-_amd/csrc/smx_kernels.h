@@ -383,4 +383,7 @@ hipError_t launch_sample_bytes(const float* logits, long long row_stride, const 
                                const SampleArgs& a, const float* u, long long* ids, float* probs, long long R,
                                hipStream_t s);
 
+// ---- byte-spectral features (smx_byte.hip: kernels AND their C entries; the error text goes through smx_api.hip) --------
+int api_fail(int code, const char* text);
+
 }  // namespace smx

@@ -2137,3 +2137,111 @@ def sample_bytes(logits: torch.Tensor, recent: Optional[torch.Tensor], u: Option
           a["frequency"], int(a["ascii_only"]), int(a["ban_cr"]), a["max_run"], u.data_ptr(), ids.data_ptr(), _ptr(probs),
           R, _SAMPLE_V, _stream(dev))
     return (ids.view(lead), probs.view(*lead, _SAMPLE_V)) if return_probs else ids.view(lead)
+
+
+# ---- byte-spectral feature rows: fft_tensor's byte language model (csrc/smx_byte.hip) ---------------------------------------
+
+@functools.lru_cache(None)
+def byte_supported(T: int, k: int, W: int) -> bool:
+    """smx_byte_supported: 1 <= T <= 4096, 0 <= k <= min(T / 2, 2048), 1 <= W <= 4096.  (A property of the library.)"""
+    return bool(_lib.lib().smx_byte_supported(int(T), int(k), int(W)))
+
+
+@functools.lru_cache(None)
+def _byte_ws_bytes(B: int, P: int, W: int, k: int) -> int:
+    return _query("smx_byte_workspace_bytes", B, P, W, k)
+
+
+class _ByteFeatures(torch.autograd.Function):
+    """The (B, P, W) feature rows of byte tokens through smx_byte_features; |S| (B, k) is kept when the band weights
+    want a gradient, which smx_byte_grad_bands forms in a fixed order.  The ids carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, tokens, bands, k, W, P):
+        B, T = tokens.shape
+        dev = tokens.device
+        out = torch.empty((B, P, W), dtype=torch.float32, device=dev)
+        mag = torch.empty((B, k), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] and k > 0 else None
+        _call(dev, "smx_byte_features", tokens.data_ptr(), tokens.element_size(), tokens.stride(0), bands.data_ptr(),
+              out.data_ptr(), _ptr(mag), B, T, k, W, P, _stream(dev))
+        ctx.dims = (B, P, W, k, bands.numel())
+        ctx.save_for_backward(mag)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        (mag,) = ctx.saved_tensors
+        B, P, W, k, n = ctx.dims
+        g = _grad_f32(g)
+        gb = torch.empty(n, dtype=torch.float32, device=g.device)
+        ws = _workspace(g.device, _byte_ws_bytes(B, P, W, k))
+        _call(g.device, "smx_byte_grad_bands", g.data_ptr(), _ptr(mag), gb.data_ptr(), n, *_ws_arg(ws), B, P, W, k,
+              _stream(g.device))
+        return None, gb, None, None, None
+
+
+def _byte_features_torch(tokens: torch.Tensor, bands: torch.Tensor, k: int, W: int, P: int) -> torch.Tensor:
+    """The same table as whole-tensor ops on the tokens' device (CPU tokens, sizes outside byte_supported): one float64
+    FFT of the rows and the shift theorem's rotation by the exact angle 2 pi (f pos mod T) / T -- never the per-position loop.
+    Differentiable in `bands` through autograd."""
+    B, T = tokens.shape
+    dev = tokens.device
+    if k == 0:
+        return torch.zeros((B, P, W), dtype=torch.float32, device=dev) + bands.sum() * 0
+    S = torch.fft.fft(tokens.to(torch.float32).double() / 127.5 - 1.0, dim=1)[:, :k]        # float64: rounded once, below
+    mag = S.abs()
+    zero = mag == 0
+    one = torch.ones((), dtype=S.dtype, device=dev)
+    u = torch.where(zero, one, S / torch.where(zero, torch.ones_like(mag), mag))
+    f = torch.arange(k, device=dev)
+    ang = ((f[None, :] * torch.arange(P, device=dev)[:, None]) % T).double() * (2.0 * torch.pi / T)
+    z = u[:, None, :] * torch.complex(torch.cos(ang), torch.sin(ang))[None]
+    z = torch.where(zero[:, None, :], one, z).to(torch.complex64)   # angle(0) = 0 at every position
+    feat = torch.cat(((mag.float() * bands[:k].to(torch.float32))[:, None, :].expand(B, P, k), z.imag, z.real), dim=-1)
+    if 3 * k < W:
+        return torch.nn.functional.pad(feat, (0, W - 3 * k))
+    return feat[..., :W].contiguous()
+
+
+def byte_features(tokens: torch.Tensor, bands: torch.Tensor, width: int, positions: bool = True,
+                  native: Optional[bool] = None) -> torch.Tensor:
+    """The feature rows of fft_tensor's byte models before their projection (reference
+    fft_tensor/byte_spectral_model.py:52-97 and fft_tensor/byte_spectral.py:63-98).  tokens (B, T) uint8 or int64 (any
+    int64 value, converted as .float() does); s = id / 127.5 - 1, S = fft(s), k = min(width // 2, T // 2).
+    positions=True: (B, T, width) fp32, row pos = [|S[:k]| bands[:k], sin, cos of angle(fft(roll(s, -pos))[:k]), zeros]
+    cut at `width` columns (ByteSpectralEmbedding); positions=False: (B, width), the row of pos = 0 (ByteSpectralEncoder).
+    On a ROCm device with byte_supported(T, k, width) it is ONE launch with no host synchronisation and a fixed-order
+    two-launch gradient for `bands`; elsewhere (CPU, T > 4096 ...) the same table as whole-tensor torch ops.  native=False
+    takes the torch ops on any device, native=True refuses to.  A bin whose |S| is tiny has phase columns that are
+    rounding noise in the reference and here alike.  The ids carry no gradient."""
+    if not (isinstance(tokens, torch.Tensor) and tokens.dtype in (torch.uint8, torch.int64) and tokens.dim() == 2):
+        raise TypeError("byte_features: tokens must be a (B, T) uint8 or int64 tensor")
+    if not (isinstance(bands, torch.Tensor) and bands.is_floating_point() and bands.dim() == 1):
+        raise TypeError("byte_features: bands must be a 1-D floating-point tensor")
+    W = int(width)
+    if W < 1:
+        raise ValueError(f"byte_features: width must be positive, got {width}")
+    B, T = tokens.shape
+    k = min(W // 2, T // 2)
+    if bands.numel() < k:
+        raise ValueError(f"byte_features: bands holds {bands.numel()} weights, {k} bins are kept")
+    if bands.device != tokens.device:
+        raise ValueError(f"byte_features: bands is on {bands.device}, tokens on {tokens.device}")
+    P = T if positions else 1
+    if B == 0 or T == 0:
+        out = torch.zeros((B, P, W), dtype=torch.float32, device=tokens.device)
+    else:
+        can = tokens.is_cuda and bands.dtype == torch.float32 and bands.numel() > 0 and byte_supported(T, k, W)
+        if native and not can:
+            raise ValueError(f"byte_features: no native launch for T={T}, k={k}, width={W} on {tokens.device}")
+        if can and native is not False:
+            if tokens.shape[1] > 1 and tokens.stride(1) != 1 or tokens.stride(0) < tokens.shape[1] \
+                    or tokens.data_ptr() % tokens.element_size():
+                tokens = tokens.contiguous()
+            out = _ByteFeatures.apply(tokens, _dense(bands), k, W, P)
+        else:
+            out = _byte_features_torch(tokens, bands, k, W, P)
+    return out if positions else out[:, 0, :]
