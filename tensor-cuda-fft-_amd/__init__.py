@@ -26,6 +26,8 @@ from .streaming import (LayerStream, StreamStates, generate_chunked, init_layer_
                         update_backbone_chunk)
 from .byte_spectral import ByteSpectralEmbedding, ByteSpectralEncoder, SpectralLanguageModel
 from .distributed import GradSync, attach_grad_sync, all_reduce_grads, shard_batch
+from .training import (TrainConfig, adaptive_cutoff, conv_freq_bins, curriculum_cutoff, jpeg_cutoff,
+                       lr_stage_params, make_val_starts, plateau_cutoff, sample_windows, sawtooth_lr)
 
 __all__ = [
     "SpectralMixingLayer", "SpectralMLPBlock", "HybridSpectralAttention", "ComplexParameter", "WirtingerGradient",
@@ -42,6 +44,8 @@ __all__ = [
     "SegmentedChunkLM", "get_word_boundaries", "compute_segmented_loss", "word_targets", "narrow_head",
     "DualHead", "TokenAwareChunkLM", "get_token_ids_fast", "compute_dual_loss", "get_gpt2_tokenizer", "cross_entropy",
     "sample_bytes", "SampleConfig", "generate", "ByteSpectralEmbedding", "ByteSpectralEncoder", "SpectralLanguageModel",
-    "byte_features",
+    "byte_features", "TrainConfig", "conv_freq_bins", "jpeg_cutoff",
+    "curriculum_cutoff", "adaptive_cutoff", "plateau_cutoff", "sawtooth_lr", "lr_stage_params", "make_val_starts",
+    "sample_windows",
 ]
 __version__ = "0.2.0"
