@@ -789,6 +789,30 @@ int smx_byte_workspace_bytes(int B, int P, int W, int k, size_t* out);
 int smx_byte_grad_bands(const float* g, const float* mag, float* grad_bands, int n_bands, void* workspace,
                         size_t workspace_bytes, int B, int P, int W, int k, void* stream);
 
+/* Multi-pattern exact byte search: the `corpus_bytes.find(snip)` loop of the trainer's parroting_score
+ * (fft_lm/train_fixed_full.py:185-205: one host scan of the whole corpus per absent snippet, up to 64 per epoch) as ONE
+ * pass over the corpus that tests all snippets at every position.
+ *   corpus: n bytes, ANY alignment.  snips: S snippets of L bytes each, contiguous (S, L).  first (S) int64:
+ *   first[s] = the smallest p in [0, n - L] with corpus[p : p + L] == snips[s], -1 if there is none -- bytes.find.
+ *   Identical snippets each get their answer.  n < L (n == 0 too, corpus may then be NULL): every answer is -1, still
+ *   written on the stream.
+ *   Two launches: persistent workgroups walk 16384-position tiles (aligned to 16-byte addresses; 16-byte loads for
+ *   every vector wholly inside the corpus, byte loads at its two ends, nothing outside [corpus, corpus + n) and
+ *   [snips, snips + S L) is read), test each position's 4-byte window against an LDS bitmap of the snippets' hashed first
+ *   words and verify hits from LDS; each workgroup's minima go to its row of a table in the workspace, and a second
+ *   launch takes the column minima (one workgroup per snippet).  No flag words, no atomics on memory, no workgroup waits for another:
+ *   the result is a pure function of the inputs, bitwise reproducible.  max_workgroups: 0 = as many as stay resident,
+ *   n > 0 caps the scan at n workgroups (tests force the tile walk with 1 or 2).
+ *   smx_match_supported(S, L) = 1 <= S <= 256, 4 <= L <= 256, S L <= 32768 (no HIP call).
+ * A set outside smx_match_supported: SMX_ERR_UNSUPPORTED; n < 0, NULL snips / first / (n > 0) corpus, first not 8-byte
+ * aligned, max_workgroups < 0: SMX_ERR_INVALID; a missing, short or unaligned workspace (smx_match_workspace_bytes,
+ * 256-byte aligned): SMX_ERR_WORKSPACE.  Nothing is enqueued then, nothing is ever allocated, the host is never
+ * synchronised; the call can be captured in a graph. */
+int smx_match_supported(int S, int L);
+int smx_match_workspace_bytes(int S, int L, size_t* out);
+int smx_match_first(const void* corpus, long long n, const void* snips, int S, int L, long long* first, void* workspace,
+                    size_t workspace_bytes, int max_workgroups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ from .wirtinger_ops import (ComplexParameter, WirtingerGradient, WirtingerSpectr
                             spectral_mix_with_filter)
 from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft, rfft_bins, seq_fft,
                          spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens, narrow_head,
-                         word_targets, cross_entropy, sample_bytes, byte_features)
+                         word_targets, cross_entropy, sample_bytes, byte_features, find_snippets)
 from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
@@ -26,8 +26,10 @@ from .streaming import (LayerStream, StreamStates, generate_chunked, init_layer_
                         update_backbone_chunk)
 from .byte_spectral import ByteSpectralEmbedding, ByteSpectralEncoder, SpectralLanguageModel
 from .distributed import GradSync, attach_grad_sync, all_reduce_grads, shard_batch
-from .training import (TrainConfig, adaptive_cutoff, conv_freq_bins, curriculum_cutoff, jpeg_cutoff,
-                       lr_stage_params, make_val_starts, plateau_cutoff, sample_windows, sawtooth_lr)
+from .training import (TrainConfig, adaptive_cutoff, checkpoint_state, config_from_checkpoint, conv_freq_bins,
+                       curriculum_cutoff, eval_loss, jpeg_cutoff, load_checkpoint, load_corpus_as_u8, load_state_flexible,
+                       lr_stage_params, make_val_starts, parroting_picks, parroting_score, plateau_cutoff, sample_windows,
+                       save_checkpoint, sawtooth_lr, verify_checkpoint)
 
 __all__ = [
     "SpectralMixingLayer", "SpectralMLPBlock", "HybridSpectralAttention", "ComplexParameter", "WirtingerGradient",
@@ -46,6 +48,8 @@ __all__ = [
     "sample_bytes", "SampleConfig", "generate", "ByteSpectralEmbedding", "ByteSpectralEncoder", "SpectralLanguageModel",
     "byte_features", "TrainConfig", "conv_freq_bins", "jpeg_cutoff",
     "curriculum_cutoff", "adaptive_cutoff", "plateau_cutoff", "sawtooth_lr", "lr_stage_params", "make_val_starts",
-    "sample_windows",
+    "sample_windows", "find_snippets", "load_corpus_as_u8", "eval_loss", "parroting_picks", "parroting_score",
+    "save_checkpoint", "verify_checkpoint", "load_checkpoint", "checkpoint_state", "config_from_checkpoint",
+    "load_state_flexible",
 ]
 __version__ = "0.2.0"

@@ -156,6 +156,9 @@ _SIGS = {
     "smx_byte_features": (_I, [_P, _I, _LL, _P, _P, _P] + [_I] * 5 + [_P]),
     "smx_byte_workspace_bytes": (_I, [_I] * 4 + [ctypes.POINTER(_SZ)]),
     "smx_byte_grad_bands": (_I, [_P, _P, _P, _I, _P, _SZ] + [_I] * 4 + [_P]),
+    "smx_match_supported": (_I, [_I, _I]),
+    "smx_match_workspace_bytes": (_I, [_I, _I, ctypes.POINTER(_SZ)]),
+    "smx_match_first": (_I, [_P, _LL, _P, _I, _I, _P, _P, _SZ, _I, _P]),
 }
 
 

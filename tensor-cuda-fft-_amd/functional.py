@@ -2245,3 +2245,62 @@ def byte_features(tokens: torch.Tensor, bands: torch.Tensor, width: int, positio
         else:
             out = _byte_features_torch(tokens, bands, k, W, P)
     return out if positions else out[:, 0, :]
+
+
+# ---- multi-pattern exact byte search: the corpus scan of the parroting score (csrc/smx_match.hip) ---------------------------
+
+@functools.lru_cache(None)
+def match_supported(S: int, L: int) -> bool:
+    """smx_match_supported: 1 <= S <= 256, 4 <= L <= 256, S * L <= 32768.  (A property of the library.)"""
+    return bool(_lib.lib().smx_match_supported(int(S), int(L)))
+
+
+@functools.lru_cache(None)
+def _match_ws_bytes(S: int, L: int) -> int:
+    return _query("smx_match_workspace_bytes", S, L)
+
+
+def _find_snippets_host(corpus: bytes, snips: bytes, S: int, L: int) -> list:
+    """the definition: bytes.find per snippet"""
+    return [corpus.find(snips[s * L:(s + 1) * L]) for s in range(S)]
+
+
+def _host_bytes(t) -> bytes:
+    return t if isinstance(t, bytes) else t.detach().contiguous().cpu().numpy().tobytes()
+
+
+def find_snippets(corpus_u8, snips_u8: torch.Tensor, *, max_workgroups: int = 0) -> torch.Tensor:
+    """first (S,) int64 on the snippets' device: first[s] = the smallest p with corpus[p : p + L] == snips[s], -1 when the
+    snippet does not occur -- `bytes.find` for S snippets of L bytes at once, the scan of the reference's parroting_score
+    (fft_lm/train_fixed_full.py:200-204, one host pass over the corpus per absent snippet).
+    corpus_u8: a 1-D uint8 tensor or `bytes`; snips_u8: (S, L) uint8.  A corpus on a ROCm device with
+    match_supported(S, L) is ONE pass over the corpus (smx_match_first: no host synchronisation, nothing allocated beside
+    the answer, capturable, bitwise reproducible; a view at any byte offset is read in place, a strided one is made
+    contiguous).  A CPU or `bytes` corpus, and any other (S, L), compute the same definition with bytes.find on the
+    host.  max_workgroups (> 0) caps the native scan's workgroups: a test and tuning knob."""
+    if not (isinstance(snips_u8, torch.Tensor) and snips_u8.dtype == torch.uint8 and snips_u8.dim() == 2):
+        raise TypeError("find_snippets: snips_u8 must be an (S, L) uint8 tensor")
+    if not isinstance(corpus_u8, bytes) and not (isinstance(corpus_u8, torch.Tensor) and corpus_u8.dtype == torch.uint8
+                                                  and corpus_u8.dim() == 1):
+        raise TypeError("find_snippets: corpus_u8 must be a 1-D uint8 tensor or bytes")
+    S, L = snips_u8.shape
+    if L < 1:
+        raise ValueError("find_snippets: snippets must hold at least one byte")
+    if max_workgroups < 0:
+        raise ValueError(f"find_snippets: max_workgroups must not be negative, got {max_workgroups}")
+    if S == 0:
+        return torch.empty(0, dtype=torch.int64, device=snips_u8.device)
+    if isinstance(corpus_u8, bytes) or not corpus_u8.is_cuda or not match_supported(S, L):
+        first = _find_snippets_host(_host_bytes(corpus_u8), _host_bytes(snips_u8), S, L)
+        return torch.tensor(first, dtype=torch.int64, device=snips_u8.device)
+    dev = corpus_u8.device
+    _require("corpus_u8", corpus_u8, (torch.uint8,), _ANY_PATH, what="a 1-D uint8 tensor", dim=1)
+    if snips_u8.device != dev:
+        raise ValueError(f"find_snippets: snips_u8 is on {snips_u8.device}, corpus_u8 on {dev}")
+    _require("snips_u8", snips_u8, (torch.uint8,), _ANY_PATH, what="an (S, L) uint8 tensor", dim=2)
+    corpus, snips = corpus_u8.contiguous(), snips_u8.contiguous()
+    first = torch.empty(S, dtype=torch.int64, device=dev)
+    ws = _workspace(dev, _match_ws_bytes(S, L))
+    _call(dev, "smx_match_first", corpus.data_ptr() if corpus.numel() else None, corpus.numel(), snips.data_ptr(), S, L,
+          first.data_ptr(), *_ws_arg(ws), int(max_workgroups), _stream(dev))
+    return first

@@ -1,14 +1,23 @@
 """The training loop pieces of the reference's trainer (fft_lm/train_fixed_full.py: TrainConfig :34-105, the cutoff and
-learning-rate schedules :129-147 and :208-424, the window sampling and the optimizer step of its loop :897-959), written
-against its behaviour: a config with the same fields and defaults, the same schedule values, and the window sampling as
-one gather.  Out of scope: eval_loss, parroting_score, checkpoint I/O, the CLIs and load_corpus_as_u8.
+learning-rate schedules :129-147 and :208-424, the window sampling of its loop :897-959), written against its behaviour:
+a config with the same fields and defaults, the same schedule values, and the window sampling as one gather -- and what
+the trainer runs at the end of every epoch (scripts/eval_ckpt.py runs the same on a saved model): load_corpus_as_u8
+:115-126, eval_loss :150-182, parroting_score :185-205 on one native corpus scan (functional.find_snippets), the
+checkpoint I/O of fft_lm/ckpt_io.py and the resume logic of main() (:824-893).  Out of scope: the CLIs and the optimizer
+step.
 """
 from __future__ import annotations
 
+import hashlib
 import math
+import os
 from dataclasses import dataclass
+from typing import Any
 
+import numpy as np
 import torch
+
+from .functional import cross_entropy, find_snippets
 
 
 @dataclass
@@ -184,3 +193,150 @@ def sample_windows(corpus_u8: torch.Tensor, starts: torch.Tensor, seq_len: int) 
         + torch.arange(seq_len + 1, device=corpus_u8.device).unsqueeze(0)
     w = corpus_u8[idx].to(torch.long)
     return w[:, :-1].contiguous(), w[:, 1:].contiguous()
+
+
+# ---- the end of an epoch: validation loss, parroting score, checkpoints ---------------------------------------------------
+
+def load_corpus_as_u8(path: str, *, sanitize_ascii: bool, device=None) -> torch.Tensor:
+    """The file's bytes as a 1-D uint8 tensor (reference :115-126); sanitize_ascii keeps \\n and printable ASCII and turns
+    every other byte into a space.  `device` places the result (None: the CPU, as the reference)."""
+    with open(path, "rb") as f:
+        arr = np.frombuffer(f.read(), dtype=np.uint8)
+    if sanitize_ascii:
+        keep = (arr == 10) | ((arr >= 32) & (arr <= 126))
+        arr = np.where(keep, arr, 32).astype(np.uint8)
+    out = torch.from_numpy(arr.copy())
+    return out if device is None else out.to(device)
+
+
+@torch.no_grad()
+def eval_loss(model, corpus_u8: torch.Tensor, starts: torch.Tensor, cfg, cutoff) -> float:
+    """Mean cross-entropy over val_batches full batches of the fixed validation windows `starts` (reference :150-182): one
+    torch.randperm(starts.numel()) draw from the global CPU generator picks the windows, so the same seed picks the
+    reference's.  The windows are gathered on the corpus's device (sample_windows) and copied only when the model lives
+    elsewhere; the per-batch losses (the native cross_entropy on a ROCm device) stay on the device and are averaged in
+    float64 and read once at the end, where the reference reads one per batch.  Leaves the model in eval mode; 0.0 when
+    `starts` holds no full batch."""
+    model.eval()
+    bs = int(cfg.batch_size)
+    idx = torch.randperm(starts.numel())[: int(cfg.val_batches) * bs]
+    sel = starts[idx.to(starts.device)]
+    n_batches = sel.numel() // bs
+    if n_batches == 0:
+        return 0.0
+    dev = next(model.parameters()).device
+    losses = []
+    for i in range(n_batches):
+        x, y = sample_windows(corpus_u8, sel[i * bs:(i + 1) * bs], int(cfg.seq_len))
+        if x.device != dev:
+            x, y = x.to(dev, non_blocking=True), y.to(dev, non_blocking=True)
+        losses.append(cross_entropy(model(x, cutoff=cutoff), y))        # F.cross_entropy on the CPU
+    return float(torch.stack(losses).double().mean().item())
+
+
+def parroting_picks(n_gen: int, cfg) -> np.ndarray:
+    """The snippet starts the reference's parroting_score draws from a generation of n_gen bytes (:190-199): every
+    parroting_stride-th start after the first 32 bytes, at most parroting_snips of them chosen without replacement by
+    np.random.default_rng(123).  Empty when the generation is shorter than a snippet plus one byte."""
+    L = int(cfg.parroting_snip_len)
+    if n_gen < L + 1:
+        return np.empty(0, np.int64)
+    candidates = list(range(min(32, n_gen - L), n_gen - L, int(cfg.parroting_stride)))
+    if not candidates:
+        return np.empty(0, np.int64)
+    rng = np.random.default_rng(123)
+    return rng.choice(candidates, size=min(int(cfg.parroting_snips), len(candidates)), replace=False)
+
+
+def parroting_score(corpus, gen_bytes: bytes, cfg) -> float:
+    """Fraction of the picked parroting_snip_len-byte snippets of `gen_bytes` that occur verbatim in the corpus (reference
+    :185-205; 0 = novel, 1 = copied).  `corpus`: bytes, a CPU uint8 tensor or a uint8 tensor on a ROCm device; the last
+    is searched by ONE native pass for all snippets (find_snippets) where the reference scans the corpus once per
+    snippet on the host.  The answers are read once."""
+    picks = parroting_picks(len(gen_bytes), cfg)
+    if picks.size == 0:
+        return 0.0
+    L = int(cfg.parroting_snip_len)
+    gen = np.frombuffer(gen_bytes, dtype=np.uint8)
+    snips = torch.from_numpy(gen[picks[:, None] + np.arange(L)[None, :]])
+    if isinstance(corpus, torch.Tensor):
+        snips = snips.to(corpus.device)
+    hits = int((find_snippets(corpus, snips) >= 0).sum().item())
+    return hits / float(len(picks))
+
+
+def _sha256_file(path: str) -> str:
+    h = hashlib.sha256()
+    with open(path, "rb") as f:
+        for chunk in iter(lambda: f.read(1024 * 1024), b""):
+            h.update(chunk)
+    return h.hexdigest()
+
+
+def save_checkpoint(obj: Any, path: str) -> None:
+    """torch.save and the file's SHA-256 in `path`.sha256 beside it (reference fft_lm/ckpt_io.py:40-45)."""
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    torch.save(obj, path)
+    with open(path + ".sha256", "w", encoding="utf-8") as f:
+        f.write(_sha256_file(path) + "\n")
+
+
+def verify_checkpoint(path: str) -> bool:
+    """True when `path` matches its .sha256 sidecar, False when there is none; a mismatch raises (ckpt_io.py:48-59)."""
+    sha = path + ".sha256"
+    if not os.path.exists(sha):
+        return False
+    with open(sha, "r", encoding="utf-8") as f:
+        expected = f.read().strip().splitlines()[0]
+    actual = _sha256_file(path)
+    if expected != actual:
+        raise RuntimeError(f"Checkpoint integrity check failed for {path}. "
+                           f"Expected sha256={expected}, got sha256={actual}.")
+    return True
+
+
+def load_checkpoint(path: str, *, map_location="cpu") -> Any:
+    """verify_checkpoint, then torch.load (pickle inside: only load files you wrote; ckpt_io.py:62-66)."""
+    verify_checkpoint(path)
+    return torch.load(path, map_location=map_location)
+
+
+def checkpoint_state(model, opt, scaler, cfg, epoch: int) -> dict:
+    """The dict the trainer saves (reference :883-893): epoch, model, opt, scaler (None without cfg.amp) and the config's
+    fields.  `opt` and `scaler` may be None."""
+    return {"epoch": epoch, "model": model.state_dict(), "opt": None if opt is None else opt.state_dict(),
+            "scaler": scaler.state_dict() if scaler is not None and cfg.amp else None, "cfg": dict(cfg.__dict__)}
+
+
+def config_from_checkpoint(ckpt: dict, cfg=None):
+    """`cfg` (default: a fresh TrainConfig) with every field the checkpoint's saved config also has set from it; keys the
+    config does not know are ignored (scripts/eval_ckpt.py:50-54)."""
+    cfg = TrainConfig() if cfg is None else cfg
+    if "cfg" in ckpt and isinstance(ckpt["cfg"], dict):
+        for k, v in ckpt["cfg"].items():
+            if hasattr(cfg, k):
+                setattr(cfg, k, v)
+    return cfg
+
+
+def load_state_flexible(model, state: dict) -> tuple:
+    """(resized, skipped): load a state dict whose tensors partly changed shape, e.g. after a seq_len change (reference
+    :824-850).  Only 1-D `*gate_freq_logits` are resized (the common prefix is copied, the rest keeps the model's values);
+    every other mismatch is skipped, unknown keys are ignored.  Both lists hold (key, saved shape, model shape)."""
+    cur = model.state_dict()
+    to_load, resized, skipped = {}, [], []
+    for k, v in state.items():
+        if k not in cur:
+            continue
+        if cur[k].shape == v.shape:
+            to_load[k] = v
+        elif k.endswith("gate_freq_logits") and v.ndim == 1 and cur[k].ndim == 1:
+            tgt = cur[k].clone()
+            n = min(tgt.numel(), v.numel())
+            tgt[:n] = v[:n]
+            to_load[k] = tgt
+            resized.append((k, tuple(v.shape), tuple(tgt.shape)))
+        else:
+            skipped.append((k, tuple(v.shape), tuple(cur[k].shape)))
+    model.load_state_dict(to_load, strict=False)
+    return resized, skipped
