@@ -813,6 +813,40 @@ int smx_match_workspace_bytes(int S, int L, size_t* out);
 int smx_match_first(const void* corpus, long long n, const void* snips, int S, int L, long long* first, void* workspace,
                     size_t workspace_bytes, int max_workgroups, void* stream);
 
+/* The two native ops of the sparse spectral tensor (fft_tensor/tensor.py:136-144 _sparsify_pytorch: abs, topk, >=,
+ * nonzero, masked gather; fft_tensor/tensor.py:194-203 _scatter_pytorch: fill + index_put; the extension that
+ * fft_tensor/setup.py:20-49 declares for them was never written).  For n complex64 values z[i] = (re, im), 8-byte aligned at any 8-byte offset:
+ *   key[i] = bits(fl(fl(re re) + fl(im im))) & 0x7fffffff   (fp32, round to nearest, no FMA), compared as unsigned;
+ *   T = the k-th largest key (1 <= k <= n); kept = {i : key[i] >= T}: m >= k, ties at T are all kept; a NaN key ranks
+ *   above inf.
+ * smx_topk_select: an exact radix select over the 31 key bits in three passes over z (digits of 11, 10, 10 bits: LDS
+ *   histograms per workgroup, rows in the workspace, a column-sum launch and a one-workgroup pick per pass), then the
+ *   kept elements are counted per 4096-element tile (a fourth pass) and the counts scanned.  result (2 int64 on the
+ *   device): result[0] = m, result[1] = T.
+ * smx_topk_compact: one more pass writes the first min(m, capacity) kept elements in ascending index order (the order
+ *   of torch.nonzero): coeffs[j] (complex64) and flat_idx[j] (int64).  It reads `result` and the tile offsets that the
+ *   preceding smx_topk_select of the same z and n left in the same workspace (any max_workgroups: offsets are per tile).
+ * smx_sparse_scatter: out (n complex64, 16-byte aligned) = zeros with out[flat_idx[j]] = coeffs[j], j < m, in ONE launch
+ *   that writes `out` exactly once with 16-byte stores (tiles built in LDS; each workgroup finds its first entry by binary
+ *   search) and reads nothing of size n.  flat_idx must be strictly ascending and in [0, n): the caller's promise.  If it
+ *   is broken the contents of `out` are unspecified, but nothing outside `out` is written.  m = 0 (coeffs and flat_idx
+ *   may then be NULL) is a plain fill.
+ * No flag words, no atomics on memory, no workgroup waits for another: every result is a pure function of the inputs,
+ * bitwise reproducible.  max_workgroups: 0 = as many as stay resident, n > 0 caps every tile walk at n workgroups
+ * (tests force the walk with 1 or 2).  smx_topk_supported(n) = 1 <= n < 2^31 (no HIP call).
+ * n outside smx_topk_supported: SMX_ERR_UNSUPPORTED; NULL pointers, k outside 1..n, m outside 0..n, capacity < 0,
+ * max_workgroups < 0, z / result / coeffs / flat_idx not 8-byte or out not 16-byte aligned: SMX_ERR_INVALID; a missing,
+ * short or unaligned workspace (smx_topk_workspace_bytes, 256-byte aligned): SMX_ERR_WORKSPACE.  Nothing is enqueued
+ * then, nothing is ever allocated, the host is never synchronised; the calls can be captured in a graph. */
+int smx_topk_supported(long long n);
+int smx_topk_workspace_bytes(long long n, size_t* out);
+int smx_topk_select(const void* z, long long n, long long k, long long* result, void* workspace, size_t workspace_bytes,
+                    int max_workgroups, void* stream);
+int smx_topk_compact(const void* z, long long n, const long long* result, void* coeffs, long long* flat_idx,
+                     long long capacity, void* workspace, size_t workspace_bytes, int max_workgroups, void* stream);
+int smx_sparse_scatter(const void* coeffs, const long long* flat_idx, long long m, void* out, long long n,
+                       int max_workgroups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,11 +9,14 @@ from .wirtinger_ops import (ComplexParameter, WirtingerGradient, WirtingerSpectr
                             spectral_mix_with_filter)
 from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft, rfft_bins, seq_fft,
                          spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens, narrow_head,
-                         word_targets, cross_entropy, sample_bytes, byte_features, find_snippets)
+                         word_targets, cross_entropy, sample_bytes, byte_features, find_snippets, sparsify_topk,
+                         sparse_scatter, fftn, ifftn)
 from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
-from .frequency_ops import FrequencyAttention
+from .frequency_ops import FrequencyAttention, FrequencyMatMul
+from .sparse_tensor import MemoryManager, SparseSpectralTensor, randn_sst, sst, zeros_sst
+from .ops import spectral_activation, spectral_normalize, spectral_pool
 from .fixed_spectral import (FixedSpectralBlock, FixedSpectralLM, FrequencyConvFunc, LMConfig, SampleConfig,
                              causal_spectral_conv, generate)
 from .frequency_native import BicameralBlock, FrequencyNativeBlock, PhaseShift, SpectralFFN, SpectralLayerNorm
@@ -50,6 +53,7 @@ __all__ = [
     "curriculum_cutoff", "adaptive_cutoff", "plateau_cutoff", "sawtooth_lr", "lr_stage_params", "make_val_starts",
     "sample_windows", "find_snippets", "load_corpus_as_u8", "eval_loss", "parroting_picks", "parroting_score",
     "save_checkpoint", "verify_checkpoint", "load_checkpoint", "checkpoint_state", "config_from_checkpoint",
-    "load_state_flexible",
+    "load_state_flexible", "SparseSpectralTensor", "MemoryManager", "sst", "zeros_sst", "randn_sst", "sparsify_topk",
+    "sparse_scatter", "fftn", "ifftn", "spectral_normalize", "spectral_activation", "spectral_pool", "FrequencyMatMul",
 ]
 __version__ = "0.2.0"

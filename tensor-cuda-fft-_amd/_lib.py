@@ -159,6 +159,11 @@ _SIGS = {
     "smx_match_supported": (_I, [_I, _I]),
     "smx_match_workspace_bytes": (_I, [_I, _I, ctypes.POINTER(_SZ)]),
     "smx_match_first": (_I, [_P, _LL, _P, _I, _I, _P, _P, _SZ, _I, _P]),
+    "smx_topk_supported": (_I, [_LL]),
+    "smx_topk_workspace_bytes": (_I, [_LL, ctypes.POINTER(_SZ)]),
+    "smx_topk_select": (_I, [_P, _LL, _LL, _P, _P, _SZ, _I, _P]),
+    "smx_topk_compact": (_I, [_P, _LL, _P, _P, _P, _LL, _P, _SZ, _I, _P]),
+    "smx_sparse_scatter": (_I, [_P, _P, _LL, _P, _LL, _I, _P]),
 }
 
 

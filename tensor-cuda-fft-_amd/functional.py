@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import math
 import warnings
 from typing import Optional
 
@@ -2304,3 +2305,144 @@ def find_snippets(corpus_u8, snips_u8: torch.Tensor, *, max_workgroups: int = 0)
     _call(dev, "smx_match_first", corpus.data_ptr() if corpus.numel() else None, corpus.numel(), snips.data_ptr(), S, L,
           first.data_ptr(), *_ws_arg(ws), int(max_workgroups), _stream(dev))
     return first
+
+
+# ---- sparse spectral tensor: top-k sparsify, scatter and the N-D transform (csrc/smx_sst.hip) -----------------------------------
+
+@functools.lru_cache(None)
+def topk_supported(n: int) -> bool:
+    """smx_topk_supported: 1 <= n < 2**31.  (A property of the library.)"""
+    return bool(_lib.lib().smx_topk_supported(int(n)))
+
+
+@functools.lru_cache(512)
+def _topk_ws_bytes(n: int) -> int:
+    return _query("smx_topk_workspace_bytes", n)
+
+
+def _squared_keys(flat: torch.Tensor) -> torch.Tensor:
+    """key = bits(fl(fl(re re) + fl(im im))) & 0x7fffffff as int32 (never negative, so signed order = unsigned order):
+    three whole-tensor fp32 ops, each rounded once, no FMA."""
+    ri = torch.view_as_real(flat)
+    re, im = ri[..., 0], ri[..., 1]
+    return (re * re + im * im).view(torch.int32) & 0x7fffffff
+
+
+def _sparsify_torch(flat: torch.Tensor, k: int):
+    """the definition of sparsify_topk with whole-tensor torch ops"""
+    keys = _squared_keys(flat.detach())
+    t = torch.kthvalue(keys, keys.numel() - k + 1).values           # the k-th largest key
+    idx = torch.nonzero(keys >= t).flatten()
+    return flat[idx], idx
+
+
+def sparsify_topk(freq: torch.Tensor, sparsity: Optional[float] = None, *, k: Optional[int] = None,
+                  max_workgroups: int = 0):
+    """(coeffs (m,) complex64, flat_indices (m,) int64): the elements of the flattened complex64 `freq` whose squared
+    magnitude is at least the k-th largest one, in ascending index order -- the reference's _sparsify_pytorch
+    (fft_tensor/tensor.py:136-144: abs, topk, >=, nonzero, masked gather) without the sort and the four extra passes.
+    k = max(1, int(numel * sparsity)), the reference's expression, or `k` itself.  Ties at the threshold are all kept
+    (m >= k), as the reference's `magnitude >= threshold` keeps them; the order is that of the key
+    bits(fl(fl(re re) + fl(im im))) & 0x7fffffff in fp32, so a NaN ranks above inf, and two magnitudes that torch.abs
+    tells apart in the last bit may tie or swap here.
+    On a ROCm device: smx_topk_select (an exact radix select, three passes over the spectrum, plus one that counts), ONE
+    host read of m (the reference's nonzero synchronises too), smx_topk_compact into exactly sized outputs; bitwise
+    reproducible.  CPU tensors, numel >= 2**31 and inputs that require grad compute the same definition with
+    whole-tensor torch ops.  Not differentiable (as in the reference): the native path builds no graph; on the torch path
+    the gather carries a gradient as any indexing does.  max_workgroups (> 0) caps the native tile walks: a test and
+    tuning knob."""
+    if not (isinstance(freq, torch.Tensor) and freq.dtype == torch.complex64):
+        raise TypeError("sparsify_topk: freq must be a complex64 tensor")
+    n = freq.numel()
+    if n == 0:
+        raise ValueError("sparsify_topk: freq is empty")
+    if (sparsity is None) == (k is None):
+        raise ValueError("sparsify_topk: give exactly one of sparsity and k")
+    k = max(1, int(n * sparsity)) if k is None else int(k)
+    if k < 1 or k > n:
+        raise ValueError(f"sparsify_topk: k must be in 1..numel, got k={k} numel={n}")
+    if max_workgroups < 0:
+        raise ValueError(f"sparsify_topk: max_workgroups must not be negative, got {max_workgroups}")
+    flat = freq.resolve_conj().contiguous().view(-1)             # complex64 storage is 8-byte aligned at any offset
+    if not flat.is_cuda or flat.requires_grad or not topk_supported(n):
+        return _sparsify_torch(flat, k)
+    dev = flat.device
+    result = torch.empty(2, dtype=torch.int64, device=dev)          # m, threshold key
+    ws = _workspace(dev, _topk_ws_bytes(n))
+    _call(dev, "smx_topk_select", flat.data_ptr(), n, k, result.data_ptr(), *_ws_arg(ws), int(max_workgroups), _stream(dev))
+    m = int(result[0].item())
+    coeffs = torch.empty(m, dtype=torch.complex64, device=dev)
+    idx = torch.empty(m, dtype=torch.int64, device=dev)
+    _call(dev, "smx_topk_compact", flat.data_ptr(), n, result.data_ptr(), coeffs.data_ptr(), idx.data_ptr(), m,
+          *_ws_arg(ws), int(max_workgroups), _stream(dev))       # the workspace is as smx_topk_select left it
+    return coeffs, idx
+
+
+def sparse_scatter(coeffs: torch.Tensor, flat_indices: torch.Tensor, shape, *, assume_ascending: bool = False,
+                   max_workgroups: int = 0) -> torch.Tensor:
+    """A complex64 tensor of `shape`: zeros with flat[flat_indices[j]] = coeffs[j] -- the reference's _scatter_pytorch
+    (fft_tensor/tensor.py:194-203).  On a ROCm device with assume_ascending=True (the caller's promise that
+    flat_indices is strictly ascending and inside [0, numel): what sparsify_topk returns) it is ONE native launch that
+    writes the output exactly once (smx_sparse_scatter; a broken promise gives unspecified contents, nothing else).
+    Otherwise zeros + index_put_.  Not differentiable on the native path (coeffs that require grad take the torch ops)."""
+    if not (isinstance(coeffs, torch.Tensor) and coeffs.dtype == torch.complex64 and coeffs.dim() == 1):
+        raise TypeError("sparse_scatter: coeffs must be a 1-D complex64 tensor")
+    if not (isinstance(flat_indices, torch.Tensor) and flat_indices.dtype == torch.int64
+            and flat_indices.shape == coeffs.shape):
+        raise TypeError("sparse_scatter: flat_indices must be an int64 tensor of coeffs' length")
+    if flat_indices.device != coeffs.device:
+        raise ValueError(f"sparse_scatter: flat_indices is on {flat_indices.device}, coeffs on {coeffs.device}")
+    if max_workgroups < 0:
+        raise ValueError(f"sparse_scatter: max_workgroups must not be negative, got {max_workgroups}")
+    shape = tuple(int(s) for s in shape)
+    n, m = math.prod(shape), coeffs.numel()
+    if coeffs.is_cuda and assume_ascending and not coeffs.requires_grad and m <= n and n > 0 and topk_supported(n):
+        dev = coeffs.device
+        out = torch.empty(shape, dtype=torch.complex64, device=dev)
+        c, i = coeffs.resolve_conj().contiguous(), flat_indices.contiguous()
+        _call(dev, "smx_sparse_scatter", c.data_ptr() if m else None, i.data_ptr() if m else None, m, out.data_ptr(), n,
+              int(max_workgroups), _stream(dev))
+        return out
+    out = torch.zeros(n, dtype=torch.complex64, device=coeffs.device)
+    out.index_put_((flat_indices,), coeffs)
+    return out.reshape(shape)
+
+
+def _axis_walk(z: torch.Tensor, fft1d) -> torch.Tensor:
+    """The N-D DFT of `z` as 1-D transforms along each axis in turn.  Axis i of a contiguous tensor is the middle axis
+    of the view (prod(shape[:i]), shape[i], prod(shape[i+1:])), so nothing is transposed; `fft1d` maps a contiguous
+    (B, N, D) complex tensor to its DFT along dim 1.  Axes of length 1 are skipped."""
+    shape = tuple(z.shape)
+    out = z.contiguous()
+    for i, n in enumerate(shape):
+        if n > 1:
+            out = fft1d(out.reshape(math.prod(shape[:i]), n, math.prod(shape[i + 1:]))).contiguous()
+    if out.data_ptr() == z.data_ptr():                   # no axis longer than 1: the transform is the identity
+        out = out.clone()
+    return out.reshape(shape)
+
+
+def _check_c64(name: str, z) -> None:
+    if not (isinstance(z, torch.Tensor) and z.dtype == torch.complex64):
+        raise TypeError(f"{name}: z must be a complex64 tensor")
+
+
+def fftn(z: torch.Tensor) -> torch.Tensor:
+    """torch.fft.fftn(z) of a complex64 tensor over all its axes.  On a ROCm device it is composed from the native
+    sequence transform (seq_fft) axis by axis on views of the contiguous tensor: no FFT library runs, nothing is
+    transposed.  CPU tensors (and empty ones, and inputs that require grad) use torch.fft.  Not differentiable on the
+    device path."""
+    _check_c64("fftn", z)
+    if not z.is_cuda or z.numel() == 0 or z.requires_grad:
+        return torch.fft.fftn(z)
+    return _axis_walk(z.resolve_conj(), seq_fft_raw)
+
+
+def ifftn(z: torch.Tensor) -> torch.Tensor:
+    """torch.fft.ifftn(z) of a complex64 tensor over all its axes: conj(fftn(conj z)) / numel on a ROCm device (see
+    fftn), torch.fft elsewhere.  Not differentiable on the device path."""
+    _check_c64("ifftn", z)
+    if not z.is_cuda or z.numel() == 0 or z.requires_grad:
+        return torch.fft.ifftn(z)
+    out = _axis_walk(z.conj().resolve_conj(), seq_fft_raw)
+    return torch.conj_physical(out).div_(z.numel())
