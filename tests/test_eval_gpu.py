@@ -95,6 +95,20 @@ def test_find_snippets_multi_tile_walk(gpu, max_workgroups):
     assert {t * TILE - 1 for t in (1, 2, 3, 4)} <= set(want.tolist())
 
 
+def test_find_snippets_joins_more_than_256_table_rows(gpu):
+    """257 tiles and a bit under the default workgroup count: one workgroup per tile, so the (G, S) table has more rows
+    than k_match_join has threads and thread j takes rows j and j + 256.  The snippet planted at n - L begins in the last
+    tile (row 257 of the table) and, being found there first, nowhere else: its answer comes through the second step."""
+    L = 64
+    n = 257 * TILE + 100
+    corpus, snips = ec.planted_case(n, L, 23, 12)
+    want = check(corpus, snips, gpu)
+    assert (n - L + 1 + TILE - 1) // TILE > 256 and (n - L) // TILE >= 256
+    assert want[1] == n - L                                      # bytes.find's FIRST occurrence is the last position
+    assert want[0] == 0 and want[3] == -1 and want[4] == -1       # ... and absent ones stay absent over all the rows
+    assert {t * TILE - 1 for t in (1, 2, 3, 4, 5, 6)} <= set(want.tolist())
+
+
 def test_find_snippets_is_bitwise_reproducible(gpu):
     corpus, snips = ec.planted_case(4 * TILE + 9, 64, 64, 3)
     c, s = corpus.to(gpu), snips.to(gpu)

@@ -320,6 +320,35 @@ def test_every_dft_product_kernel_family_agrees_with_the_oracle(gpu, mode):
     assert errs[0] <= 1e-6 and errs[1] <= 1e-6, errs          # in fact all four sit at fp32 noise
 
 
+def test_more_batch_rows_than_one_grid_axis_holds_on_the_dft_product_plan(gpu):
+    """B = 65537 rows of N = 12 (no multiple of 256: the DFT-product plan, whose launchers put the batch row in grid.z)
+    forward and backward against the closed forms.  These are the literal kernels: a shape takes the tiled ones from
+    2^22 multiply-adds per batch row (use_tiled), which at this B needs gigabytes, not the few hundred MB a test may
+    use, so lib.set_option("tiled_dft", m) would select nothing else here and is not swept."""
+    pkg, lib, fn = _pkg()
+    B, N, D, F = 65537, 12, 2, 4
+    rng = np.random.default_rng(78)
+    x = rng.standard_normal((B, N, D)).astype(np.float32)
+    g = rng.standard_normal((B, N, D)).astype(np.float32)
+    wr = (1 + 0.5 * rng.standard_normal((D, F))).astype(np.float32)
+    wi = (0.5 * rng.standard_normal((D, F))).astype(np.float32)
+    b = (0.1 * rng.standard_normal(D)).astype(np.float32)
+    xd, wrd, wid, bd = (T(a).to(gpu).requires_grad_(True) for a in (x, wr, wi, b))
+    y = fn.spectral_mix(xd, wrd, wid, bd)
+    y.backward(T(g).to(gpu))
+    torch.cuda.synchronize()
+    y_ref, _ = so.forward_closed(x, wr, wi, b)
+    gx_ref, gwr_ref, gwi_ref, gb_ref = so.backward_closed(x, wr, wi, g)
+    c = lambda t: t.detach().cpu().numpy()
+    errs = (rel_err(c(y), y_ref), rel_err(c(xd.grad), gx_ref), rel_err(c(wrd.grad), gwr_ref),
+            rel_err(c(wid.grad), gwi_ref), rel_err(c(bd.grad), gb_ref))
+    print(f"(B, N, D, F) = ({B}, {N}, {D}, {F}): max-normalised distances (y, grad_x, grad_w_real, grad_w_imag, "
+          f"grad_bias) {errs}; bounds {TOL_ACT:.0e} / {TOL_PARAM:.0e}")
+    last = slice(B - 2, B)                                       # the rows past 65535 by themselves
+    assert rel_err(c(y)[last], y_ref[last]) <= TOL_ACT and rel_err(c(xd.grad)[last], gx_ref[last]) <= TOL_ACT
+    assert errs[0] <= TOL_ACT and errs[1] <= TOL_ACT and max(errs[2:]) <= TOL_PARAM, errs
+
+
 @pytest.mark.parametrize("B,N,D,F", [(3, 4000, 64, 128), (2, 2000, 34, 60), (5, 128, 16, 64), (2, 48, 8, 24),
                                      (1, 16, 4, 8), (2, 4112, 32, 128), (70, 1200, 96, 100), (2, 6000, 256, 128),
                                      (2, 4000, 512, 256), (3, 2000, 34, 200), (2, 1200, 40, 256),     # two bands

@@ -46,10 +46,12 @@ def draw(B, T, W, seed=None):
     return ids, torch.rand(max(W // 2, 1), generator=g) + 0.5
 
 
-def check(out, ids, bands, W, positions=True, what=""):
+def check(out, ids, bands, W, positions=True, what="", r_here=0.0):
+    """`r_here`: the reference's own error against the table AT THIS SHAPE, where that is above r_ref (R_REF_AT)"""
     e, share = bc.compare(out.detach().cpu().numpy(), ids.numpy(), bands.numpy(), W, positions)
-    print(f"{what}: kernel {e:.3e}, bound {bc.TOL_FACTOR * bc.r_ref():.3e}, left out {share:.2%}")
-    assert e <= bc.TOL_FACTOR * bc.r_ref(), (what, e)
+    bound = bc.TOL_FACTOR * max(bc.r_ref(), r_here)
+    print(f"{what}: kernel {e:.3e}, bound {bound:.3e}, left out {share:.2%}")
+    assert e <= bound, (what, e)
 
 
 @pytest.mark.parametrize("B,T,W", SHAPES)
@@ -71,6 +73,68 @@ def test_one_row_per_sequence_and_scalar_store_widths(gpu, B, T, W):
     full = pkg().byte_features(ids.to(gpu), bands.to(gpu), W, native=True)
     check(full, ids, bands, W, what=f"({B}, {T}, {W})")
     assert torch.equal(full[:, 0], row)
+
+
+# (B, T, W, positions): rows wide enough for k = min(W // 2, T // 2) > 128, where one thread sums all T terms of a bin
+# (NS = 1), a thread owns bins f, f + 256, ... (one pass of step B each) and walks columns c, c + 256, ... in step D
+WIDE = [(2, 512, 512, True),        # k = 256: NS = 1, one pass, the small-LDS instance
+        (1, 600, 601, True),        # k = 300: two passes, the second ragged (44 bins); scalar store, three column steps
+        (1, 1030, 1032, True),      # k = 515: three passes; 258 vectors a row, a second column step of one vector
+        (2, 4096, 4096, False),     # k = 2048: all eight passes, the encoder's single row
+        (1, 2048, 1028, True)]      # k = 514: 64 positions per workgroup (pp >= T / 32) with a second column step
+
+
+# The bound TOL_FACTOR * r_ref takes the reference's error from the fixtures, whose rows have at most 512 points.  At
+# (2, 4096, 4096) the kernel measured 7.27e-07 against it (6.69e-07), so the reference's own fp32 op sequence (torch.fft
+# on the CPU, as the fixtures were made: reference_ops32 below) was measured against the table on the same drawn input:
+# 4.746e-07, above r_ref -- a 4096-point fp32 FFT loses more than a 512-point one.  The bound at that shape is TOL_FACTOR
+# times that measurement; at every other shape, where the kernel is inside TOL_FACTOR * r_ref, it stays.
+R_REF_AT = {(2, 4096, 4096, False): 4.746e-07}
+
+
+def reference_ops32(ids, bands, W, positions):
+    """the reference's per-position procedure as it runs it, in fp32 torch on the CPU (bc.loop64 is its float64 twin)"""
+    k = min(W // 2, ids.shape[1] // 2)
+    s = ids.to(torch.float32) / 127.5 - 1.0
+    rows = []
+    for p in range(ids.shape[1] if positions else 1):
+        spec = torch.fft.fft(torch.roll(s, -p, dims=1), dim=1)[:, :k]
+        f = torch.cat([spec.abs() * bands[:k], torch.sin(spec.angle()), torch.cos(spec.angle())], dim=-1)
+        rows.append(torch.nn.functional.pad(f, (0, W - 3 * k)) if 3 * k < W else f[:, :W])
+    return torch.stack(rows, dim=1) if positions else rows[0]
+
+
+@pytest.mark.parametrize("B,T,W,pos", WIDE)
+def test_wide_rows_against_the_table(gpu, B, T, W, pos):
+    ids, bands = draw(B, T, W)
+    out = pkg().byte_features(ids.to(gpu), bands.to(gpu), W, positions=pos, native=True)
+    assert out.shape == ((B, T, W) if pos else (B, W)) and out.dtype == torch.float32
+    r_here = R_REF_AT.get((B, T, W, pos), 0.0)
+    if r_here:                                                   # (one row per sequence: two FFTs) shown beside the record
+        live, _ = bc.compare(reference_ops32(ids, bands, W, pos).numpy(), ids.numpy(), bands.numpy(), W, pos)
+        print(f"({B}, {T}, {W}) positions={pos}: the reference's fp32 ops {live:.3e} here, {r_here:.3e} recorded, "
+              f"r_ref {bc.r_ref():.3e}")
+    check(out, ids, bands, W, positions=pos, what=f"({B}, {T}, {W}) positions={pos}", r_here=r_here)
+    assert torch.equal(pkg().byte_features(ids.to(torch.uint8).to(gpu), bands.to(gpu), W, positions=pos, native=True), out)
+
+
+def test_band_gradient_of_a_wide_row_against_loop64_and_bitwise_twice(gpu):
+    """(1, 600, 601): k = 300 bins, five 64-column tiles of k_byte_gb_part with a ragged last one, ten position chunks;
+    the reference's per-position procedure in float64, differentiated by autograd."""
+    B, T, W = 1, 600, 601
+    ids, bands = draw(B, T, W)
+    up = torch.randn(B, T, W, generator=torch.Generator().manual_seed(1))
+    runs = []
+    for _ in range(2):
+        b = bands.to(gpu).requires_grad_(True)
+        pkg().byte_features(ids.to(gpu), b, W, native=True).backward(up.to(gpu))
+        runs.append(b.grad.clone())
+    assert torch.equal(runs[0], runs[1])
+    b64 = bands.double().requires_grad_(True)
+    (bc.loop64(ids.numpy(), b64, W) * up.double()).sum().backward()
+    e = rel_err(runs[0].cpu().numpy(), b64.grad.numpy())
+    print(f"grad_bands ({B}, {T}, {W}) against loop64: {e:.3e}, bound {TOL_PARAM:.0e}")
+    assert e <= TOL_PARAM
 
 
 def test_strided_token_rows(gpu):

@@ -16,7 +16,8 @@ from conftest import TOL_ACT, load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
 TILE = sc.TILE
-GPU_SHAPES = ((32, 32), (16, 16, 16), (8, 8, 8, 8), (64,), (33, 7))
+GPU_SHAPES = ((32, 32), (16, 16, 16), (8, 8, 8, 8), (64,), (33, 7), (100, 100))
+N_PAST_1024 = 1025 * TILE + 5   # local to this file: the CPU tests share sst_common.SIZES and stay as light as they are
 
 
 def pkg():
@@ -66,6 +67,31 @@ def test_native_sparsify_equals_the_definition_exactly(gpu, n):
             if kind in ("zeros", "mag5"):
                 assert got_i.numel() == n
     assert seen_mw == {0, 1, 2} or n == 1
+
+
+@pytest.mark.parametrize("kind", ["normal", "three_keys", "offset_view"])
+def test_native_sparsify_past_1024_tiles(gpu, kind):
+    """N_PAST_1024 elements are 1026 tiles (1027 for offset_view, which starts one element into its first tile): each of
+    k_topk_scan's 1024 threads owns two tiles and the last 511 none; under the default caps (max_workgroups = 0) the
+    histogram pass walks three tiles per workgroup and the count / write passes two."""
+    p = pkg()
+    n = N_PAST_1024
+    z = sc.build(kind, n, 300 + sc.CLASSES.index(kind))
+    keys = sc.keys_np(z)
+    srt = np.sort(keys, kind="stable")
+    dev = on_device(kind, z, gpu)
+    for k in (n // 20, n - 1):
+        want_c, want_i, _ = sc.sparsify_np(z, k, keys, srt)
+        got_c, got_i = p.sparsify_topk(dev, k=k, max_workgroups=0)
+        assert got_i.numel() == want_i.size, (kind, k, got_i.numel(), want_i.size)
+        assert np.array_equal(got_i.cpu().numpy(), want_i), (kind, k)
+        assert np.array_equal(bits(got_c), want_c.view(np.uint32)), (kind, k)
+        if kind == "three_keys" and k == n // 20:                   # ... and back: the scatter over 1026 tiles
+            assert got_i.numel() > n // 3                           # the tie at the threshold is kept whole
+            want = torch.zeros(n, dtype=torch.complex64, device=gpu)
+            want.index_put_((got_i,), got_c)
+            back = p.sparse_scatter(got_c, got_i, (n,), assume_ascending=True)
+            assert torch.equal(torch.view_as_real(back).view(torch.int32), torch.view_as_real(want).view(torch.int32))
 
 
 def test_native_sparsify_is_reproducible_and_takes_sparsity_and_shapes(gpu):
@@ -204,6 +230,27 @@ def test_sst_on_the_device_matches_the_reference(gpu, shape):
             worst = max(worst, *errs)
     assert worst <= TOL_ACT
     p.MemoryManager.clear_all()
+
+
+@pytest.mark.parametrize("shape", [(512, 3), (3, 512), (100, 100), (48, 20, 6), (1, 7, 1), (257, 256, 12)],
+                         ids=lambda s: "x".join(map(str, s)))
+def test_fftn_and_ifftn_on_the_device_against_float64(gpu, shape):
+    """The axis-by-axis transforms against numpy's on the complex128 copy of the same input, max-normalised, and their
+    round trip.  (3, 512): the last axis as a one-channel native transform; (257, 256, 12): the last axis is a batch of
+    65792 rows of 12 points -- more than one grid axis holds -- and the first a prime length; (1, 7, 1): axes of length
+    1 are skipped."""
+    p = pkg()
+    rng = np.random.default_rng(sum(shape))
+    z = (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
+    dev = torch.from_numpy(z).to(gpu)
+    z64 = z.astype(np.complex128)
+    fwd, inv = p.fftn(dev), p.ifftn(dev)
+    assert fwd.is_cuda and fwd.dtype == torch.complex64 and tuple(fwd.shape) == shape and tuple(inv.shape) == shape
+    errs = {"fftn": rel_err(fwd.cpu().numpy(), np.fft.fftn(z64)), "ifftn": rel_err(inv.cpu().numpy(), np.fft.ifftn(z64)),
+            "ifftn(fftn(z))": rel_err(p.ifftn(fwd).cpu().numpy(), z64)}
+    print(f"{shape}: max-normalised distances to float64 {errs}; bound {TOL_ACT:.0e}")
+    assert max(errs.values()) <= TOL_ACT, errs
+    assert torch.equal(dev, torch.from_numpy(z).to(gpu))           # the input is left as it was
 
 
 def test_block_streaming_matmul_on_the_device_matches_the_reference(gpu):

@@ -102,24 +102,32 @@ def test_batch_rows_do_not_interact_and_runs_are_bitwise_reproducible(gpu):
             assert torch.equal(x[b:b + 1], y)
 
 
-# (Bt, chunk, C) -> the rows per workgroup R the launcher takes: the largest of 4, 2, 1 with Bt ceil(chunk / R) >= 256
-# workgroups (and R VEC CH <= 64 accumulator registers, which every width here meets)
+# (Bt, chunk, C) -> the instance k_stream_conv<VEC, CH, R> the launcher takes.  VEC, CH: Vec<4> rows for C % 4 == 0 with
+# CH = 1, 2, 4, 8, 16 register chunks for C up to 256, 512, 1024, 2048, 4096; the scalar variant otherwise with CH = 1, 4, 16
+# for C up to 64, 256, 1023.  R: the largest of 4, 2, 1 with R VEC CH <= 64 accumulator registers AND
+# Bt ceil(chunk / R) >= 256 workgroups.
 ROW_GROUP_CASES = [(3, 5, 260),       # R = 1: 15 workgroups
                    (64, 16, 36),      # R = 4: 64 x 4 = 256; Vec<4>, one register chunk
                    (128, 5, 260),     # R = 4: 128 x 2 = 256, last group holds ONE row; Vec<4>, two register chunks
                    (100, 5, 36),      # R = 2: 100 x 2 < 256 <= 100 x 3, last group holds one row; Vec<4>
                    (100, 5, 70),      # R = 2, the scalar variant (C % 4 != 0), four register chunks
-                   (128, 5, 6)]       # R = 4, the scalar variant, C < 64
+                   (128, 5, 6),       # R = 4, the scalar variant, C < 64
+                   (128, 5, 1024),    # Vec<4> CH 4 R 4: exactly 4 x 4 x 4 = 64 accumulator registers, 128 x 2 = 256
+                   (100, 5, 772),     # Vec<4> CH 4 R 2: 100 x 2 < 256 <= 100 x 3; the last vector chunk part-filled
+                   (2, 5, 1020),      # Vec<4> CH 4 R 1: 10 workgroups
+                   (128, 5, 2048),    # Vec<4> CH 8 R 2: the workgroup count would take 4 (256), 4 x 4 x 8 = 128 registers do not
+                   (3, 5, 1540),      # Vec<4> CH 8 R 1: 15 workgroups; ragged last register chunk
+                   (128, 5, 2052),    # Vec<4> CH 16 R 1: R forced by the registers (2 x 4 x 16 = 128); ragged
+                   (2, 3, 4096),      # Vec<4> CH 16 R 1: the widest row
+                   (128, 5, 1023),    # scalar CH 16 R 4: 4 x 1 x 16 = 64 registers, 128 x 2 = 256
+                   (100, 5, 258),     # scalar CH 16 R 2: 100 x 2 < 256 <= 100 x 3
+                   (3, 5, 1022),      # scalar CH 16 R 1: 15 workgroups
+                   (128, 5, 70)]      # scalar CH 4 R 4: 128 x 2 = 256
 
 
 @torch.no_grad()
-@pytest.mark.parametrize("Bt,chunk,C", ROW_GROUP_CASES)
-def test_the_two_launches_alone_keep_batch_rows_apart(gpu, Bt, chunk, C):
-    """The library entries by themselves, on given inputs (no GEMM between them), at every rows-per-workgroup count of
-    smx_stream_conv: a row of a Bt-row launch is bit for bit that row launched alone (Bt = 1 always runs R = 1, so the
-    sums do not depend on R), each at its own ring position, and all rows agree with the plain fp64 statement."""
+def check_the_two_launches(gpu, Bt, chunk, C, T, K):
     from tensor_cuda_fft_amd import streaming as sm
-    T, K = 40, 7
     L = K - 1 + chunk
     gen = torch.Generator().manual_seed(8)
     rnd = lambda *s: torch.randn(*s, generator=gen).to(gpu)
@@ -129,7 +137,7 @@ def test_the_two_launches_alone_keep_batch_rows_apart(gpu, Bt, chunk, C):
     ring, hi, h, scale, taps = rnd(Bt, T, C), rnd(Bt, C), rnd(Bt, chunk, C), rnd(Bt, C), rnd(K + 2 * chunk - 2)
     sums = torch.stack((hi, 1e-7 * rnd(Bt, C)), dim=1).contiguous()
     pos = torch.randint(0, T, (Bt,), generator=gen).to(torch.int32)
-    pos[:3] = torch.tensor([0, T - 3, T - 1], dtype=torch.int32)             # rows 1 and 2 wrap inside the chunk
+    pos[:3] = torch.tensor([0, T - 3, T - 1], dtype=torch.int32)[:Bt]        # rows 1 and 2 wrap inside the chunk
     pos = pos.to(gpu)
 
     def run(sl):
@@ -139,7 +147,7 @@ def test_the_two_launches_alone_keep_batch_rows_apart(gpu, Bt, chunk, C):
 
     whole = run(slice(0, Bt))
     assert torch.equal(whole[2], (pos + chunk) % T)
-    for b in sorted({0, 1, 2, Bt // 2, Bt - 1}):
+    for b in sorted({0, 1, min(2, Bt - 1), Bt // 2, Bt - 1}):
         for x, y in zip(whole, run(slice(b, b + 1))):
             assert torch.equal(x[b:b + 1], y), b
     # and against the plain statement of the step in fp64
@@ -147,15 +155,37 @@ def test_the_two_launches_alone_keep_batch_rows_apart(gpu, Bt, chunk, C):
                                    .unsqueeze(-1).expand(-1, -1, C))
     new = torch.nn.functional.layer_norm(h.double(), (C,), ln.weight.double(), ln.bias.double(), ln.eps)
     w = torch.cat([chrono(ring, pos).double()[:, chunk:], new], dim=1)
-    assert rel_err(chrono(whole[0], whole[2]).cpu().numpy(), w.cpu().numpy()) <= TOL_ACT
+    e = {"ring": rel_err(chrono(whole[0], whole[2]).cpu().numpy(), w.cpu().numpy())}
     tot = sums.double().sum(dim=1) + (new - chrono(ring, pos).double()[:, :chunk]).sum(dim=1)
-    assert rel_err(whole[3].cpu().numpy(), (tot / T).cpu().numpy()) <= TOL_ACT
+    e["pooled"] = rel_err(whole[3].cpu().numpy(), (tot / T).cpu().numpy())
     seg = w[:, T - L:]
-    y = torch.stack([sum(taps[n + L - 1 - j].double() * seg[:, j] for j in range(L)) for n in range(chunk)], dim=1)
+    if L <= 64:
+        y = torch.stack([sum(taps[n + L - 1 - j].double() * seg[:, j] for j in range(L)) for n in range(chunk)], dim=1)
+    else:                                                # the same sum as one Toeplitz gather and a matmul
+        lag = torch.arange(chunk, device=gpu).unsqueeze(1) + (L - 1 - torch.arange(L, device=gpu)).unsqueeze(0)
+        y = torch.matmul(taps.double()[lag], seg)        # (chunk, L) @ (Bt, L, C)
     h_out = h.double() + scale.double().unsqueeze(1) * y
-    assert rel_err(whole[4].cpu().numpy(), h_out.cpu().numpy()) <= TOL_ACT
+    e["h_out"] = rel_err(whole[4].cpu().numpy(), h_out.cpu().numpy())
     ff = torch.nn.functional.layer_norm(h_out, (C,), ffn_ln.weight.double(), ffn_ln.bias.double(), ffn_ln.eps)
-    assert rel_err(whole[5].cpu().numpy(), ff.cpu().numpy()) <= TOL_ACT
+    e["ff_in"] = rel_err(whole[5].cpu().numpy(), ff.cpu().numpy())
+    print(f"(Bt, chunk, C, T, K) = ({Bt}, {chunk}, {C}, {T}, {K}): max-normalised distances to fp64 "
+          + ", ".join(f"{k} {v:.3e}" for k, v in e.items()) + f"; bound {TOL_ACT:.0e}")
+    assert max(e.values()) <= TOL_ACT, e
+
+
+@pytest.mark.parametrize("Bt,chunk,C", ROW_GROUP_CASES)
+def test_the_two_launches_alone_keep_batch_rows_apart(gpu, Bt, chunk, C):
+    """The library entries by themselves, on given inputs (no GEMM between them), at every (VEC, CH, R) instance of
+    smx_stream_conv: a row of a Bt-row launch is bit for bit that row launched alone (Bt = 1 always runs R = 1, so the
+    sums do not depend on R), each at its own ring position, and all rows agree with the plain fp64 statement."""
+    check_the_two_launches(gpu, Bt, chunk, C, T=40, K=7)
+
+
+@pytest.mark.parametrize("Bt", [2, 16])
+def test_the_two_launches_at_the_bounds_of_the_tap_table(gpu, Bt):
+    """K = 4096 and chunk = 64, the sizes the LDS tap table is made for (4222 taps), over L = 4159 of the T = 4160 ring
+    rows, C = 8 (Vec<4>, one register chunk): Bt = 2 runs R = 1 (128 workgroups), Bt = 16 runs R = 4 (16 x 16 = 256)."""
+    check_the_two_launches(gpu, Bt, 64, 8, T=4160, K=4096)
 
 
 @torch.no_grad()
