@@ -364,8 +364,6 @@ Plan make_plan(const Shape& h) {
   return p;
 }
 
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Ws {
   size_t z = 0, zs = 0, s = 0, slab = 0, gbp = 0, spec0 = 0, spec1 = 0, spec2 = 0, lnp = 0, total = 0;
   size_t s_group = 0;            // bytes of one band group's parked spectrum
@@ -433,18 +431,37 @@ Ws ws_layout(const Plan& p, int B, int N, int D) {
 
 // THE workspace test: `need` bytes at a 256-byte aligned address
 bool ws_usable(const void* ws, size_t bytes, size_t need) { return ws && bytes >= need && !((uintptr_t)ws & 255); }
-// ... and its refusal.  query: the entry that tells the size ("" = none is named), or NULL for the three messages of
-// the transform entries
+// ... and its refusal, in one message.  query: the entry that tells the size ("" = none is named)
 int need_ws(const void* ws, size_t bytes, size_t need, const char* query) {
   if (ws_usable(ws, bytes, need)) return SMX_OK;
-  if (query)
-    return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes%s%s%s", need, *query ? " (" : "",
-                query, *query ? ")" : "");
-  if (!ws) return fail(SMX_ERR_WORKSPACE, "workspace is NULL, %zu bytes required", need);
-  if (bytes < need) return fail(SMX_ERR_WORKSPACE, "workspace has %zu bytes, %zu required", bytes, need);
-  return fail(SMX_ERR_INVALID, "workspace must be 256-byte aligned");
+  return fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned and hold %zu bytes%s%s%s", need, *query ? " (" : "",
+              query, *query ? ")" : "");
 }
-int need_ws(const Ws& w, const void* ws, size_t bytes) { return need_ws(ws, bytes, w.total, nullptr); }
+// ... or in three: those of the transform entries as they stand; `who` (the entry, "smx_x") goes in front of each and
+// `query` (its size query) behind the two that state a size.  misaligned: the code of that fault (include/smx.h: the
+// entries differ)
+int need_ws(const void* ws, size_t bytes, size_t need, int misaligned, const char* who, const char* query) {
+  if (ws_usable(ws, bytes, need)) return SMX_OK;
+  const std::string pre = who ? std::string(who) + ": " : "", suf = query ? " (" + std::string(query) + ")" : "";
+  if (!ws) return fail(SMX_ERR_WORKSPACE, "%sworkspace is NULL, %zu bytes required%s", pre.c_str(), need, suf.c_str());
+  if (bytes < need)
+    return fail(SMX_ERR_WORKSPACE, "%sworkspace has %zu bytes, %zu required%s", pre.c_str(), bytes, need, suf.c_str());
+  return fail(misaligned, "%sworkspace must be 256-byte aligned", pre.c_str());
+}
+int need_ws(const Ws& w, const void* ws, size_t bytes) {
+  return need_ws(ws, bytes, w.total, SMX_ERR_INVALID, nullptr, nullptr);
+}
+
+// THE token source of the entries that read byte tokens (B, T) in place, rows row_stride elements apart: token_bytes 1 /
+// 8 -> kind 1 / 2 (uint8 / int64: EmaSrc, launch_word_targets, ...); required: the rows are read (non-NULL, row_stride >= T)
+int token_src(const void* tokens, int token_bytes, long long row_stride, long long T, bool required, int* kind) {
+  if (token_bytes != 1 && token_bytes != 8) return fail(SMX_ERR_INVALID, "token_bytes must be 1 (uint8) or 8 (int64)");
+  if (required && !tokens) return fail(SMX_ERR_INVALID, "tokens must be non-NULL");
+  if (required && row_stride < T) return fail(SMX_ERR_INVALID, "row_stride must be at least T");
+  if (token_bytes == 8 && ((uintptr_t)tokens & 7)) return fail(SMX_ERR_INVALID, "int64 tokens must be 8-byte aligned");
+  *kind = token_bytes == 1 ? 1 : 2;
+  return SMX_OK;
+}
 
 // elem: bytes per element of the streamed x / y (4; 2 for the 2-byte activations of the _io entries)
 // dir: 0 = a forward entry point, 1 = a backward one (which "st_layout_*" option places the write-back rows)
@@ -586,9 +603,6 @@ DirectArgs direct_args(const Plan& p, const Tables& t, const Shape& h) {
 }
 
 }  // namespace
-
-// what an entry point defined in another unit (smx_byte.hip) reports through smx_last_error()
-int smx::api_fail(int code, const char* text) { return fail(code, "%s", text); }
 
 extern "C" {
 
@@ -2026,12 +2040,10 @@ static int ema_check(int mode, int B, int S, int F) {
 static int ema_tokens_src(const void* tokens, int token_bytes, long long row_stride, int B, int T, int L, EmaSrc* src) {
   if (L < 2 || L > 64) return fail(SMX_ERR_INVALID, "chunk length L must be in 2..64, got %d", L);
   if (T < 0) return fail(SMX_ERR_INVALID, "T must not be negative, got %d", T);
-  if (token_bytes != 1 && token_bytes != 8) return fail(SMX_ERR_INVALID, "token_bytes must be 1 (uint8) or 8 (int64)");
   const int S = T / L;
-  if (S > 0 && !tokens) return fail(SMX_ERR_INVALID, "tokens must be non-NULL");
-  if (S > 0 && row_stride < T) return fail(SMX_ERR_INVALID, "row_stride must be at least T");
-  if (token_bytes == 8 && ((uintptr_t)tokens & 7)) return fail(SMX_ERR_INVALID, "int64 tokens must be 8-byte aligned");
-  *src = EmaSrc{tokens, token_bytes == 1 ? 1 : 2, row_stride, B, S, L / 2 + 1, L};
+  int kind;
+  if (int rc = token_src(tokens, token_bytes, row_stride, T, S > 0, &kind)) return rc;
+  *src = EmaSrc{tokens, kind, row_stride, B, S, L / 2 + 1, L};
   return SMX_OK;
 }
 static size_t ema_need(int B, int S, int F) { return WS_HEADER_BYTES + al(ema_states_bytes(B, S, F)) + al(ema_part_bytes(B, F)); }
@@ -2106,14 +2118,12 @@ int smx_word_targets(const void* tokens, int token_bytes, long long row_stride, 
   if (B <= 0 || T <= 0) return fail(SMX_ERR_INVALID, "shape must be positive: B=%d T=%d", B, T);
   if (T > WT_MAX_T) return fail(SMX_ERR_INVALID, "T must be at most %d, got %d", WT_MAX_T, T);
   if ((long long)B * T >= (1ll << 31)) return fail(SMX_ERR_INVALID, "B*T too large");
-  if (token_bytes != 1 && token_bytes != 8) return fail(SMX_ERR_INVALID, "token_bytes must be 1 (uint8) or 8 (int64)");
-  if (!tokens) return fail(SMX_ERR_INVALID, "tokens must be non-NULL");
+  int kind;
+  if (int rc = token_src(tokens, token_bytes, row_stride, T, true, &kind)) return rc;
   if (!phase && !boundary) return fail(SMX_ERR_INVALID, "phase and boundary are both NULL");
-  if (row_stride < T) return fail(SMX_ERR_INVALID, "row_stride must be at least T");
-  if (token_bytes == 8 && ((uintptr_t)tokens & 7)) return fail(SMX_ERR_INVALID, "int64 tokens must be 8-byte aligned");
   if (((uintptr_t)phase & 7) || ((uintptr_t)boundary & 3))
     return fail(SMX_ERR_INVALID, "phase must be 8-byte aligned and boundary 4-byte aligned");
-  HIP_TRY(launch_word_targets(tokens, token_bytes == 1 ? 1 : 2, row_stride, phase, boundary, B, T, (hipStream_t)stream));
+  HIP_TRY(launch_word_targets(tokens, kind, row_stride, phase, boundary, B, T, (hipStream_t)stream));
   return SMX_OK;
 }
 
@@ -2251,7 +2261,8 @@ int smx_sample_bytes(const float* logits, long long row_stride, const void* rece
   if (R >= (1ll << 31)) return fail(SMX_ERR_INVALID, "R too large");
   if (!logits || !u || !ids) return fail(SMX_ERR_INVALID, "logits, u, ids must be non-NULL");
   if (row_stride < V) return fail(SMX_ERR_INVALID, "row_stride must be at least V");
-  if (token_bytes != 1 && token_bytes != 8) return fail(SMX_ERR_INVALID, "token_bytes must be 1 (uint8) or 8 (int64)");
+  int kind;                              // (the window's own NULL and alignment refusals follow: they read differently)
+  if (int rc = token_src(nullptr, token_bytes, 0, 0, false, &kind)) return rc;
   if (n_recent < 0 || n_recent > SAMPLE_MAX_RECENT)
     return fail(SMX_ERR_INVALID, "n_recent must be in [0, %d], got %d", SAMPLE_MAX_RECENT, n_recent);
   if (n_recent > 0 && !recent) return fail(SMX_ERR_INVALID, "recent must be non-NULL with n_recent > 0");
@@ -2268,8 +2279,139 @@ int smx_sample_bytes(const float* logits, long long row_stride, const void* rece
   if (top_k < 0 || max_run_length < 0) return fail(SMX_ERR_INVALID, "top_k and max_run_length must not be negative");
   const SampleArgs a{temperature, top_p, repetition_penalty, presence_penalty, frequency_penalty,
                      top_k, ascii_only != 0, ban_cr != 0, max_run_length};
-  HIP_TRY(launch_sample_bytes(logits, row_stride, recent, token_bytes == 1 ? 1 : 2, n_recent, a, u, ids, probs, R,
+  HIP_TRY(launch_sample_bytes(logits, row_stride, recent, kind, n_recent, a, u, ids, probs, R, (hipStream_t)stream));
+  return SMX_OK;
+}
+
+// ---- byte-spectral features (smx_byte.hip) -------------------------------------------------------------------------------
+static int byte_shape(int B, const char* rows, int R, int W, int k) {
+  if (B <= 0 || R <= 0 || W <= 0 || k < 0)
+    return fail(SMX_ERR_INVALID, "shape must be positive (k: not negative): B=%d %s=%d W=%d", B, rows, R, W);
+  return SMX_OK;
+}
+int smx_byte_supported(int T, int k, int W) { return byte_supported(T, k, W) ? 1 : 0; }
+int smx_byte_features(const void* tokens, int token_bytes, long long row_stride, const float* bands, float* out,
+                      float* mag, int B, int T, int k, int W, int P, void* stream) {
+  if (int rc = byte_shape(B, "T", T, W, k)) return rc;
+  if (P != 1 && P != T) return fail(SMX_ERR_INVALID, "P must be 1 (one row per sequence) or T=%d, got %d", T, P);
+  if (k > T / 2) return fail(SMX_ERR_INVALID, "k must be at most T / 2: k=%d T=%d", k, T);
+  if (!tokens || !out || (k > 0 && !bands)) return fail(SMX_ERR_INVALID, "tokens, out and (k > 0) bands must be non-NULL");
+  int kind;
+  if (int rc = token_src(tokens, token_bytes, row_stride, T, true, &kind)) return rc;
+  if ((uintptr_t)out & 15) return fail(SMX_ERR_INVALID, "out must be 16-byte aligned");
+  if (((uintptr_t)bands | (uintptr_t)mag) & 3) return fail(SMX_ERR_INVALID, "bands and mag must be 4-byte aligned");
+  if (!byte_supported(T, k, W))
+    return fail(SMX_ERR_UNSUPPORTED, "unsupported size (smx_byte_supported): T=%d k=%d W=%d", T, k, W);
+  if ((long long)B * (P == 1 ? 1 : (T + 15) / 16) >= (1ll << 31) || (long long)B * P * W >= (1ll << 40))
+    return fail(SMX_ERR_INVALID, "B*P*W too large");
+  HIP_TRY(launch_byte_features(tokens, kind, row_stride, bands, out, mag, B, T, k, W, P, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_byte_workspace_bytes(int B, int P, int W, int k, size_t* out) {
+  if (!out) return fail(SMX_ERR_INVALID, "out is NULL");
+  if (int rc = byte_shape(B, "P", P, W, k)) return rc;
+  *out = byte_gb_part_bytes(B, P, k < W ? k : W);
+  return SMX_OK;
+}
+int smx_byte_grad_bands(const float* g, const float* mag, float* grad_bands, int n_bands, void* workspace,
+                        size_t workspace_bytes, int B, int P, int W, int k, void* stream) {
+  if (int rc = byte_shape(B, "P", P, W, k)) return rc;
+  const int kk = k < W ? k : W;
+  if (n_bands < kk || n_bands < 1) return fail(SMX_ERR_INVALID, "n_bands must be at least max(1, min(k, W)), got %d", n_bands);
+  if (!g || !grad_bands || (kk > 0 && !mag)) return fail(SMX_ERR_INVALID, "g, grad_bands and (k > 0) mag must be non-NULL");
+  if (((uintptr_t)g | (uintptr_t)mag | (uintptr_t)grad_bands) & 3) return fail(SMX_ERR_INVALID, "pointers must be 4-byte aligned");
+  if (byte_gb_blocks(B, P, kk) >= (1ll << 31)) return fail(SMX_ERR_INVALID, "B*P too large");
+  if (const size_t need = byte_gb_part_bytes(B, P, kk))      // (kk = 0: no partials, any workspace)
+    if (int rc = need_ws(workspace, workspace_bytes, need, SMX_ERR_INVALID, nullptr, "smx_byte_workspace_bytes")) return rc;
+  HIP_TRY(launch_byte_grad_bands(g, mag, (float*)workspace, grad_bands, n_bands, B, P, W, k, (hipStream_t)stream));
+  return SMX_OK;
+}
+
+// ---- multi-pattern exact byte search (smx_match.hip) ---------------------------------------------------------------------
+// (`max_workgroups` of this search, of the top-k passes and of the scatter: 0 = the launcher's own count)
+static int wg_check(int max_workgroups) {
+  if (max_workgroups < 0) return fail(SMX_ERR_INVALID, "max_workgroups must not be negative, got %d", max_workgroups);
+  return SMX_OK;
+}
+static int match_check(int S, int L) {
+  if (!match_supported(S, L))
+    return fail(SMX_ERR_UNSUPPORTED, "unsupported snippet set (smx_match_supported): S=%d L=%d", S, L);
+  return SMX_OK;
+}
+int smx_match_supported(int S, int L) { return match_supported(S, L) ? 1 : 0; }
+int smx_match_workspace_bytes(int S, int L, size_t* out) {
+  if (!out) return fail(SMX_ERR_INVALID, "out is NULL");
+  if (int rc = match_check(S, L)) return rc;
+  *out = match_part_bytes(S);
+  return SMX_OK;
+}
+int smx_match_first(const void* corpus, long long n, const void* snips, int S, int L, long long* first, void* workspace,
+                    size_t workspace_bytes, int max_workgroups, void* stream) {
+  if (int rc = match_check(S, L)) return rc;
+  if (n < 0) return fail(SMX_ERR_INVALID, "n must not be negative, got %lld", n);
+  if (!snips || !first || (n > 0 && !corpus))
+    return fail(SMX_ERR_INVALID, "corpus (n > 0), snips and first must be non-NULL");
+  if ((uintptr_t)first & 7) return fail(SMX_ERR_INVALID, "first must be 8-byte aligned");
+  if (int rc = wg_check(max_workgroups)) return rc;
+  if (int rc = need_ws(workspace, workspace_bytes, match_part_bytes(S), SMX_ERR_WORKSPACE, nullptr, "smx_match_workspace_bytes"))
+    return rc;
+  HIP_TRY(launch_match_first((const unsigned char*)corpus, n, (const unsigned char*)snips, S, L, first,
+                             (unsigned long long*)workspace, max_workgroups, (hipStream_t)stream));
+  return SMX_OK;
+}
+
+// ---- top-k sparsify and scatter of the sparse spectral tensor (smx_sst.hip) ------------------------------------------------
+static int topk_check(long long n) {
+  if (!topk_supported(n)) return fail(SMX_ERR_UNSUPPORTED, "unsupported size (smx_topk_supported): n=%lld", n);
+  return SMX_OK;
+}
+static int topk_ws(const char* who, long long n, const void* workspace, size_t workspace_bytes) {
+  return need_ws(workspace, workspace_bytes, topk_layout(n).need, SMX_ERR_WORKSPACE, who, "smx_topk_workspace_bytes");
+}
+int smx_topk_supported(long long n) { return topk_supported(n) ? 1 : 0; }
+int smx_topk_workspace_bytes(long long n, size_t* out) {
+  if (!out) return fail(SMX_ERR_INVALID, "out is NULL");
+  if (int rc = topk_check(n)) return rc;
+  *out = topk_layout(n).need;
+  return SMX_OK;
+}
+int smx_topk_select(const void* z, long long n, long long k, long long* result, void* workspace, size_t workspace_bytes,
+                    int max_workgroups, void* stream) {
+  if (int rc = topk_check(n)) return rc;
+  if (!z || !result) return fail(SMX_ERR_INVALID, "z and result must be non-NULL");
+  if (k < 1 || k > n) return fail(SMX_ERR_INVALID, "k must be in 1..n, got k=%lld n=%lld", k, n);
+  if (((uintptr_t)z & 7) || ((uintptr_t)result & 7)) return fail(SMX_ERR_INVALID, "z and result must be 8-byte aligned");
+  if (int rc = wg_check(max_workgroups)) return rc;
+  if (int rc = topk_ws("smx_topk_select", n, workspace, workspace_bytes)) return rc;
+  HIP_TRY(launch_topk_select((const float2*)z, n, k, result, workspace, max_workgroups, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_topk_compact(const void* z, long long n, const long long* result, void* coeffs, long long* flat_idx,
+                     long long capacity, void* workspace, size_t workspace_bytes, int max_workgroups, void* stream) {
+  if (int rc = topk_check(n)) return rc;
+  if (capacity < 0) return fail(SMX_ERR_INVALID, "capacity must not be negative, got %lld", capacity);
+  if (!z || !result || (capacity > 0 && (!coeffs || !flat_idx)))
+    return fail(SMX_ERR_INVALID, "z, result and (capacity > 0) coeffs, flat_idx must be non-NULL");
+  if (((uintptr_t)z & 7) || ((uintptr_t)result & 7) || ((uintptr_t)coeffs & 7) || ((uintptr_t)flat_idx & 7))
+    return fail(SMX_ERR_INVALID, "z, result, coeffs and flat_idx must be 8-byte aligned");
+  if (int rc = wg_check(max_workgroups)) return rc;
+  if (int rc = topk_ws("smx_topk_compact", n, workspace, workspace_bytes)) return rc;
+  if (capacity == 0) return SMX_OK;
+  HIP_TRY(launch_topk_compact((const float2*)z, n, result, (float2*)coeffs, flat_idx, capacity, workspace, max_workgroups,
                               (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_sparse_scatter(const void* coeffs, const long long* flat_idx, long long m, void* out, long long n,
+                       int max_workgroups, void* stream) {
+  if (int rc = topk_check(n)) return rc;
+  if (m < 0 || m > n) return fail(SMX_ERR_INVALID, "m must be in 0..n, got m=%lld n=%lld", m, n);
+  if (!out || (m > 0 && (!coeffs || !flat_idx)))
+    return fail(SMX_ERR_INVALID, "out and (m > 0) coeffs, flat_idx must be non-NULL");
+  if ((uintptr_t)out & 15) return fail(SMX_ERR_INVALID, "out must be 16-byte aligned");
+  if (((uintptr_t)coeffs & 7) || ((uintptr_t)flat_idx & 7))
+    return fail(SMX_ERR_INVALID, "coeffs and flat_idx must be 8-byte aligned");
+  if (int rc = wg_check(max_workgroups)) return rc;
+  HIP_TRY(launch_sparse_scatter((const float2*)coeffs, flat_idx, m, (float2*)out, n, max_workgroups, (hipStream_t)stream));
   return SMX_OK;
 }
 

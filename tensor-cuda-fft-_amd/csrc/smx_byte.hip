@@ -29,11 +29,9 @@
 // grad_bands[f] = sum_b sum_p g[b, p, f] |S[b, f]|: per (batch row, 64 positions) partial sums, one lane per column, then
 // a sum over the partials in index order by a second launch.  No atomics, no flags: bitwise reproducible.
 //
-// The C entries of these kernels are at the end of this file; their error text goes through smx_api.hip (api_fail).
+// The launchers and size rules at the end of this file are declared in smx_kernels.h; the C entries are in smx_api.hip.
 #include <cstdint>
-#include <cstdio>
 
-#include "../../include/smx.h"
 #include "smx_kernels.h"
 
 namespace smx {
@@ -44,18 +42,6 @@ constexpr int BYTE_SMALL_T = 512;                       // the instance with 7 K
 constexpr int BYTE_MAX_PASS = BYTE_MAX_K / BYTE_BLOCK;  // bins one thread can own
 constexpr int BYTE_WG_TARGET = 512;                     // workgroups of a launch before rows are cut into fewer chunks
 constexpr int BYTE_GB_ROWS = 64;                        // positions per partial sum of the band gradient
-
-struct ByteArgs {
-  const void* tokens;
-  long long row_stride;
-  const float* bands;
-  float* out;
-  float* mag;
-  int B, T, k, W, P;
-  int pp, chunks;                  // positions per workgroup, workgroups per batch row
-  int ns_log;                      // lanes per bin = 1 << ns_log (<= 64)
-  int cw_log;                      // threads across a row = 1 << cw_log
-};
 
 // |z| and z / |z| through an exact power-of-two scaling (no overflow or flush of x^2 + y^2); z == 0 -> r = 0, u = (0, 0),
 // which step D reads as "no rotation: sin 0, cos 1".
@@ -259,7 +245,19 @@ void byte_launch_t(const ByteArgs& a, hipStream_t s) {
   else hipLaunchKernelGGL((k_byte_features<TOK, VEC, BYTE_MAX_T>), grid, block, 0, s, a);
 }
 
-hipError_t launch_byte_features(ByteArgs a, int token_bytes, hipStream_t s) {
+int gb_chunks_per_row(int P) { return (P + BYTE_GB_ROWS - 1) / BYTE_GB_ROWS; }
+
+}  // namespace
+
+bool byte_supported(int T, int k, int W) {
+  return T >= 1 && T <= BYTE_MAX_T && k >= 0 && k <= T / 2 && k <= BYTE_MAX_K && W >= 1 && W <= BYTE_MAX_W;
+}
+
+hipError_t launch_byte_features(const void* tokens, int kind, long long row_stride, const float* bands, float* out,
+                                float* mag, int B, int T, int k, int W, int P, hipStream_t s) {
+  ByteArgs a{};
+  a.tokens = tokens; a.row_stride = row_stride; a.bands = bands; a.out = out; a.mag = mag;
+  a.B = B; a.T = T; a.k = k; a.W = W; a.P = P;
   const int npos = a.P == 1 ? 1 : a.T;
   // Every workgroup recomputes its row's bins, so a row is cut into few chunks once the batch alone fills the chip
   // (about 512 workgroups, two per CU): at least 16 positions each, at most 32 chunks of a long row.
@@ -274,7 +272,7 @@ hipError_t launch_byte_features(ByteArgs a, int token_bytes, hipStream_t s) {
   const bool vec = a.W % 4 == 0;
   a.cw_log = pow2_ceil_log(vec ? a.W / 4 : a.W);
   if (a.cw_log > 8) a.cw_log = 8;
-  if (token_bytes == 1) {
+  if (kind == 1) {
     if (vec) byte_launch_t<unsigned char, true>(a, s);
     else byte_launch_t<unsigned char, false>(a, s);
   } else {
@@ -284,96 +282,22 @@ hipError_t launch_byte_features(ByteArgs a, int token_bytes, hipStream_t s) {
   return hipGetLastError();
 }
 
-size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-int gb_chunks_per_row(int P) { return (P + BYTE_GB_ROWS - 1) / BYTE_GB_ROWS; }
-size_t gb_need(int B, int P, int kk) { return al256((size_t)B * gb_chunks_per_row(P) * kk * sizeof(float)); }
-
-int hip_fail(const char* what, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s failed: %s", what, hipGetErrorString(e));
-  return api_fail(SMX_ERR_HIP, buf);
+long long byte_gb_blocks(int B, int P, int kk) {
+  const int tiles = (kk + 63) / 64;
+  return (long long)B * gb_chunks_per_row(P) * (tiles > 0 ? tiles : 1);
 }
-int failf(int code, const char* fmt, long long a = 0, long long b = 0, long long c = 0) {
-  char buf[256];
-  snprintf(buf, sizeof buf, fmt, a, b, c);
-  return api_fail(code, buf);
-}
+size_t byte_gb_part_bytes(int B, int P, int kk) { return al((size_t)B * gb_chunks_per_row(P) * kk * sizeof(float)); }
 
-bool byte_supported(int T, int k, int W) {
-  return T >= 1 && T <= BYTE_MAX_T && k >= 0 && k <= T / 2 && k <= BYTE_MAX_K && W >= 1 && W <= BYTE_MAX_W;
-}
-
-}  // namespace
-}  // namespace smx
-
-using namespace smx;
-
-extern "C" {
-
-int smx_byte_supported(int T, int k, int W) { return byte_supported(T, k, W) ? 1 : 0; }
-
-int smx_byte_features(const void* tokens, int token_bytes, long long row_stride, const float* bands, float* out,
-                      float* mag, int B, int T, int k, int W, int P, void* stream) {
-  if (B <= 0 || T <= 0 || W <= 0 || k < 0)
-    return failf(SMX_ERR_INVALID, "shape must be positive (k: not negative): B=%lld T=%lld W=%lld", B, T, W);
-  if (token_bytes != 1 && token_bytes != 8) return failf(SMX_ERR_INVALID, "token_bytes must be 1 (uint8) or 8 (int64)");
-  if (P != 1 && P != T) return failf(SMX_ERR_INVALID, "P must be 1 (one row per sequence) or T=%lld, got %lld", T, P);
-  if (k > T / 2) return failf(SMX_ERR_INVALID, "k must be at most T / 2: k=%lld T=%lld", k, T);
-  if (!tokens || !out || (k > 0 && !bands)) return failf(SMX_ERR_INVALID, "tokens, out and (k > 0) bands must be non-NULL");
-  if (row_stride < T) return failf(SMX_ERR_INVALID, "row_stride must be at least T");
-  if (token_bytes == 8 && ((uintptr_t)tokens & 7)) return failf(SMX_ERR_INVALID, "int64 tokens must be 8-byte aligned");
-  if ((uintptr_t)out & 15) return failf(SMX_ERR_INVALID, "out must be 16-byte aligned");
-  if (((uintptr_t)bands | (uintptr_t)mag) & 3) return failf(SMX_ERR_INVALID, "bands and mag must be 4-byte aligned");
-  if (!byte_supported(T, k, W))
-    return failf(SMX_ERR_UNSUPPORTED, "unsupported size (smx_byte_supported): T=%lld k=%lld W=%lld", T, k, W);
-  if ((long long)B * (P == 1 ? 1 : (T + 15) / 16) >= (1ll << 31) || (long long)B * P * W >= (1ll << 40))
-    return failf(SMX_ERR_INVALID, "B*P*W too large");
-  ByteArgs a{};
-  a.tokens = tokens; a.row_stride = row_stride; a.bands = bands; a.out = out; a.mag = mag;
-  a.B = B; a.T = T; a.k = k; a.W = W; a.P = P;
-  (void)hipGetLastError();
-  const hipError_t e = launch_byte_features(a, token_bytes, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail("k_byte_features", e);
-  return SMX_OK;
-}
-
-int smx_byte_workspace_bytes(int B, int P, int W, int k, size_t* out) {
-  if (!out) return failf(SMX_ERR_INVALID, "out is NULL");
-  if (B <= 0 || P <= 0 || W <= 0 || k < 0)
-    return failf(SMX_ERR_INVALID, "shape must be positive (k: not negative): B=%lld P=%lld W=%lld", B, P, W);
-  *out = gb_need(B, P, k < W ? k : W);
-  return SMX_OK;
-}
-
-int smx_byte_grad_bands(const float* g, const float* mag, float* grad_bands, int n_bands, void* workspace,
-                        size_t workspace_bytes, int B, int P, int W, int k, void* stream) {
-  if (B <= 0 || P <= 0 || W <= 0 || k < 0)
-    return failf(SMX_ERR_INVALID, "shape must be positive (k: not negative): B=%lld P=%lld W=%lld", B, P, W);
-  const int kk = k < W ? k : W;
-  if (n_bands < kk || n_bands < 1) return failf(SMX_ERR_INVALID, "n_bands must be at least max(1, min(k, W)), got %lld", n_bands);
-  if (!g || !grad_bands || (kk > 0 && !mag)) return failf(SMX_ERR_INVALID, "g, grad_bands and (k > 0) mag must be non-NULL");
-  if (((uintptr_t)g | (uintptr_t)mag | (uintptr_t)grad_bands) & 3) return failf(SMX_ERR_INVALID, "pointers must be 4-byte aligned");
-  const int CP = gb_chunks_per_row(P);
-  if ((long long)B * CP * ((kk + 63) / 64 > 0 ? (kk + 63) / 64 : 1) >= (1ll << 31)) return failf(SMX_ERR_INVALID, "B*P too large");
-  const size_t need = gb_need(B, P, kk);
-  if (need) {
-    if (!workspace) return failf(SMX_ERR_WORKSPACE, "workspace is NULL, %lld bytes required (smx_byte_workspace_bytes)", (long long)need);
-    if (workspace_bytes < need)
-      return failf(SMX_ERR_WORKSPACE, "workspace has %lld bytes, %lld required (smx_byte_workspace_bytes)",
-                   (long long)workspace_bytes, (long long)need);
-    if ((uintptr_t)workspace & 255) return failf(SMX_ERR_INVALID, "workspace must be 256-byte aligned");
-  }
-  hipStream_t s = (hipStream_t)stream;
-  (void)hipGetLastError();
+hipError_t launch_byte_grad_bands(const float* g, const float* mag, float* part, float* grad_bands, int n_bands, int B,
+                                  int P, int W, int k, hipStream_t s) {
+  const int kk = k < W ? k : W, CP = gb_chunks_per_row(P);
   const int nchunk = B * CP, tiles = (kk + 63) / 64;
   if (kk > 0)
-    hipLaunchKernelGGL(k_byte_gb_part, dim3((unsigned)((long long)nchunk * tiles)), dim3(64), 0, s, g, mag,
-                       (float*)workspace, P, W, k, kk, CP, tiles);
+    hipLaunchKernelGGL(k_byte_gb_part, dim3((unsigned)((long long)nchunk * tiles)), dim3(64), 0, s, g, mag, part, P, W, k,
+                       kk, CP, tiles);
   hipLaunchKernelGGL(k_byte_gb_sum, dim3((unsigned)((n_bands + BYTE_BLOCK - 1) / BYTE_BLOCK)), dim3(BYTE_BLOCK), 0, s,
-                     (const float*)workspace, grad_bands, nchunk, kk, n_bands);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("k_byte_gb_*", e);
-  return SMX_OK;
+                     (const float*)part, grad_bands, nchunk, kk, n_bands);
+  return hipGetLastError();
 }
 
-}  // extern "C"
+}  // namespace smx

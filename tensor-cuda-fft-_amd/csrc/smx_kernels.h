@@ -383,7 +383,84 @@ hipError_t launch_sample_bytes(const float* logits, long long row_stride, const 
                                const SampleArgs& a, const float* u, long long* ids, float* probs, long long R,
                                hipStream_t s);
 
-// ---- byte-spectral features (smx_byte.hip: kernels AND their C entries; the error text goes through smx_api.hip) --------
-int api_fail(int code, const char* text);
+// ---- steps the units below share ----------------------------------------------------------------------------------------
+// a workspace part: rounded up to 256 bytes
+inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
+// Persistent workgroups that walk `ntiles` tiles g, g + G, ...: as many as stay resident (`cap`; `max_workgroups` > 0
+// lowers it: tests force the walk with 1 or 2), cut down so that every workgroup walks the same number of tiles, give or
+// take one.  No tiles: none.
+inline int tile_workgroups(long long ntiles, long long cap, int max_workgroups) {
+  if (ntiles <= 0) return 0;
+  if (max_workgroups > 0 && max_workgroups < cap) cap = max_workgroups;
+  const long long rounds = (ntiles + cap - 1) / cap;
+  return (int)((ntiles + rounds - 1) / rounds);
+}
+
+// ---- byte-spectral features (smx_byte.hip) ----------------------------------------------------------------------------
+struct ByteArgs {
+  const void* tokens;
+  long long row_stride;
+  const float* bands;
+  float* out;
+  float* mag;
+  int B, T, k, W, P;
+  int pp, chunks;                  // positions per workgroup, workgroups per batch row
+  int ns_log;                      // lanes per bin = 1 << ns_log (<= 64)
+  int cw_log;                      // threads across a row = 1 << cw_log
+};
+bool byte_supported(int T, int k, int W);
+// out (B, P, W), mag (B, k; nullable) of tokens (B, T), kind 1 / 2 = uint8 / int64, rows row_stride elements apart; P = 1 or
+// T.  Derives pp, chunks, ns_log, cw_log.
+hipError_t launch_byte_features(const void* tokens, int kind, long long row_stride, const float* bands, float* out,
+                                float* mag, int B, int T, int k, int W, int P, hipStream_t s);
+// grad_bands (n_bands) from g (B, P, W) and mag (B, k) over kk = min(k, W) columns: per-chunk partials in `part`
+// (byte_gb_part_bytes; untouched when kk = 0), then their sum.  byte_gb_blocks: workgroups of the partial launch.
+long long byte_gb_blocks(int B, int P, int kk);
+size_t byte_gb_part_bytes(int B, int P, int kk);
+hipError_t launch_byte_grad_bands(const float* g, const float* mag, float* part, float* grad_bands, int n_bands, int B,
+                                  int P, int W, int k, hipStream_t s);
+
+// ---- multi-pattern exact byte search (smx_match.hip) ------------------------------------------------------------------
+struct MatchArgs {
+  const unsigned char* corpus;
+  const unsigned char* snips;
+  unsigned long long* part;        // (G, S)
+  long long n;                     // corpus bytes
+  long long npos;                  // n - L + 1 > 0
+  long long ntiles;
+  int S, L, off, nvec;             // nvec: 16-byte vectors of a tile's image, ceil((TILE + L - 1) / 16)
+};
+bool match_supported(int S, int L);
+size_t match_part_bytes(int S);          // the (workgroups, S) table of minima
+// first[s] of S snippets of L bytes in corpus[0 : n]; derives off, nvec, npos, ntiles and the workgroups from the LDS of
+// (S, L); n < L: the join alone
+hipError_t launch_match_first(const unsigned char* corpus, long long n, const unsigned char* snips, int S, int L,
+                              long long* first, unsigned long long* part, int max_workgroups, hipStream_t s);
+
+// ---- top-k sparsify and scatter of the sparse spectral tensor (smx_sst.hip) ------------------------------------------------
+struct TopkState {                                        // written by k_topk_pick, read by the next pass
+  unsigned prefix;                                        // the key bits decided so far (right-aligned)
+  unsigned rank;                                          // the rank of T among the keys that share the prefix (1-based)
+  unsigned above;                                         // keys greater than every key that shares the prefix
+  unsigned pad;
+};
+
+struct TopkArgs {
+  const float2* z;
+  long long n;
+  long long ntiles;
+  int off;                                                // 0 or 1: elements between the 16-byte boundary below z and z
+};
+bool topk_supported(long long n);
+// workspace of select / compact: TopkState at 0, then the offsets of the column totals, the histogram rows and the tile
+// counts (after select: offsets); need: its size
+struct TopkLayout { size_t totals, rows, counts, need; };
+TopkLayout topk_layout(long long n);
+hipError_t launch_topk_select(const float2* z, long long n, long long k, long long* result, void* workspace,
+                              int max_workgroups, hipStream_t s);
+hipError_t launch_topk_compact(const float2* z, long long n, const long long* result, float2* coeffs, long long* flat_idx,
+                               long long capacity, const void* workspace, int max_workgroups, hipStream_t s);
+hipError_t launch_sparse_scatter(const float2* coeffs, const long long* flat_idx, long long m, float2* out, long long n,
+                                 int max_workgroups, hipStream_t s);
 
 }  // namespace smx

@@ -22,11 +22,9 @@
 // column, one workgroup per snippet.  No flag words, no waiting of one workgroup on another, no global atomics: a minimum does not
 // depend on the order in which positions are found, so the answer is a pure function of the inputs.
 //
-// The C entries are at the end of this file; their error text goes through smx_api.hip (api_fail).
+// The launcher and size rules at the end of this file are declared in smx_kernels.h; the C entries are in smx_api.hip.
 #include <cstdint>
-#include <cstdio>
 
-#include "../../include/smx.h"
 #include "smx_kernels.h"
 
 namespace smx {
@@ -44,16 +42,6 @@ constexpr int MATCH_CUS = 256, MATCH_MAX_WG = 4 * MATCH_CUS;
 constexpr int MATCH_STATIC_LDS = MATCH_IMAGE_VECS * 16 + MATCH_BITMAP_WORDS * 4 + MATCH_BUCKETS * 4
                                  + MATCH_MAX_S * (4 + 4 + 8);
 constexpr unsigned long long MATCH_NONE = ~0ull;
-
-struct MatchArgs {
-  const unsigned char* corpus;
-  const unsigned char* snips;
-  unsigned long long* part;        // (G, S)
-  long long n;                     // corpus bytes
-  long long npos;                  // n - L + 1 > 0
-  long long ntiles;
-  int S, L, off, nvec;             // nvec: 16-byte vectors of a tile's image, ceil((TILE + L - 1) / 16)
-};
 
 SMX_HD unsigned match_hash(unsigned w) { return (w * 0x9E3779B1u) >> (32 - MATCH_HASH_BITS); }
 
@@ -183,88 +171,28 @@ __global__ __launch_bounds__(MATCH_BLOCK) void k_match_join(const unsigned long 
   if (tid == 0) first[s] = red[0] == MATCH_NONE ? -1ll : (long long)red[0];
 }
 
-namespace {
-
 bool match_supported(int S, int L) {
   return S >= 1 && S <= MATCH_MAX_S && L >= 4 && L <= MATCH_MAX_L && (long long)S * L <= MATCH_MAX_BYTES;
 }
-size_t match_need(int S) { return ((size_t)MATCH_MAX_WG * S * sizeof(unsigned long long) + 255) / 256 * 256; }
+size_t match_part_bytes(int S) { return al((size_t)MATCH_MAX_WG * S * sizeof(unsigned long long)); }
 
-int match_fail(int code, const char* fmt, long long a = 0, long long b = 0) {
-  char buf[256];
-  snprintf(buf, sizeof buf, fmt, a, b);
-  return api_fail(code, buf);
-}
-
-}  // namespace
-
-// Workgroups of a launch: as many as stay resident (LDS bounds them to 2 ... 4 per CU), cut down so that every
-// workgroup walks the same number of tiles, give or take one; `max_workgroups` > 0 caps it (tests: 1 or 2).
-int match_workgroups(long long ntiles, int S, int L, int max_workgroups) {
-  if (ntiles <= 0) return 0;
-  const int lds = MATCH_STATIC_LDS + (S * L + 15) / 16 * 16;
-  int per_cu = (160 * 1024) / lds;
-  if (per_cu > 4) per_cu = 4;
-  long long cap = (long long)MATCH_CUS * per_cu;
-  if (max_workgroups > 0 && max_workgroups < cap) cap = max_workgroups;
-  const long long rounds = (ntiles + cap - 1) / cap;
-  return (int)((ntiles + rounds - 1) / rounds);
-}
-
-}  // namespace smx
-
-using namespace smx;
-
-extern "C" {
-
-int smx_match_supported(int S, int L) { return match_supported(S, L) ? 1 : 0; }
-
-int smx_match_workspace_bytes(int S, int L, size_t* out) {
-  if (!out) return match_fail(SMX_ERR_INVALID, "out is NULL");
-  if (!match_supported(S, L))
-    return match_fail(SMX_ERR_UNSUPPORTED, "unsupported snippet set (smx_match_supported): S=%lld L=%lld", S, L);
-  *out = match_need(S);
-  return SMX_OK;
-}
-
-int smx_match_first(const void* corpus, long long n, const void* snips, int S, int L, long long* first, void* workspace,
-                    size_t workspace_bytes, int max_workgroups, void* stream) {
-  if (!match_supported(S, L))
-    return match_fail(SMX_ERR_UNSUPPORTED, "unsupported snippet set (smx_match_supported): S=%lld L=%lld", S, L);
-  if (n < 0) return match_fail(SMX_ERR_INVALID, "n must not be negative, got %lld", n);
-  if (!snips || !first || (n > 0 && !corpus))
-    return match_fail(SMX_ERR_INVALID, "corpus (n > 0), snips and first must be non-NULL");
-  if ((uintptr_t)first & 7) return match_fail(SMX_ERR_INVALID, "first must be 8-byte aligned");
-  if (max_workgroups < 0) return match_fail(SMX_ERR_INVALID, "max_workgroups must not be negative, got %lld", max_workgroups);
-  const size_t need = match_need(S);
-  if (!workspace)
-    return match_fail(SMX_ERR_WORKSPACE, "workspace is NULL, %lld bytes required (smx_match_workspace_bytes)", (long long)need);
-  if (workspace_bytes < need)
-    return match_fail(SMX_ERR_WORKSPACE, "workspace has %lld bytes, %lld required (smx_match_workspace_bytes)",
-                      (long long)workspace_bytes, (long long)need);
-  if ((uintptr_t)workspace & 255) return match_fail(SMX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-
+hipError_t launch_match_first(const unsigned char* corpus, long long n, const unsigned char* snips, int S, int L,
+                              long long* first, unsigned long long* part, int max_workgroups, hipStream_t s) {
   MatchArgs a{};
-  a.corpus = (const unsigned char*)corpus; a.snips = (const unsigned char*)snips;
-  a.part = (unsigned long long*)workspace;
+  a.corpus = corpus; a.snips = snips; a.part = part;
   a.n = n; a.npos = n - L + 1; a.S = S; a.L = L;
   a.off = (int)((uintptr_t)corpus & 15);
   a.nvec = (MATCH_TILE + L - 1 + 15) / 16;
   a.ntiles = a.npos > 0 ? (a.off + a.npos + MATCH_TILE - 1) / MATCH_TILE : 0;
-  const int G = match_workgroups(a.ntiles, S, L, max_workgroups);
-  hipStream_t s = (hipStream_t)stream;
-  (void)hipGetLastError();
+  // as many workgroups as stay resident: LDS bounds them to 2 ... 4 per CU (`max_workgroups`: tests, 1 or 2)
+  const int lds = MATCH_STATIC_LDS + (S * L + 15) / 16 * 16;
+  int per_cu = (160 * 1024) / lds;
+  if (per_cu > 4) per_cu = 4;
+  const int G = tile_workgroups(a.ntiles, MATCH_CUS * per_cu, max_workgroups);
   if (G > 0)
     hipLaunchKernelGGL(k_match_scan, dim3((unsigned)G), dim3(MATCH_BLOCK), (size_t)((S * L + 15) / 16 * 16), s, a);
-  hipLaunchKernelGGL(k_match_join, dim3((unsigned)S), dim3(MATCH_BLOCK), 0, s,
-                     (const unsigned long long*)workspace, first, G, S);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "k_match_* failed: %s", hipGetErrorString(e));
-    return api_fail(SMX_ERR_HIP, buf);
-  }
-  return SMX_OK;
+  hipLaunchKernelGGL(k_match_join, dim3((unsigned)S), dim3(MATCH_BLOCK), 0, s, (const unsigned long long*)part, first, G, S);
+  return hipGetLastError();
 }
 
-}  // extern "C"
+}  // namespace smx

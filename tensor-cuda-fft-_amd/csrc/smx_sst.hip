@@ -31,11 +31,9 @@
 // No flag words, no waiting of one workgroup on another, no atomics on global memory, nothing allocated, no host
 // synchronisation: integer counts do not depend on order, so every result is a pure function of the inputs.
 //
-// The C entries are at the end of this file; their error text goes through smx_api.hip (api_fail).
+// The launchers and size rules at the end of this file are declared in smx_kernels.h; the C entries are in smx_api.hip.
 #include <cstdint>
-#include <cstdio>
 
-#include "../../include/smx.h"
 #include "smx_kernels.h"
 
 namespace smx {
@@ -53,20 +51,6 @@ constexpr int TOPK_WALK_WG = 1024;                        // count / write workg
 constexpr int TOPK_JOIN_BINS = 16, TOPK_JOIN_GROUPS = SST_BLOCK / TOPK_JOIN_BINS;
 constexpr int SCATTER_WG = 2048;
 constexpr long long SST_MAX_N = (1ll << 31) - 1;
-
-struct TopkState {                                        // written by k_topk_pick, read by the next pass
-  unsigned prefix;                                        // the key bits decided so far (right-aligned)
-  unsigned rank;                                          // the rank of T among the keys that share the prefix (1-based)
-  unsigned above;                                         // keys greater than every key that shares the prefix
-  unsigned pad;
-};
-
-struct TopkArgs {
-  const float2* z;
-  long long n;
-  long long ntiles;
-  int off;                                                // 0 or 1: elements between the 16-byte boundary below z and z
-};
 
 // Two products and a sum, each rounded.  build.sh compiles the other units with -ffp-contract=fast, under which the
 // backend fuses any product into a following sum -- HIP's __fmul_rn / __fadd_rn are plain `*` and `+` in a header, and
@@ -323,99 +307,34 @@ __global__ __launch_bounds__(SST_BLOCK) void k_sparse_scatter(const float2* __re
   }
 }
 
-namespace {
-
-int sst_fail(int code, const char* fmt, long long a = 0, long long b = 0) {
-  char buf[256];
-  snprintf(buf, sizeof buf, fmt, a, b);
-  return api_fail(code, buf);
-}
-
 bool topk_supported(long long n) { return n >= 1 && n <= SST_MAX_N; }
-long long topk_max_tiles(long long n) { return (n + 1 + SST_TILE - 1) / SST_TILE; }       // off is 0 or 1
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 // workspace: state | totals (2048) | rows (min(512, tiles), 2048) | tile counts / offsets
-struct TopkLayout { size_t totals, rows, counts, need; };
 TopkLayout topk_layout(long long n) {
-  const long long tiles = topk_max_tiles(n);
+  const long long tiles = (n + 1 + SST_TILE - 1) / SST_TILE;                 // off is 0 or 1
   const long long g = tiles < TOPK_HIST_WG ? tiles : TOPK_HIST_WG;
   TopkLayout l;
-  l.totals = up256(sizeof(TopkState));
-  l.rows = l.totals + up256((size_t)TOPK_MAX_BINS * 4);
-  l.counts = l.rows + up256((size_t)g * TOPK_MAX_BINS * 4);
-  l.need = l.counts + up256((size_t)tiles * 4);
+  l.totals = al(sizeof(TopkState));
+  l.rows = l.totals + al((size_t)TOPK_MAX_BINS * 4);
+  l.counts = l.rows + al((size_t)g * TOPK_MAX_BINS * 4);
+  l.need = l.counts + al((size_t)tiles * 4);
   return l;
 }
 
-// as many workgroups as stay resident (`cap`), cut down so that each walks the same number of tiles, give or take one
-int sst_workgroups(long long ntiles, int cap, int max_workgroups) {
-  long long c = cap;
-  if (max_workgroups > 0 && max_workgroups < c) c = max_workgroups;
-  const long long rounds = (ntiles + c - 1) / c;
-  return (int)((ntiles + rounds - 1) / rounds);
-}
+namespace {
 
-int topk_check_ws(const char* who, long long n, const void* workspace, size_t workspace_bytes) {
-  const size_t need = topk_layout(n).need;
-  char buf[256];
-  if (!workspace) {
-    snprintf(buf, sizeof buf, "%s: workspace is NULL, %lld bytes required (smx_topk_workspace_bytes)", who, (long long)need);
-    return api_fail(SMX_ERR_WORKSPACE, buf);
-  }
-  if (workspace_bytes < need) {
-    snprintf(buf, sizeof buf, "%s: workspace has %lld bytes, %lld required (smx_topk_workspace_bytes)", who,
-             (long long)workspace_bytes, (long long)need);
-    return api_fail(SMX_ERR_WORKSPACE, buf);
-  }
-  if ((uintptr_t)workspace & 255) {
-    snprintf(buf, sizeof buf, "%s: workspace must be 256-byte aligned", who);
-    return api_fail(SMX_ERR_WORKSPACE, buf);
-  }
-  return SMX_OK;
-}
-
-TopkArgs topk_args(const void* z, long long n) {
+TopkArgs topk_args(const float2* z, long long n) {
   TopkArgs a{};
-  a.z = (const float2*)z; a.n = n;
+  a.z = z; a.n = n;
   a.off = (int)(((uintptr_t)z & 15) / 8);
   a.ntiles = (a.off + n + SST_TILE - 1) / SST_TILE;
   return a;
 }
 
-int sst_launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return SMX_OK;
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s failed: %s", what, hipGetErrorString(e));
-  return api_fail(SMX_ERR_HIP, buf);
-}
-
 }  // namespace
-}  // namespace smx
 
-using namespace smx;
-
-extern "C" {
-
-int smx_topk_supported(long long n) { return topk_supported(n) ? 1 : 0; }
-
-int smx_topk_workspace_bytes(long long n, size_t* out) {
-  if (!out) return sst_fail(SMX_ERR_INVALID, "out is NULL");
-  if (!topk_supported(n)) return sst_fail(SMX_ERR_UNSUPPORTED, "unsupported size (smx_topk_supported): n=%lld", n);
-  *out = topk_layout(n).need;
-  return SMX_OK;
-}
-
-int smx_topk_select(const void* z, long long n, long long k, long long* result, void* workspace, size_t workspace_bytes,
-                    int max_workgroups, void* stream) {
-  if (!topk_supported(n)) return sst_fail(SMX_ERR_UNSUPPORTED, "unsupported size (smx_topk_supported): n=%lld", n);
-  if (!z || !result) return sst_fail(SMX_ERR_INVALID, "z and result must be non-NULL");
-  if (k < 1 || k > n) return sst_fail(SMX_ERR_INVALID, "k must be in 1..n, got k=%lld n=%lld", k, n);
-  if (((uintptr_t)z & 7) || ((uintptr_t)result & 7)) return sst_fail(SMX_ERR_INVALID, "z and result must be 8-byte aligned");
-  if (max_workgroups < 0) return sst_fail(SMX_ERR_INVALID, "max_workgroups must not be negative, got %lld", max_workgroups);
-  if (const int rc = topk_check_ws("smx_topk_select", n, workspace, workspace_bytes)) return rc;
-
+hipError_t launch_topk_select(const float2* z, long long n, long long k, long long* result, void* workspace,
+                              int max_workgroups, hipStream_t s) {
   const TopkArgs a = topk_args(z, n);
   const TopkLayout l = topk_layout(n);
   char* ws = (char*)workspace;
@@ -423,10 +342,8 @@ int smx_topk_select(const void* z, long long n, long long k, long long* result, 
   unsigned* totals = (unsigned*)(ws + l.totals);
   unsigned* rows = (unsigned*)(ws + l.rows);
   unsigned* counts = (unsigned*)(ws + l.counts);
-  const int G = sst_workgroups(a.ntiles, TOPK_HIST_WG, max_workgroups);       // <= min(512, tiles): the rows fit
-  const int Gw = sst_workgroups(a.ntiles, TOPK_WALK_WG, max_workgroups);
-  hipStream_t s = (hipStream_t)stream;
-  (void)hipGetLastError();
+  const int G = tile_workgroups(a.ntiles, TOPK_HIST_WG, max_workgroups);      // <= min(512, tiles): the rows fit
+  const int Gw = tile_workgroups(a.ntiles, TOPK_WALK_WG, max_workgroups);
   const int bits[3] = {TOPK_BITS0, TOPK_BITS1, TOPK_BITS2};
   int shift = 31;
   for (int p = 0; p < 3; ++p) {
@@ -441,48 +358,25 @@ int smx_topk_select(const void* z, long long n, long long k, long long* result, 
   }
   hipLaunchKernelGGL(k_topk_count, dim3((unsigned)Gw), dim3(SST_BLOCK), 0, s, a, (const long long*)result, counts);
   hipLaunchKernelGGL(k_topk_scan, dim3(1), dim3(1024), 0, s, counts, a.ntiles);
-  return sst_launched("k_topk_* (select)");
+  return hipGetLastError();
 }
 
-int smx_topk_compact(const void* z, long long n, const long long* result, void* coeffs, long long* flat_idx,
-                     long long capacity, void* workspace, size_t workspace_bytes, int max_workgroups, void* stream) {
-  if (!topk_supported(n)) return sst_fail(SMX_ERR_UNSUPPORTED, "unsupported size (smx_topk_supported): n=%lld", n);
-  if (capacity < 0) return sst_fail(SMX_ERR_INVALID, "capacity must not be negative, got %lld", capacity);
-  if (!z || !result || (capacity > 0 && (!coeffs || !flat_idx)))
-    return sst_fail(SMX_ERR_INVALID, "z, result and (capacity > 0) coeffs, flat_idx must be non-NULL");
-  if (((uintptr_t)z & 7) || ((uintptr_t)result & 7) || ((uintptr_t)coeffs & 7) || ((uintptr_t)flat_idx & 7))
-    return sst_fail(SMX_ERR_INVALID, "z, result, coeffs and flat_idx must be 8-byte aligned");
-  if (max_workgroups < 0) return sst_fail(SMX_ERR_INVALID, "max_workgroups must not be negative, got %lld", max_workgroups);
-  if (const int rc = topk_check_ws("smx_topk_compact", n, workspace, workspace_bytes)) return rc;
-  if (capacity == 0) return SMX_OK;
-
+hipError_t launch_topk_compact(const float2* z, long long n, const long long* result, float2* coeffs, long long* flat_idx,
+                               long long capacity, const void* workspace, int max_workgroups, hipStream_t s) {
   const TopkArgs a = topk_args(z, n);
-  const unsigned* offsets = (const unsigned*)((char*)workspace + topk_layout(n).counts);
-  const int Gw = sst_workgroups(a.ntiles, TOPK_WALK_WG, max_workgroups);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(k_topk_write, dim3((unsigned)Gw), dim3(SST_BLOCK), 0, (hipStream_t)stream, a, result, offsets,
-                     (float2*)coeffs, flat_idx, capacity);
-  return sst_launched("k_topk_write");
+  const unsigned* offsets = (const unsigned*)((const char*)workspace + topk_layout(n).counts);
+  const int Gw = tile_workgroups(a.ntiles, TOPK_WALK_WG, max_workgroups);
+  hipLaunchKernelGGL(k_topk_write, dim3((unsigned)Gw), dim3(SST_BLOCK), 0, s, a, result, offsets, coeffs, flat_idx, capacity);
+  return hipGetLastError();
 }
 
-int smx_sparse_scatter(const void* coeffs, const long long* flat_idx, long long m, void* out, long long n,
-                       int max_workgroups, void* stream) {
-  if (!topk_supported(n)) return sst_fail(SMX_ERR_UNSUPPORTED, "unsupported size (smx_topk_supported): n=%lld", n);
-  if (m < 0 || m > n) return sst_fail(SMX_ERR_INVALID, "m must be in 0..n, got m=%lld n=%lld", m, n);
-  if (!out || (m > 0 && (!coeffs || !flat_idx)))
-    return sst_fail(SMX_ERR_INVALID, "out and (m > 0) coeffs, flat_idx must be non-NULL");
-  if ((uintptr_t)out & 15) return sst_fail(SMX_ERR_INVALID, "out must be 16-byte aligned");
-  if (((uintptr_t)coeffs & 7) || ((uintptr_t)flat_idx & 7))
-    return sst_fail(SMX_ERR_INVALID, "coeffs and flat_idx must be 8-byte aligned");
-  if (max_workgroups < 0) return sst_fail(SMX_ERR_INVALID, "max_workgroups must not be negative, got %lld", max_workgroups);
-
+hipError_t launch_sparse_scatter(const float2* coeffs, const long long* flat_idx, long long m, float2* out, long long n,
+                                 int max_workgroups, hipStream_t s) {
   const long long ntiles = (n + SST_TILE - 1) / SST_TILE;
-  const int G = sst_workgroups(ntiles, SCATTER_WG, max_workgroups);
+  const int G = tile_workgroups(ntiles, SCATTER_WG, max_workgroups);
   const long long per = (ntiles + G - 1) / G;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(k_sparse_scatter, dim3((unsigned)G), dim3(SST_BLOCK), 0, (hipStream_t)stream, (const float2*)coeffs,
-                     flat_idx, m, (float2*)out, n, ntiles, per);
-  return sst_launched("k_sparse_scatter");
+  hipLaunchKernelGGL(k_sparse_scatter, dim3((unsigned)G), dim3(SST_BLOCK), 0, s, coeffs, flat_idx, m, out, n, ntiles, per);
+  return hipGetLastError();
 }
 
-}  // extern "C"
+}  // namespace smx

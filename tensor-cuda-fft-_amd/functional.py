@@ -1811,6 +1811,15 @@ def ema_scan(chunks: torch.Tensor, rho_logit: torch.Tensor, theta_raw: torch.Ten
     return _EmaScan.apply(_dense(chunks), rho_logit, theta_raw, _dense(init), m)
 
 
+def _token_rows(tokens: torch.Tensor) -> torch.Tensor:
+    """(B, T) tokens as the kernels read them in place -- unit stride along a row, rows at least T elements apart, aligned
+    to the element -- else their contiguous copy."""
+    if tokens.shape[1] > 1 and tokens.stride(1) != 1 or tokens.stride(0) < tokens.shape[1] \
+            or tokens.data_ptr() % tokens.element_size():
+        return tokens.contiguous()
+    return tokens
+
+
 def ema_scan_tokens(tokens: torch.Tensor, chunk_len: int, rho_logit: torch.Tensor, theta_raw: torch.Tensor,
                     mode: str = "aligned") -> torch.Tensor:
     """ema_scan over the chunk spectra of byte tokens (B, T), uint8 or int64: chunk t of row b is the
@@ -1824,9 +1833,7 @@ def ema_scan_tokens(tokens: torch.Tensor, chunk_len: int, rho_logit: torch.Tenso
     rho_logit, theta_raw = _ema_params(L // 2 + 1, rho_logit, theta_raw)
     if tokens.shape[0] == 0:
         return torch.empty((0, L // 2 + 1), dtype=torch.complex64, device=tokens.device)
-    if tokens.shape[1] > 1 and tokens.stride(1) != 1 or tokens.stride(0) < tokens.shape[1] \
-            or tokens.data_ptr() % tokens.element_size():
-        tokens = tokens.contiguous()
+    tokens = _token_rows(tokens)
     return _EmaScanTokens.apply(tokens, L, rho_logit, theta_raw, m)
 
 
@@ -1881,9 +1888,7 @@ def word_targets(tokens: torch.Tensor, phase: bool = True, boundary: bool = True
             return (torch.zeros((B, T, 2), dtype=torch.float32, device=dev) if phase else None,
                     torch.zeros((B, T), dtype=torch.float32, device=dev) if boundary else None)
         return _word_targets_torch(tokens, phase, boundary)
-    if tokens.shape[1] > 1 and tokens.stride(1) != 1 or tokens.stride(0) < tokens.shape[1] \
-            or tokens.data_ptr() % tokens.element_size():
-        tokens = tokens.contiguous()
+    tokens = _token_rows(tokens)
     ph = torch.empty((B, T, 2), dtype=torch.float32, device=dev) if phase else None
     bd = torch.empty((B, T), dtype=torch.float32, device=dev) if boundary else None
     _call(dev, "smx_word_targets", tokens.data_ptr(), tokens.element_size(), tokens.stride(0), _ptr(ph), _ptr(bd), B, T,
@@ -2239,9 +2244,7 @@ def byte_features(tokens: torch.Tensor, bands: torch.Tensor, width: int, positio
         if native and not can:
             raise ValueError(f"byte_features: no native launch for T={T}, k={k}, width={W} on {tokens.device}")
         if can and native is not False:
-            if tokens.shape[1] > 1 and tokens.stride(1) != 1 or tokens.stride(0) < tokens.shape[1] \
-                    or tokens.data_ptr() % tokens.element_size():
-                tokens = tokens.contiguous()
+            tokens = _token_rows(tokens)
             out = _ByteFeatures.apply(tokens, _dense(bands), k, W, P)
         else:
             out = _byte_features_torch(tokens, bands, k, W, P)

@@ -7,15 +7,17 @@
 //     <entry> <inputs> -> <rc> <text of smx_last_error()> [after <launches>]            (rc != 0)
 //     <entry> <inputs> -> 0: <kernel> <grid.x>[x<grid.y>[x<grid.z>]]/<block.x> #<digest> | ...
 // (trailing grid dimensions of 1 are left out; "#=" is the digest of the launch before it in the line)
-// The digest is a 64-bit hash of the launch's arguments printed value by value (DecimArgs and DirectArgs field by
-// field); --verbose prints those values instead (to read a mismatch; not compared).  Pointers are written
+// (a launch with dynamic LDS: " lds=<bytes>" after the block)
+// The digest is a 64-bit hash of the launch's arguments printed value by value (DecimArgs, DirectArgs, ByteArgs,
+// MatchArgs, TopkArgs and SampleArgs field by field); --verbose prints those values instead (to read a mismatch; not compared).  Pointers are written
 // symbolically -- ws+<offset>, tables:<bytes>.<n>+<offset> (the n-th allocation of its API call, <bytes> long), or the
 // name of the dummy input -- so that a line depends neither on the allocator nor on the order of the calls (every
 // n_fft is prepared by its own smx_prepare call before its first use).
 // tests/test_api_trace.py compares the output with expected.txt, line for line.
 //
 // Sections: the plans over a grid of shapes and options; the transform entries on every plan kind; their call variants
-// and options; block entries; convolution; the smaller ops; refusals, one fault at a time.
+// and options; block entries; convolution; the smaller ops; refusals, one fault at a time; the newer ops (word targets,
+// row head, cross-entropy, sampler, byte features, byte search, top-k and scatter) with theirs.
 #include <cxxabi.h>
 #include <hip/hip_runtime.h>
 
@@ -34,6 +36,10 @@
 
 using smx::DecimArgs;
 using smx::DirectArgs;
+using smx::ByteArgs;
+using smx::MatchArgs;
+using smx::SampleArgs;
+using smx::TopkArgs;
 
 // ---- symbolic addresses ----------------------------------------------------------------------------------------------
 static constexpr uintptr_t DUMMY0 = 0x100000000000ull, DUMMY_SPAN = 1ull << 32, TAB0 = 0x200000000000ull,
@@ -113,6 +119,28 @@ static std::string dump(const DecimArgs& a) {
 static std::string dump(const DirectArgs& a) {
   std::string s;
   INT(B); INT(N); INT(D); INT(F); INT(k); PTR(tw); INT(f0); INT(fstep); INT(rows); INT(accumulate); INT(R);
+  return s;
+}
+static std::string dump(const ByteArgs& a) {
+  std::string s;
+  PTR(tokens); INT(row_stride); PTR(bands); PTR(out); PTR(mag); INT(B); INT(T); INT(k); INT(W); INT(P);
+  INT(pp); INT(chunks); INT(ns_log); INT(cw_log);
+  return s;
+}
+static std::string dump(const MatchArgs& a) {
+  std::string s;
+  PTR(corpus); PTR(snips); PTR(part); INT(n); INT(npos); INT(ntiles); INT(S); INT(L); INT(off); INT(nvec);
+  return s;
+}
+static std::string dump(const TopkArgs& a) {
+  std::string s;
+  PTR(z); INT(n); INT(ntiles); INT(off);
+  return s;
+}
+static std::string dump(const SampleArgs& a) {
+  std::string s;
+  FLT(temperature); FLT(top_p); FLT(rep); FLT(presence); FLT(frequency); INT(top_k); INT(ascii_only); INT(ban_cr);
+  INT(max_run);
 #undef PTR
 #undef INT
 #undef FLT
@@ -176,7 +204,7 @@ hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* shmem, hip
   *grid = g_grid; *block = g_block; *shmem = g_shmem; *s = g_stream;
   return hipSuccess;
 }
-hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, size_t, hipStream_t) {
+hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t) {
   auto it = kernels().find(f);
   if (it == kernels().end()) { record("unregistered-kernel", ""); return hipSuccess; }
   const Kernel& k = it->second;
@@ -186,6 +214,10 @@ hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, si
     const void* a = args[i];
     if (t == "DecimArgs") v += dump(*(const DecimArgs*)a);
     else if (t == "DirectArgs") v += dump(*(const DirectArgs*)a);
+    else if (t == "ByteArgs") v += dump(*(const ByteArgs*)a);
+    else if (t == "MatchArgs") v += dump(*(const MatchArgs*)a);
+    else if (t == "TopkArgs") v += dump(*(const TopkArgs*)a);
+    else if (t == "SampleArgs") v += dump(*(const SampleArgs*)a);
     else if (t.back() == '*') v += " " + sym(*(void* const*)a);
     else if (t == "int") v += fmt(" %d", *(const int*)a);
     else if (t == "unsigned int") v += fmt(" %u", *(const unsigned*)a);
@@ -196,7 +228,7 @@ hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, si
     else v += " (" + t + ")";
   }
   const std::string dims = grid.z > 1 ? fmt("%ux%ux%u", grid.x, grid.y, grid.z) : grid.y > 1 ? fmt("%ux%u", grid.x, grid.y) : fmt("%u", grid.x);
-  record(k.name + " " + dims + fmt("/%u", block.x), v);
+  record(k.name + " " + dims + fmt("/%u", block.x) + (lds ? fmt(" lds=%zu", lds) : std::string()), v);
   return hipSuccess;
 }
 hipError_t hipMalloc(void** p, size_t bytes) {
@@ -1029,6 +1061,491 @@ static void refusals() {
   g_capturing = false;
 }
 
+// ---- the newer ops: every branch of an entry or launcher that selects an instance, a grid or an argument; every refusal --
+// (nothing is read or written here, so a size costs nothing: the shapes are the ones that reach the branches)
+static void answer(const std::string& v) { call([&] { g_rec = v; return 0; }); }
+static void query(const std::function<int(size_t*)>& f) {
+  call([&] { size_t n = 0; const int rc = f(&n); if (!rc) g_rec = fmt("%zu", n); return rc; });
+}
+static size_t sized(const std::function<int(size_t*)>& f) { size_t n = 0; return f(&n) ? 4096 : n; }
+
+static void word_targets_and_head() {
+  void* TK = dp<char>("tokens");
+  float *PH = dp("phase"), *BD = dp("boundary");
+  auto wt = [&](const char* what, const void* tokens, int tb, long long stride, float* phase, float* boundary, int B, int T) {
+    IN("word_targets (%d,%d) token_bytes=%d stride=%lld %s", B, T, tb, stride, what);
+    call([&] { return smx_word_targets(tokens, tb, stride, phase, boundary, B, T, nullptr); });
+  };
+  for (int tb : {1, 8}) {
+    wt("phase", TK, tb, 128, PH, nullptr, 3, 100);
+    wt("boundary", TK, tb, 128, nullptr, BD, 3, 100);
+    wt("both", TK, tb, 128, PH, BD, 3, 100);
+  }
+  wt("T=65536", TK, 1, 65536, PH, BD, 2, 65536);
+  wt("B=0", TK, 1, 128, PH, BD, 0, 100);
+  wt("T=65537", TK, 1, 70000, PH, BD, 3, 65537);
+  wt("B*T=2^31", TK, 1, 65536, PH, BD, 32768, 65536);
+  wt("token_bytes=4", TK, 4, 128, PH, BD, 3, 100);
+  wt("tokens=0", nullptr, 1, 128, PH, BD, 3, 100);
+  wt("both outputs NULL", TK, 1, 128, nullptr, nullptr, 3, 100);
+  wt("row_stride < T", TK, 1, 99, PH, BD, 3, 100);
+  wt("tokens+4", dp<char>("tokens", 4), 8, 128, PH, BD, 3, 100);
+  wt("tokens+4", dp<char>("tokens", 4), 1, 128, PH, BD, 3, 100);        // (accepted: bytes)
+  wt("phase+4", TK, 1, 128, dp("phase", 4), BD, 3, 100);
+  wt("boundary+2", TK, 1, 128, PH, dp("boundary", 2), 3, 100);
+
+  float *H = dp("h"), *W = dp("w"), *Bv = dp("b"), *Y = dp("y"), *G = dp("g");
+  IN("head_supported C=96,97,1000,1024,1025,1028,4096,4100,0 x O=0..3");
+  {
+    std::string v;
+    for (int C : {96, 97, 1000, 1024, 1025, 1028, 4096, 4100, 0}) {
+      for (int O = 0; O <= 3; ++O) v += fmt("%d", smx_head_supported(C, O));
+      v += " ";
+    }
+    answer(v);
+  }
+  auto head_ws = [&](const char* what, long long R, int C, int O, bool out = true) {
+    IN("head_workspace_bytes (%lld,%d) O=%d %s", R, C, O, what);
+    query([&](size_t* n) { return smx_head_workspace_bytes(R, C, O, out ? n : nullptr); });
+  };
+  head_ws("", 37, 96, 1);
+  head_ws("", 37, 96, 2);
+  head_ws("", 100000, 96, 2);
+  head_ws("out=0", 37, 96, 1, false);
+  head_ws("R=0", 0, 96, 1);
+  head_ws("O=3", 37, 96, 3);
+  head_ws("C=1025", 37, 1025, 1);
+  head_ws("R*C=2^40", 1ll << 28, 4096, 1);
+  auto head_fwd = [&](const char* what, const float* h, const float* w, const float* b, float* y, long long R, int C, int O) {
+    IN("head_forward (%lld,%d) O=%d %s", R, C, O, what);
+    call([&] { return smx_head_forward(h, w, b, y, R, C, O, nullptr); });
+  };
+  for (int O : {1, 2}) {
+    head_fwd("", H, W, Bv, Y, 37, 96, O);
+    head_fwd("b=0", H, W, nullptr, Y, 37, 97, O);
+    head_fwd("", H, W, Bv, Y, 100000, 1000, O);
+  }
+  head_fwd("O=3", H, W, Bv, Y, 37, 96, 3);
+  head_fwd("C=1025", H, W, Bv, Y, 37, 1025, 1);
+  head_fwd("R=0", H, W, Bv, Y, 0, 96, 1);
+  head_fwd("h=0", nullptr, W, Bv, Y, 37, 96, 1);
+  head_fwd("y=0", H, W, Bv, nullptr, 37, 96, 1);
+  head_fwd("w+8", H, dp("w", 8), Bv, Y, 37, 96, 1);
+  head_fwd("y+2", H, W, Bv, dp("y", 2), 37, 96, 1);
+  struct HB { const float *g, *h, *w; float *gh, *gw, *gb; };
+  const HB all{G, H, W, dp("grad_h"), dp("grad_w"), dp("grad_b")};
+  auto head_bwd = [&](const std::string& what, const HB& a, long long R, int C, int O, bool ws_cases = false) {
+    const size_t need = sized([&](size_t* n) { return smx_head_workspace_bytes(R, C, O == 3 ? 1 : O, n); });
+    const std::string name = fmt("head_backward (%lld,%d) O=%d ", R, C, O) + what;
+    auto f = [&](void* ws, size_t n) { return smx_head_backward(a.g, a.h, a.w, a.gh, a.gw, a.gb, ws, n, R, C, O, nullptr); };
+    if (ws_cases) return with_ws(name.c_str(), need, f);
+    IN("%s", name.c_str());
+    call([&] { return f(WS, need); });
+  };
+  for (int O : {1, 2}) {
+    head_bwd("all", all, 37, 96, O, true);
+    head_bwd("grad_h only", HB{G, H, W, all.gh, nullptr, nullptr}, 37, 96, O);
+    head_bwd("grad_w grad_b only", HB{G, H, W, nullptr, all.gw, all.gb}, 37, 96, O);
+    head_bwd("grad_b only, h=0 w=0", HB{G, nullptr, nullptr, nullptr, nullptr, all.gb}, 37, 97, O);
+    head_bwd("no gradient", HB{G, H, W, nullptr, nullptr, nullptr}, 37, 96, O);
+    head_bwd("all", all, 100000, 1000, O);
+  }
+  head_bwd("all", all, 37, 96, 3);
+  head_bwd("all", all, 37, 1025, 1);
+  head_bwd("g=0", HB{nullptr, H, W, all.gh, all.gw, all.gb}, 37, 96, 1);
+  head_bwd("h=0 with grad_w", HB{G, nullptr, W, all.gh, all.gw, all.gb}, 37, 96, 1);
+  head_bwd("w=0 with grad_h", HB{G, H, nullptr, all.gh, all.gw, all.gb}, 37, 96, 1);
+  head_bwd("grad_h+8", HB{G, H, W, dp("grad_h", 8), all.gw, all.gb}, 37, 96, 1);
+  head_bwd("grad_w+2", HB{G, H, W, all.gh, dp("grad_w", 2), all.gb}, 37, 96, 1);
+  head_bwd("grad_h=h", HB{G, H, W, H, all.gw, all.gb}, 37, 96, 1);
+  head_bwd("grad_h=g", HB{G, H, W, G, all.gw, all.gb}, 37, 96, 1);
+}
+
+static void xent_and_sampler() {
+  float *X = dp("logits"), *G = dp("g"), *LOSS = dp("loss"), *LSE = dp("lse"), *CNT = dp("count"), *GR = dp("grad");
+  long long* TG = dp<long long>("targets");
+  IN("xent_supported V=-1,0,1,50257");
+  answer(fmt("%d%d%d%d", smx_xent_supported(-1), smx_xent_supported(0), smx_xent_supported(1), smx_xent_supported(50257)));
+  auto xent_ws = [&](const char* what, long long R, int V, bool out = true) {
+    IN("xent_workspace_bytes (%lld,%d) %s", R, V, what);
+    query([&](size_t* n) { return smx_xent_workspace_bytes(R, V, out ? n : nullptr); });
+  };
+  xent_ws("", 37, 256);
+  xent_ws("", 5000, 50257);
+  xent_ws("out=0", 37, 256, false);
+  xent_ws("R=0", 0, 256);
+  xent_ws("V=0", 37, 0);
+  xent_ws("R=2^31", 1ll << 31, 256);
+  struct XF { const float* x; long long stride; const long long* t; int red; float *loss, *lse, *cnt; };
+  auto xfwd = [&](const std::string& what, const XF& a, long long R, int V, bool ws_cases = false) {
+    const size_t need = sized([&](size_t* n) { return smx_xent_workspace_bytes(R, V, n); });
+    const std::string name = fmt("xent_forward (%lld,%d) stride=%lld reduction=%d ", R, V, a.stride, a.red) + what;
+    auto f = [&](void* ws, size_t n) {
+      return smx_xent_forward(a.x, a.stride, a.t, -100, a.red, a.loss, a.lse, a.cnt, ws, n, R, V, nullptr);
+    };
+    if (ws_cases) return with_ws(name.c_str(), need, f);
+    IN("%s", name.c_str());
+    call([&] { return f(WS, need); });
+  };
+  struct XB { const float *g, *x; long long stride; const long long* t; int red; const float *lse, *cnt; float* grad; };
+  auto xbwd = [&](const std::string& what, const XB& a, long long R, int V) {
+    IN("xent_backward (%lld,%d) stride=%lld reduction=%d %s", R, V, a.stride, a.red, what.c_str());
+    call([&] { return smx_xent_backward(a.g, a.x, a.stride, a.t, -100, a.red, a.lse, a.cnt, a.grad, R, V, nullptr); });
+  };
+  // the row families: 16-byte register rows; scalar register rows (V % 4, or rows off 16 bytes with V <= 1024); streaming
+  // rows (wider than the register rows of their alignment), few and more than the most blocks
+  struct Fam { const char* name; long long R; int V; long long stride; int off; };
+  const Fam fams[] = {{"vec4 rows", 37, 256, 260, 0},       {"vec4 rows, widest", 37, 4096, 4096, 0},
+                      {"scalar rows: V % 4", 37, 255, 300, 0}, {"scalar rows: stride % 4", 37, 256, 257, 0},
+                      {"scalar rows: logits+4", 37, 1024, 1024, 4}, {"streaming: V % 4", 37, 50257, 50260, 0},
+                      {"streaming: stride % 4", 37, 1028, 1029, 0}, {"streaming: V > 4096", 5000, 4100, 4100, 0}};
+  for (const Fam& f : fams)
+    for (int red : {0, 1, 2}) {
+      if (red && &f != &fams[0] && &f != &fams[5]) continue;
+      xfwd(f.name, XF{dp("logits", f.off), f.stride, TG, red, LOSS, LSE, CNT}, f.R, f.V, red == 0 && &f == &fams[0]);
+      xbwd(f.name, XB{G, dp("logits", f.off), f.stride, TG, red, LSE, CNT, GR}, f.R, f.V);
+    }
+  xbwd("grad+4: scalar rows", XB{G, X, 260, TG, 0, LSE, CNT, dp("grad", 4)}, 37, 256);
+  const XF xf{X, 260, TG, 0, LOSS, LSE, CNT};
+  xfwd("row_stride < V", with<XF>([&](XF& a) { a = xf; a.stride = 255; }), 37, 256);
+  xfwd("reduction=3", with<XF>([&](XF& a) { a = xf; a.red = 3; }), 37, 256);
+  xfwd("R=0", xf, 0, 256);
+  xfwd("R=2^31", xf, 1ll << 31, 256);
+  xfwd("logits=0", with<XF>([&](XF& a) { a = xf; a.x = nullptr; }), 37, 256);
+  xfwd("lse=0", with<XF>([&](XF& a) { a = xf; a.lse = nullptr; }), 37, 256);
+  xfwd("logits+2", with<XF>([&](XF& a) { a = xf; a.x = dp("logits", 2); }), 37, 256);
+  xfwd("targets+4", with<XF>([&](XF& a) { a = xf; a.t = dp<long long>("targets", 4); }), 37, 256);
+  const XB xb{G, X, 260, TG, 0, LSE, CNT, GR};
+  xbwd("row_stride < V", with<XB>([&](XB& a) { a = xb; a.stride = 255; }), 37, 256);
+  xbwd("reduction=3", with<XB>([&](XB& a) { a = xb; a.red = 3; }), 37, 256);
+  xbwd("V=0", xb, 37, 0);
+  xbwd("g=0", with<XB>([&](XB& a) { a = xb; a.g = nullptr; }), 37, 256);
+  xbwd("grad=0", with<XB>([&](XB& a) { a = xb; a.grad = nullptr; }), 37, 256);
+  xbwd("grad+2", with<XB>([&](XB& a) { a = xb; a.grad = dp("grad", 2); }), 37, 256);
+  xbwd("targets+4", with<XB>([&](XB& a) { a = xb; a.t = dp<long long>("targets", 4); }), 37, 256);
+  xbwd("grad=logits", with<XB>([&](XB& a) { a = xb; a.grad = X; }), 37, 256);
+
+  IN("sample_supported V=255,256,257");
+  answer(fmt("%d%d%d", smx_sample_supported(255), smx_sample_supported(256), smx_sample_supported(257)));
+  struct Smp {
+    const float* logits = dp("logits"); long long stride = 300; const void* recent = dp<char>("recent"); int tb = 1, n_recent = 8;
+    float temp = 0.8f, top_p = 0.9f; int top_k = 40; float rep = 1.1f, pres = 0.1f, freq = 0.2f; int ascii = 1, ban_cr = 1, run = 4;
+    const float* u = dp("u"); long long* ids = dp<long long>("ids"); float* probs = dp("probs"); long long R = 5; int V = 256;
+  };
+  auto smp = [&](const std::string& what, const Smp& a) {
+    IN("sample_bytes (%lld,%d) stride=%lld token_bytes=%d n_recent=%d %s", a.R, a.V, a.stride, a.tb, a.n_recent, what.c_str());
+    call([&] {
+      return smx_sample_bytes(a.logits, a.stride, a.recent, a.tb, a.n_recent, a.temp, a.top_p, a.top_k, a.rep, a.pres, a.freq,
+                              a.ascii, a.ban_cr, a.run, a.u, a.ids, a.probs, a.R, a.V, nullptr);
+    });
+  };
+#define SMP(stmt) with<Smp>([&](Smp& a) { stmt; })
+  for (int tb : {1, 8})
+    for (int nr : {0, 8})
+      for (int pr : {0, 1})
+        smp(pr ? "probs" : "probs=0", SMP(a.tb = tb; a.n_recent = nr; if (!pr) a.probs = nullptr; if (!nr) a.recent = nullptr));
+  smp("plain: top_k=0 top_p=1 no penalties, flags off, n_recent=65536",
+      SMP(a.top_k = 0; a.top_p = 1.f; a.rep = 1.f; a.pres = a.freq = 0.f; a.ascii = a.ban_cr = a.run = 0; a.n_recent = 65536));
+  smp("R=0", SMP(a.R = 0));
+  smp("V=255", SMP(a.V = 255; a.stride = 255));
+  smp("R=2^31", SMP(a.R = 1ll << 31));
+  smp("logits=0", SMP(a.logits = nullptr));
+  smp("u=0", SMP(a.u = nullptr));
+  smp("row_stride < V", SMP(a.stride = 255));
+  smp("token_bytes=4", SMP(a.tb = 4));
+  smp("n_recent=65537", SMP(a.n_recent = 65537));
+  smp("n_recent=-1", SMP(a.n_recent = -1));
+  smp("recent=0", SMP(a.recent = nullptr));
+  smp("recent+4", SMP(a.tb = 8; a.recent = dp<char>("recent", 4)));
+  smp("ids+4", SMP(a.ids = dp<long long>("ids", 4)));
+  smp("probs+2", SMP(a.probs = dp("probs", 2)));
+  smp("temperature=0", SMP(a.temp = 0.f));
+  smp("temperature=inf", SMP(a.temp = __builtin_inff()));
+  smp("repetition_penalty=0", SMP(a.rep = 0.f));
+  smp("top_p=NaN", SMP(a.top_p = __builtin_nanf("")));
+  smp("presence_penalty=inf", SMP(a.pres = __builtin_inff()));
+  smp("top_k=-1", SMP(a.top_k = -1));
+  smp("max_run_length=-1", SMP(a.run = -1));
+#undef SMP
+}
+
+static void byte_ops() {
+  // smx_byte_supported: 1 <= T <= 4096, 0 <= k <= min(T / 2, 2048), 1 <= W <= 4096
+  for (int T : {0, 1, 2, 512, 513, 4096, 4097}) {
+    IN("byte_supported T=%d: k=-1,0,T/2,T/2+1 x W=0,1,4096,4097", T);
+    std::string v;
+    for (int k : {-1, 0, T / 2, T / 2 + 1}) {
+      for (int W : {0, 1, 4096, 4097}) v += fmt("%d", smx_byte_supported(T, k, W));
+      v += " ";
+    }
+    answer(v);
+  }
+  struct Feat {
+    const void* tokens = dp<char>("tokens"); int tb = 1; long long stride = -1; const float* bands = dp("bands");
+    float *out = dp("out"), *mag = dp("mag"); int B = 2, T = 512, k = 32, W = 96, P = -1;
+  };
+  auto feat = [&](const std::string& what, Feat a) {
+    if (a.stride < 0) a.stride = a.T + 8;
+    if (a.P < 0) a.P = a.T;
+    IN("byte_features (B%d,T%d,k%d,W%d,P%d) token_bytes=%d stride=%lld %s", a.B, a.T, a.k, a.W, a.P, a.tb, a.stride, what.c_str());
+    call([&] { return smx_byte_features(a.tokens, a.tb, a.stride, a.bands, a.out, a.mag, a.B, a.T, a.k, a.W, a.P, nullptr); });
+  };
+#define FEAT(stmt) with<Feat>([&](Feat& a) { stmt; })
+  for (int tb : {1, 8})
+    for (int W : {96, 97})
+      for (int T : {512, 513}) feat("", FEAT(a.tb = tb; a.W = W; a.T = T));
+  for (int B : {1, 2, 600, 1024})                           // chunks per row: many ... one
+    for (int T : {100, 512, 4096})
+      for (int P : {1, T}) feat("", FEAT(a.B = B; a.T = T; a.P = P));
+  feat("k=0 bands=0", FEAT(a.k = 0; a.bands = nullptr));
+  feat("mag=0", FEAT(a.mag = nullptr));
+  for (int k : {1, 3, 4, 5, 64, 128, 255, 256})             // lanes per bin
+    feat("", FEAT(a.k = k));
+  for (int W : {1, 2, 3, 4, 5, 256, 257, 1024, 1028, 4096}) // threads across a row
+    feat("", FEAT(a.W = W));
+  feat("widest", FEAT(a.T = 4096; a.k = 2048; a.W = 4096));
+  feat("T=1", FEAT(a.T = 1; a.k = 0));
+  feat("B=0", FEAT(a.B = 0));
+  feat("k=-1", FEAT(a.k = -1));
+  feat("token_bytes=4", FEAT(a.tb = 4));
+  feat("P=2", FEAT(a.P = 2));
+  feat("k > T/2", FEAT(a.k = 257));
+  feat("tokens=0", FEAT(a.tokens = nullptr));
+  feat("out=0", FEAT(a.out = nullptr));
+  feat("bands=0", FEAT(a.bands = nullptr));
+  feat("row_stride < T", FEAT(a.stride = 511));
+  feat("tokens+4", FEAT(a.tb = 8; a.tokens = dp<char>("tokens", 4)));
+  feat("out+8", FEAT(a.out = dp("out", 8)));
+  feat("bands+2", FEAT(a.bands = dp("bands", 2)));
+  feat("mag+2", FEAT(a.mag = dp("mag", 2)));
+  feat("T=4097", FEAT(a.T = 4097));
+  feat("W=4097", FEAT(a.W = 4097));
+  feat("B*chunks=2^31", FEAT(a.B = 1 << 23; a.T = 4096));
+  feat("B*P*W=2^40", FEAT(a.B = 1 << 20; a.T = 4096; a.W = 256));
+#undef FEAT
+
+  auto bws = [&](const char* what, int B, int P, int W, int k, bool out = true) {
+    IN("byte_workspace_bytes (B%d,P%d,W%d,k%d) %s", B, P, W, k, what);
+    query([&](size_t* n) { return smx_byte_workspace_bytes(B, P, W, k, out ? n : nullptr); });
+  };
+  bws("", 2, 100, 96, 0);
+  bws("", 2, 100, 96, 32);
+  bws("", 2, 100, 96, 100);
+  bws("", 1024, 4096, 4096, 2048);
+  bws("", 3, 1, 96, 32);
+  bws("out=0", 2, 100, 96, 32, false);
+  bws("B=0", 0, 100, 96, 32);
+  bws("k=-1", 2, 100, 96, -1);
+  struct GB {
+    const float *g = dp("g"), *mag = dp("mag"); float* grad = dp("grad_bands"); int n_bands = -1, B = 2, P = 100, W = 96, k = 32;
+  };
+  auto gb = [&](const std::string& what, GB a, bool ws_cases = false, void* ws = WS) {
+    if (a.n_bands < 0) a.n_bands = a.k > 0 ? a.k : 1;
+    const size_t need = sized([&](size_t* n) { return smx_byte_workspace_bytes(a.B, a.P, a.W, a.k, n); });
+    const std::string name = fmt("byte_grad_bands (B%d,P%d,W%d,k%d) n_bands=%d ", a.B, a.P, a.W, a.k, a.n_bands) + what;
+    auto f = [&](void* w, size_t n) {
+      return smx_byte_grad_bands(a.g, a.mag, a.grad, a.n_bands, w, n, a.B, a.P, a.W, a.k, nullptr);
+    };
+    if (ws_cases) return with_ws(name.c_str(), need, f);
+    IN("%s", name.c_str());
+    call([&] { return f(ws, need); });
+  };
+#define GBA(stmt) with<GB>([&](GB& a) { stmt; })
+  gb("", GB{}, true);
+  gb("k=0: ws=0 mag=0", GBA(a.k = 0; a.mag = nullptr), false, nullptr);
+  gb("W=1: min(k, W) = 1", GBA(a.W = 1));
+  for (int k : {63, 64, 65, 200}) gb("", GBA(a.k = k; a.W = 4096));
+  gb("min(k, W) = W", GBA(a.k = 100));
+  gb("n_bands > k", GBA(a.n_bands = 300));
+  gb("n_bands > k", GBA(a.n_bands = 257));
+  gb("P=1", GBA(a.P = 1; a.B = 3));
+  gb("P=64", GBA(a.P = 64));
+  gb("P=65", GBA(a.P = 65));
+  gb("B=0", GBA(a.B = 0));
+  gb("k=-1", GBA(a.k = -1; a.n_bands = 1));
+  gb("n_bands < min(k, W)", GBA(a.n_bands = 31));
+  gb("n_bands=0", GBA(a.k = 0; a.n_bands = 0));
+  gb("g=0", GBA(a.g = nullptr));
+  gb("grad_bands=0", GBA(a.grad = nullptr));
+  gb("mag=0", GBA(a.mag = nullptr));
+  gb("g+2", GBA(a.g = dp("g", 2)));
+  gb("grad_bands+2", GBA(a.grad = dp("grad_bands", 2)));
+  gb("B*P=2^31", GBA(a.B = 1 << 20; a.P = 1 << 17));
+#undef GBA
+}
+
+static void match_ops() {
+  // smx_match_supported: 1 <= S <= 256, 4 <= L <= 256, S L <= 32768 (32769 = 9 * 11 * 331 has no such pair: 99 x 331)
+  IN("match_supported S=0,1,128,129,256,257 x L=3,4,128,255,256,257; (99,331)");
+  {
+    std::string v;
+    for (int S : {0, 1, 128, 129, 256, 257}) {
+      for (int L : {3, 4, 128, 255, 256, 257}) v += fmt("%d", smx_match_supported(S, L));
+      v += " ";
+    }
+    answer(v + fmt("%d", smx_match_supported(99, 331)));
+  }
+  auto mws = [&](const char* what, int S, int L, bool out = true) {
+    IN("match_workspace_bytes (S%d,L%d) %s", S, L, what);
+    query([&](size_t* n) { return smx_match_workspace_bytes(S, L, out ? n : nullptr); });
+  };
+  mws("", 1, 4);
+  mws("", 8, 16);
+  mws("", 128, 256);
+  mws("", 256, 128);
+  mws("out=0", 8, 16, false);
+  mws("S*L=33024", 129, 256);
+  mws("L=3", 8, 3);
+  struct Mt {
+    const void* corpus = dp<char>("corpus"); long long n = 1000; const void* snips = dp<char>("snips"); int S = 8, L = 16;
+    long long* first = dp<long long>("first"); int max_wg = 0;
+  };
+  auto mt = [&](const std::string& what, const Mt& a, bool ws_cases = false) {
+    const size_t need = sized([&](size_t* n) { return smx_match_workspace_bytes(a.S, a.L, n); });
+    const std::string name = fmt("match_first n=%lld (S%d,L%d) max_workgroups=%d ", a.n, a.S, a.L, a.max_wg) + what;
+    auto f = [&](void* ws, size_t n) { return smx_match_first(a.corpus, a.n, a.snips, a.S, a.L, a.first, ws, n, a.max_wg, nullptr); };
+    if (ws_cases) return with_ws(name.c_str(), need, f);
+    IN("%s", name.c_str());
+    call([&] { return f(WS, need); });
+  };
+#define MT(stmt) with<Mt>([&](Mt& a) { stmt; })
+  mt("one tile", Mt{}, true);
+  mt("corpus=0: the join alone", MT(a.n = 0; a.corpus = nullptr));
+  mt("n < L: the join alone", MT(a.n = 15));
+  mt("n = L", MT(a.n = 16));
+  mt("a full tile", MT(a.n = 16384 + 15));
+  mt("one position more", MT(a.n = 16384 + 16));
+  mt("off + npos = 16384", MT(a.n = 16394; a.corpus = dp<char>("corpus", 5)));
+  mt("off + npos = 16385: a second tile", MT(a.n = 16395; a.corpus = dp<char>("corpus", 5)));
+  mt("the same corpus at offset 0: one tile", MT(a.n = 16395));
+  mt("corpus+15", MT(a.n = 100; a.corpus = dp<char>("corpus", 15)));
+  for (int mw : {0, 1, 2, 2000}) mt("3000 tiles", MT(a.n = 3000ll * 16384; a.max_wg = mw));
+  for (long long tiles : {1023, 1024, 1025, 2049})            // around one resident round of four workgroups per CU
+    mt(fmt("%lld tiles", tiles), MT(a.n = tiles * 16384));
+  // LDS per workgroup: 30976 + S L bytes of 160 KiB: four, three and two workgroups per CU
+  const int sls[][2] = {{8, 16}, {128, 160}, {128, 256}, {1, 4}, {256, 128}, {3, 5}};
+  for (const auto& sl : sls) mt("3000 tiles: workgroups per CU", MT(a.n = 3000ll * 16384; a.S = sl[0]; a.L = sl[1]));
+  mt("L=3", MT(a.L = 3));
+  mt("S=257", MT(a.S = 257));
+  mt("n=-1", MT(a.n = -1));
+  mt("snips=0", MT(a.snips = nullptr));
+  mt("first=0", MT(a.first = nullptr));
+  mt("corpus=0", MT(a.corpus = nullptr));
+  mt("first+4", MT(a.first = dp<long long>("first", 4)));
+  mt("max_workgroups=-1", MT(a.max_wg = -1));
+#undef MT
+}
+
+static void sst_ops() {
+  const long long TILE = 4096, NMAX = (1ll << 31) - 1;
+  IN("topk_supported n=-1,0,1,2^31-1,2^31");
+  answer(fmt("%d%d%d%d%d", smx_topk_supported(-1), smx_topk_supported(0), smx_topk_supported(1), smx_topk_supported(NMAX),
+             smx_topk_supported(NMAX + 1)));
+  auto tws = [&](const char* what, long long n, bool out = true) {
+    IN("topk_workspace_bytes n=%lld %s", n, what);
+    query([&](size_t* w) { return smx_topk_workspace_bytes(n, out ? w : nullptr); });
+  };
+  for (long long n : {1ll, TILE - 2, TILE - 1, TILE, 511 * TILE - 1, 511 * TILE, 512 * TILE, 600 * TILE, NMAX}) tws("", n);
+  tws("out=0", 1000, false);
+  tws("n=0", 0);
+  tws("n=2^31", NMAX + 1);
+  struct Tk {
+    const void* z = dp<char>("z"); long long n = 10000, k = 100; long long* result = dp<long long>("result");
+    void* coeffs = dp<char>("coeffs"); long long* flat_idx = dp<long long>("flat_idx"); long long capacity = 128; int max_wg = 0;
+  };
+  auto need_of = [&](long long n) { return sized([&](size_t* w) { return smx_topk_workspace_bytes(n, w); }); };
+  auto sel = [&](const std::string& what, const Tk& a, bool ws_cases = false) {
+    const std::string name = fmt("topk_select n=%lld k=%lld max_workgroups=%d ", a.n, a.k, a.max_wg) + what;
+    auto f = [&](void* ws, size_t w) { return smx_topk_select(a.z, a.n, a.k, a.result, ws, w, a.max_wg, nullptr); };
+    if (ws_cases) return with_ws(name.c_str(), need_of(a.n), f);
+    IN("%s", name.c_str());
+    call([&] { return f(WS, need_of(a.n)); });
+  };
+  auto cmp = [&](const std::string& what, const Tk& a, bool ws_cases = false) {
+    const std::string name = fmt("topk_compact n=%lld capacity=%lld max_workgroups=%d ", a.n, a.capacity, a.max_wg) + what;
+    auto f = [&](void* ws, size_t w) {
+      return smx_topk_compact(a.z, a.n, a.result, a.coeffs, a.flat_idx, a.capacity, ws, w, a.max_wg, nullptr);
+    };
+    if (ws_cases) return with_ws(name.c_str(), need_of(a.n), f);
+    IN("%s", name.c_str());
+    call([&] { return f(WS, need_of(a.n)); });
+  };
+#define TK(stmt) with<Tk>([&](Tk& a) { stmt; })
+  sel("", Tk{}, true);
+  cmp("", Tk{}, true);
+  cmp("capacity=0: nothing launched", TK(a.capacity = 0; a.coeffs = nullptr; a.flat_idx = nullptr), true);
+  for (long long n : {1ll, 3 * TILE, 512 * TILE, 513 * TILE, 600 * TILE, 1024 * TILE, 1025 * TILE, 2500 * TILE, NMAX}) {
+    sel("", TK(a.n = n; a.k = n == 1 ? 1 : n / 2));
+    cmp("", TK(a.n = n));
+  }
+  // z 8 bytes past a 16-byte boundary: off = 1, one tile more where n fills its tiles
+  for (long long n : {1ll, 3 * TILE - 1, 3 * TILE, 512 * TILE}) {
+    sel("z+8", TK(a.n = n; a.k = 1; a.z = dp<char>("z", 8)));
+    cmp("z+8", TK(a.n = n; a.z = dp<char>("z", 8)));
+  }
+  for (int mw : {1, 3, 5000}) {
+    sel("", TK(a.n = 600 * TILE; a.max_wg = mw));
+    cmp("", TK(a.n = 600 * TILE; a.max_wg = mw));
+  }
+  sel("k=n", TK(a.k = a.n));
+  sel("n=0", TK(a.n = 0));
+  sel("n=2^31", TK(a.n = NMAX + 1));
+  sel("z=0", TK(a.z = nullptr));
+  sel("result=0", TK(a.result = nullptr));
+  sel("k=0", TK(a.k = 0));
+  sel("k=n+1", TK(a.k = a.n + 1));
+  sel("z+4", TK(a.z = dp<char>("z", 4)));
+  sel("result+4", TK(a.result = dp<long long>("result", 4)));
+  sel("max_workgroups=-1", TK(a.max_wg = -1));
+  cmp("n=0", TK(a.n = 0));
+  cmp("capacity=-1", TK(a.capacity = -1));
+  cmp("z=0", TK(a.z = nullptr));
+  cmp("result=0", TK(a.result = nullptr));
+  cmp("coeffs=0", TK(a.coeffs = nullptr));
+  cmp("flat_idx=0", TK(a.flat_idx = nullptr));
+  cmp("z+4", TK(a.z = dp<char>("z", 4)));
+  cmp("coeffs+4", TK(a.coeffs = dp<char>("coeffs", 4)));
+  cmp("flat_idx+4", TK(a.flat_idx = dp<long long>("flat_idx", 4)));
+  cmp("max_workgroups=-1", TK(a.max_wg = -1));
+#undef TK
+
+  struct Sc {
+    const void* coeffs = dp<char>("coeffs"); const long long* flat_idx = dp<long long>("flat_idx"); long long m = 100;
+    void* out = dp<char>("out"); long long n = 10 * 4096 + 5; int max_wg = 0;
+  };
+  auto sc = [&](const std::string& what, const Sc& a) {
+    IN("sparse_scatter m=%lld n=%lld max_workgroups=%d %s", a.m, a.n, a.max_wg, what.c_str());
+    call([&] { return smx_sparse_scatter(a.coeffs, a.flat_idx, a.m, a.out, a.n, a.max_wg, nullptr); });
+  };
+#define SC(stmt) with<Sc>([&](Sc& a) { stmt; })
+  sc("", Sc{});
+  sc("m=0 coeffs=0 flat_idx=0", SC(a.m = 0; a.coeffs = nullptr; a.flat_idx = nullptr));
+  sc("m=n", SC(a.m = a.n));
+  for (long long n : {1ll, TILE, TILE + 1, 2048 * TILE, 2048 * TILE + 1, 5000 * TILE, NMAX}) sc("", SC(a.n = n; a.m = 1));
+  for (int mw : {1, 3, 5000}) sc("", SC(a.n = 5000 * TILE; a.max_wg = mw));
+  sc("n=0", SC(a.n = 0; a.m = 0));
+  sc("n=2^31", SC(a.n = NMAX + 1));
+  sc("m=-1", SC(a.m = -1));
+  sc("m=n+1", SC(a.m = a.n + 1));
+  sc("out=0", SC(a.out = nullptr));
+  sc("coeffs=0", SC(a.coeffs = nullptr));
+  sc("flat_idx=0", SC(a.flat_idx = nullptr));
+  sc("out+8", SC(a.out = dp<char>("out", 8)));
+  sc("coeffs+4", SC(a.coeffs = dp<char>("coeffs", 4)));
+  sc("flat_idx+4", SC(a.flat_idx = dp<long long>("flat_idx", 4)));
+  sc("max_workgroups=-1", SC(a.max_wg = -1));
+#undef SC
+}
+
+static void newer_ops() {
+  g_last_shape.clear(), puts("## newer ops");
+  word_targets_and_head();
+  xent_and_sampler();
+  byte_ops();
+  match_ops();
+  sst_ops();
+}
+
 // ---- plans ------------------------------------------------------------------------------------------------------------
 // plan = path L bands nsplit workgroups groups, the workspace size, sup = row_scale io(bf16) io(f32) block_io(f16)
 // block_io(f32); conv (which does not look at F or k) = workspace and save bytes, the cfft workspace, conv conv_io(bf16)
@@ -1104,5 +1621,6 @@ int main(int argc, char** argv) {
   convolution();
   small_ops();
   refusals();
+  newer_ops();
   return 0;
 }

@@ -8,7 +8,7 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 CSRC=${SMX_TRACE_CSRC:-../../tensor-cuda-fft-_amd/csrc}
 OUT=${SMX_TRACE_OUT:-api_trace}
-UNITS="smx_decim smx_fourstep smx_fourstep2 smx_conv1 smx_direct smx_block smx_enh smx_time smx_ema smx_stream smx_api"
+UNITS="smx_decim smx_fourstep smx_fourstep2 smx_conv1 smx_direct smx_block smx_enh smx_time smx_ema smx_stream smx_byte smx_match smx_sst smx_api"
 stale=0
 [ -f "$OUT" ] || stale=1
 for f in api_trace.hip build.sh ../../include/smx.h "$CSRC"/*.h "$CSRC"/*.hip; do
@@ -19,7 +19,7 @@ if [ $stale = 1 ]; then
   trap 'rm -rf "$OBJ"' EXIT
   FLAGS="--cuda-host-only -O1 -std=c++17 -I $CSRC -I ../../include"
   PIDS=""
-  for u in $UNITS; do                     # eleven units + the program: twelve jobs
+  for u in $UNITS; do                     # fourteen units + the program: fifteen jobs
     $HIPCC $FLAGS -c "$CSRC/$u.hip" -o "$OBJ/$u.o" &
     PIDS="$PIDS $!"
   done
