@@ -1,170 +1,97 @@
-"""ctypes binding of libsmx.so (include/smx.h).  No CPU fallback: if the library is missing the
-import of the product path fails with a build hint."""
+"""ctypes binding of libsmx.so, derived from include/smx.h when this module is imported: the entry points' signatures,
+the fields of the three structs and the SMX_* constants are read from the header's text, so an entry point is declared
+there and nowhere else on the Python side.  No CPU fallback: if the library is missing the import of the product path
+fails with a build hint."""
 from __future__ import annotations
 
 import ctypes
 import os
+import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SMX_LIB selects an experimental build of the same ABI (tuning only)
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "csrc", "libsmx.so")
-
-SMX_PATH_DECIMATED = 1
-SMX_PATH_DIRECT = 2
-SMX_PATH_DECIM16 = 3
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "smx.h")      # the layout csrc/build.sh relies on too
 
 
 class SmxError(RuntimeError):
     pass
 
 
-class smx_plan(ctypes.Structure):
-    _fields_ = [("path", ctypes.c_int), ("k", ctypes.c_int), ("L", ctypes.c_int),
-                ("bands", ctypes.c_int), ("nsplit", ctypes.c_int), ("workgroups", ctypes.c_int),
-                ("groups", ctypes.c_int)]
+class smx_plan(ctypes.Structure):           # the _fields_ of these three are the header's (below)
+    pass
 
 
 class smx_options(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("nsplit", "placement", "round", "force_direct", "full8", "fourstep",
-                                            "fs_bgroups", "fold_gradw", "decim16", "conv1", "st_plain")]
+    pass
 
 
 class smx_shape(ctypes.Structure):
-    _fields_ = [("B", ctypes.c_int), ("rows", ctypes.c_int), ("D", ctypes.c_int), ("F", ctypes.c_int),
-                ("n_fft", ctypes.c_int), ("k", ctypes.c_int)]
+    pass
 
 
 _lock = threading.Lock()
 _lib = None
 
 _P = ctypes.c_void_p
-_I = ctypes.c_int
-_LL = ctypes.c_longlong
 _SZ = ctypes.c_size_t
 
-_SIGS = {
-    "smx_version": (ctypes.c_int, []),
-    "smx_last_error": (ctypes.c_char_p, []),
-    "smx_set_option": (_I, [ctypes.c_char_p, _I]),
-    "smx_options_default": (_I, [_P]),
-    "smx_options_push": (_I, [_P]),
-    "smx_options_pop": (_I, []),
-    "smx_options_epoch": (ctypes.c_ulonglong, []),
-    "smx_tables_epoch": (ctypes.c_ulonglong, []),
-    "smx_build_flags": (ctypes.c_char_p, []),
-    "smx_diag_clock": (_I, [_P, _I, _P]),
-    "smx_plan_query": (_I, [_I, _I, _I, _I, ctypes.POINTER(smx_plan)]),
-    "smx_workspace_bytes": (_I, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
-    "smx_prepare": (_I, [_I]),
-    "smx_forward": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, _P]),
-    "smx_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, _P]),
-    "smx_spectrum": (_I, [_P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
-    "smx_grad_w": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "smx_wfilter_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "smx_wfilter_grad_w": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "smx_cmul": (_I, [_P, _P, _P, _LL, _LL, _I, _P]),
-    "smx_cmul_grad_w": (_I, [_P, _P, _P, _LL, _LL, _P]),
-    "smx_rng_next": (_I, [_P, _P, _P]),
-    "smx_forward_dropout": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, ctypes.c_float,
-                                 _P, _P, _P]),
-    "smx_backward_dropout": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I,
-                                  ctypes.c_float, _P, _P, _P]),
-    "smx_block_forward_dropout": (_I, [_P, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _SZ,
-                                       _I, _I, _I, _I, ctypes.c_float, _P, _P, _P]),
-    "smx_block_backward_dropout": (_I, [_P] * 14 + [_SZ, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P]),
-    "smx_block_supported": (_I, [_I]),
-    "smx_plan_query_ex": (_I, [ctypes.POINTER(smx_shape), ctypes.POINTER(smx_plan)]),
-    "smx_workspace_bytes_ex": (_I, [ctypes.POINTER(smx_shape), ctypes.POINTER(_SZ)]),
-    "smx_forward_ex": (_I, [ctypes.POINTER(smx_shape), _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P]),
-    "smx_backward_ex": (_I, [ctypes.POINTER(smx_shape), _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _P,
-                             _P, _P, _P]),
-    "smx_row_scale_supported": (_I, [ctypes.POINTER(smx_shape)]),
-    "smx_cfft_ex": (_I, [ctypes.POINTER(smx_shape), _P, _P, _P, _SZ, _P]),
-    "smx_rfft_ex": (_I, [ctypes.POINTER(smx_shape), _P, _P, ctypes.c_float, _I, _P, _SZ, _P]),
-    "smx_irfft_ex": (_I, [ctypes.POINTER(smx_shape), _P, _P, ctypes.c_float, _I, _P, _SZ, _P]),
-    "smx_cfft_workspace_bytes": (_I, [ctypes.POINTER(smx_shape), ctypes.POINTER(_SZ)]),
-    "smx_conv_supported": (_I, [ctypes.POINTER(smx_shape)]),
-    "smx_conv_workspace_bytes": (_I, [ctypes.POINTER(smx_shape), ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
-    "smx_conv_forward": (_I, [ctypes.POINTER(smx_shape), _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
-    "smx_conv_backward": (_I, [ctypes.POINTER(smx_shape), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
-    "smx_phase_filter": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
-    "smx_phase_filter_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    "smx_conv_response": (_I, [_I, _I, _P, _P, _P, _P, _P, _P]),
-    "smx_conv_response_backward": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "smx_spectrum_ex": (_I, [ctypes.POINTER(smx_shape), _P, _P, _P, _SZ, _P]),
-    "smx_block_forward": (_I, [_P, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _SZ,
-                               _I, _I, _I, _I, _P]),
-    "smx_block_backward": (_I, [_P] * 14 + [_SZ, _I, _I, _I, _I, _I, _P]),
-    "smx_dwconv3_workspace_bytes": (_I, [_I, _I, _I, ctypes.POINTER(_SZ)]),
-    "smx_dwconv3_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "smx_dwconv3_backward": (_I, [_P] * 10 + [_SZ, _I, _I, _I, _P]),
-    "smx_spectral_ln_supported": (_I, [_I]),
-    "smx_spectral_ln_forward": (_I, [_P, _P, _P, ctypes.c_float, _P, _I, _I, _I, _I, _P]),
-    "smx_spectral_ln_backward": (_I, [_P, _P, _P, _P, ctypes.c_float, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "smx_planar_cmul_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    "smx_planar_cmul_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "smx_planar_add": (_I, [_P, _P, _P, _LL, _P]),
-    "smx_planar_split": (_I, [_P, _P, _LL, _P]),
-    "smx_spectral_gate_workspace_bytes": (_I, [_I, _I, _I, ctypes.POINTER(_SZ)]),
-    "smx_spectral_gate_forward": (_I, [_P] * 7 + [_I, _I, _I, _P]),
-    "smx_spectral_gate_backward": (_I, [_P] * 12 + [_SZ, _I, _I, _I, _P]),
-    "smx_mix_workspace_bytes": (_I, [ctypes.POINTER(_SZ)]),
-    "smx_mix_forward": (_I, [_P] * 5 + [ctypes.c_float, _P, _LL, _P]),
-    "smx_mix_backward": (_I, [_P] * 4 + [ctypes.c_float] + [_P] * 5 + [_SZ, _LL, _P]),
-    "smx_enh_supported": (_I, [_I]),
-    "smx_enh_workspace_bytes": (_I, [_I, _I, _I, ctypes.POINTER(_SZ)]),
-    "smx_rope_norm_forward": (_I, [_P, _P, _I] + [_P] * 4 + [ctypes.c_float] * 2 + [_P] * 3
-                              + [_I] * 4 + [ctypes.c_float, _P, _P]),
-    "smx_rope_norm_backward": (_I, [_P] * 4 + [_I] + [_P] * 10 + [_SZ] + [_I] * 4 + [ctypes.c_float, _P, _P]),
-    "smx_residual_norm_forward": (_I, [_P] * 4 + [ctypes.c_float] + [_P] * 3 + [_I] * 3 + [ctypes.c_float, _P, _P]),
-    "smx_residual_norm_backward": (_I, [_P] * 10 + [_SZ] + [_I] * 3 + [ctypes.c_float, _P, _P]),
-    "smx_gate_blend_forward": (_I, [_P] * 5 + [ctypes.c_float] + [_P] * 2 + [_I] * 3 + [ctypes.c_float, _P, _P]),
-    "smx_gate_blend_backward": (_I, [_P] * 11 + [_SZ] + [_I] * 3 + [ctypes.c_float, _P, _P]),
-    "smx_io_supported": (_I, [_I] * 5),
-    "smx_forward_io": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I]),
-    "smx_backward_io": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, ctypes.c_float,
-                             _P, _P, _P, _I]),
-    "smx_conv_io_supported": (_I, [ctypes.POINTER(smx_shape), _I]),
-    "smx_conv_forward_io": (_I, [ctypes.POINTER(smx_shape), _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _P]),
-    "smx_conv_backward_io": (_I, [ctypes.POINTER(smx_shape), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _P]),
-    "smx_block_io_supported": (_I, [_I] * 5),
-    "smx_block_forward_io": (_I, [_P, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _SZ,
-                                  _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I]),
-    "smx_block_backward_io": (_I, [_P] * 15 + [_SZ, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I]),
-    "smx_ema_workspace_bytes": (_I, [_I, _I, _I, ctypes.POINTER(_SZ)]),
-    "smx_ema_scan_forward": (_I, [_P] * 5 + [_I] * 4 + [_P]),
-    "smx_ema_scan_backward": (_I, [_P] * 10 + [_SZ] + [_I] * 4 + [_P]),
-    "smx_ema_tokens_forward": (_I, [_P, _I, _LL] + [_P] * 4 + [_I] * 4 + [_P]),
-    "smx_ema_tokens_backward": (_I, [_P, _P, _I, _LL] + [_P] * 7 + [_SZ] + [_I] * 4 + [_P]),
-    "smx_word_targets": (_I, [_P, _I, _LL, _P, _P, _I, _I, _P]),
-    "smx_head_supported": (_I, [_I, _I]),
-    "smx_head_workspace_bytes": (_I, [_LL, _I, _I, ctypes.POINTER(_SZ)]),
-    "smx_head_forward": (_I, [_P] * 4 + [_LL, _I, _I, _P]),
-    "smx_head_backward": (_I, [_P] * 7 + [_SZ, _LL, _I, _I, _P]),
-    "smx_xent_supported": (_I, [_I]),
-    "smx_xent_workspace_bytes": (_I, [_LL, _I, ctypes.POINTER(_SZ)]),
-    "smx_xent_forward": (_I, [_P, _LL, _P, _LL, _I] + [_P] * 4 + [_SZ, _LL, _I, _P]),
-    "smx_xent_backward": (_I, [_P, _P, _LL, _P, _LL, _I] + [_P] * 3 + [_LL, _I, _P]),
-    "smx_stream_supported": (_I, [_I] * 4),
-    "smx_stream_push": (_I, [_P] * 3 + [ctypes.c_float] + [_P] * 4 + [_I] * 4 + [_P]),
-    "smx_stream_conv": (_I, [_P] * 7 + [ctypes.c_float] + [_P] * 2 + [_I] * 5 + [_P]),
-    "smx_sample_supported": (_I, [_I]),
-    "smx_sample_bytes": (_I, [_P, _LL, _P, _I, _I, ctypes.c_float, ctypes.c_float, _I] + [ctypes.c_float] * 3
-                         + [_I] * 3 + [_P] * 3 + [_LL, _I, _P]),
-    "smx_byte_supported": (_I, [_I] * 3),
-    "smx_byte_features": (_I, [_P, _I, _LL, _P, _P, _P] + [_I] * 5 + [_P]),
-    "smx_byte_workspace_bytes": (_I, [_I] * 4 + [ctypes.POINTER(_SZ)]),
-    "smx_byte_grad_bands": (_I, [_P, _P, _P, _I, _P, _SZ] + [_I] * 4 + [_P]),
-    "smx_match_supported": (_I, [_I, _I]),
-    "smx_match_workspace_bytes": (_I, [_I, _I, ctypes.POINTER(_SZ)]),
-    "smx_match_first": (_I, [_P, _LL, _P, _I, _I, _P, _P, _SZ, _I, _P]),
-    "smx_topk_supported": (_I, [_LL]),
-    "smx_topk_workspace_bytes": (_I, [_LL, ctypes.POINTER(_SZ)]),
-    "smx_topk_select": (_I, [_P, _LL, _LL, _P, _P, _SZ, _I, _P]),
-    "smx_topk_compact": (_I, [_P, _LL, _P, _P, _P, _LL, _P, _SZ, _I, _P]),
-    "smx_sparse_scatter": (_I, [_P, _P, _LL, _P, _LL, _I, _P]),
-}
+# the header's vocabulary: scalar types, and the pointers that are not a plain address (what stands before the `*`)
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "size_t": _SZ, "float": ctypes.c_float,
+            "unsigned long long": ctypes.c_ulonglong}
+_POINTERS = {"const char": ctypes.c_char_p, "smx_plan": ctypes.POINTER(smx_plan),
+             "const smx_shape": ctypes.POINTER(smx_shape), "size_t": ctypes.POINTER(_SZ)}
+_STRUCT = re.compile(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;")
+
+
+def _ctype(entry: str, decl: str):
+    """`decl`: a result type, or one parameter with or without its name"""
+    words = decl.replace("*", " * ").split()
+    if "*" in words:
+        return _POINTERS.get(" ".join(words[:words.index("*")]), _P)
+    for cand in (words, words[:-1]):
+        if " ".join(cand) in _SCALARS:
+            return _SCALARS[" ".join(cand)]
+    raise SmxError(f"smx.h: {entry}: the type {' '.join(words[:-1] or words)!r} is not one the binding knows "
+                   f"({', '.join(_SCALARS)}, or a pointer): teach _lib._SCALARS before declaring it.")
+
+
+def read_header(text: str):
+    """(prototypes {entry: (restype, [argtypes])}, integer defines {SMX_NAME: value}, struct fields {struct: [names]})
+    of the header's text.  No C parser: comments go first (they hold `smx_...(` and parentheses), then the preprocessor
+    lines and the typedef'd structs (int fields only, several declarators a line), and what is left is prototypes:
+    `type smx_name(parameters);` over any number of lines, (void) for none, types from the vocabulary above."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    defines = {n: int(v) for n, v in
+               re.findall(r"^[ \t]*#[ \t]*define[ \t]+(SMX_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    structs = {}
+    for body, name in _STRUCT.findall(text):
+        decls = [d.split(None, 1) for d in body.split(";") if d.strip()]
+        for d in decls:
+            if d[0] != "int" or len(d) != 2 or not re.fullmatch(r"[\w\s,]+", d[1]):
+                raise SmxError(f"smx.h: struct {name}: the field {' '.join(d)!r} is not a plain int")
+        structs[name] = [f for d in decls for f in d[1].replace(",", " ").split()]
+    sigs = {}
+    for res, name, params in re.findall(r"([\w\s*]+?)\b(smx_\w+)\s*\(([^()]*)\)\s*;", _STRUCT.sub("", text)):
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        sigs[name] = (_ctype(name, res), [_ctype(name, p) for p in params])
+    return sigs, defines, structs
+
+
+def _read_header_file():
+    if not os.path.exists(HEADER_PATH):
+        raise SmxError(f"{HEADER_PATH} not found: the ctypes binding is read from the C header, which the source tree "
+                       f"keeps beside the package directory. There is no built-in copy of the signatures.")
+    with open(HEADER_PATH) as f:
+        return read_header(f.read())
+
+
+_SIGS, _DEFINES, _FIELDS = _read_header_file()
+for _s in (smx_plan, smx_options, smx_shape):
+    _s._fields_ = [(n, ctypes.c_int) for n in _FIELDS[_s.__name__]]
+globals().update(_DEFINES)                  # SMX_PATH_*, SMX_IO_*, SMX_PHASE_*, SMX_ERR_* ...: every integer #define
 
 
 _SINCE = {"smx_diag_clock": 302, "smx_dwconv3_workspace_bytes": 302, "smx_dwconv3_forward": 302,
@@ -230,9 +157,6 @@ def plan(B: int, N: int, D: int, F: int) -> smx_plan:
     p = smx_plan()
     check(lib().smx_plan_query(B, N, D, F, ctypes.byref(p)))
     return p
-
-
-SMX_IO_F32, SMX_IO_BF16, SMX_IO_F16 = 0, 1, 2       # include/smx.h: element type of x / y / g / grad_x
 
 
 def io_supported(B: int, N: int, D: int, F: int, io: int) -> bool:

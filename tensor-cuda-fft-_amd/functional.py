@@ -33,8 +33,7 @@ def _under_forward_options(backward):
 
 
 # element type of the streamed x / y / g / grad_x (include/smx.h SMX_IO_*): arithmetic stays fp32 on every one
-_IO = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-
+_IO = {torch.float32: _lib.SMX_IO_F32, torch.bfloat16: _lib.SMX_IO_BF16, torch.float16: _lib.SMX_IO_F16}
 
 _F32 = (torch.float32,)
 _C64 = (torch.complex64,)
@@ -316,7 +315,7 @@ _io_cache = _Memo()
 
 
 def forward_raw(x, w_re, w_im, bias, *, conj_w=False, save_spectrum=False, dropout_p=0.0, rng=None,
-                pack=None, pack_ready=False, ws=None, io=0):
+                pack=None, pack_ready=False, ws=None, io=_lib.SMX_IO_F32):
     """y, xk = smx_forward[_dropout](...).  x (B,N,D) contiguous f32 on GPU; returns xk (B,k,D) c64 or
     None.  rng: the int64[2] device tensor from DropoutState.next() when dropout_p > 0.  pack: (k,D)
     complex64 tensor that receives the packed filter (hand it to backward_raw to skip its packing launch);
@@ -332,8 +331,8 @@ def forward_raw(x, w_re, w_im, bias, *, conj_w=False, save_spectrum=False, dropo
     if ws is None:
         ws = _workspace(x.device, _ws_bytes(B, N, D, F))
     args = (x.data_ptr(), w_re.data_ptr(), w_im.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(xk), *_ws_arg(ws),
-            B, N, D, F, int(bool(conj_w)) | (2 if pack_ready else 0), float(dropout_p), _ptr(rng), _ptr(pack),
-            _stream(x.device))
+            B, N, D, F, int(bool(conj_w)) | (_lib.SMX_FILTER_PACK_READY if pack_ready else 0), float(dropout_p),
+            _ptr(rng), _ptr(pack), _stream(x.device))
     # (2-byte rows through the _io entry, f32 through the f32 entry: the tests tell the routes apart by the call)
     if io:
         _call(x.device, "smx_forward_io", *args, int(io))
@@ -342,11 +341,12 @@ def forward_raw(x, w_re, w_im, bias, *, conj_w=False, save_spectrum=False, dropo
     return y, xk
 
 
-PHASE_SPECTRUM, PHASE_INVERSE, PHASE_PARAMS, PHASE_ALL = 1, 2, 4, 7     # include/smx.h
+PHASE_SPECTRUM, PHASE_INVERSE, PHASE_PARAMS = _lib.SMX_PHASE_SPECTRUM, _lib.SMX_PHASE_INVERSE, _lib.SMX_PHASE_PARAMS
+PHASE_ALL = _lib.SMX_PHASE_ALL
 
 
 def backward_raw(g, xk, w_re, w_im, *, want_x=True, want_w=True, phases=PHASE_ALL, grad_x=None,
-                 flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, io=0):
+                 flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, io=_lib.SMX_IO_F32):
     """Runs smx_backward.  Returns (grad_x, flat) where flat = [gw_re | gw_im | gbias] fp32.
     `ws`: workspace of an earlier phase (a call made on another stream must not pick that stream's), or the
     workspace the forward call of the same autograd node used.
@@ -524,7 +524,7 @@ def spectral_mix(x: torch.Tensor, weight_real: torch.Tensor, weight_imag: torch.
 
 
 def block_forward_raw(x, ln_w, ln_b, eps, w_re, w_im, bias, *, save=True, dropout_p=0.0, rng=None,
-                      pack=None, ws=None, io=0):
+                      pack=None, ws=None, io=_lib.SMX_IO_F32):
     """y, xk, stats = smx_block_forward(...): y = x + mix(LayerNorm(x)); stats (B,N,2) = (mean, rstd).
     io: element type of x and y (SMX_IO_BF16 / SMX_IO_F16: bf16 / fp16 x, 8-byte aligned, on a shape with
     _lib.block_io_supported; y comes back in x's dtype, xk and stats stay fp32)."""
@@ -548,7 +548,7 @@ def block_forward_raw(x, ln_w, ln_b, eps, w_re, w_im, bias, *, save=True, dropou
 
 
 def block_backward_raw(g, x, stats, ln_w, xk, w_re, w_im, *, phases=PHASE_ALL, grad_x=None,
-                       flat=None, ln_flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, io=0,
+                       flat=None, ln_flat=None, ws=None, dropout_p=0.0, rng=None, pack=None, io=_lib.SMX_IO_F32,
                        grad_h=None):
     """Runs smx_block_backward.  Returns (grad_x, flat, ln_flat): flat = [gw_re | gw_im | gbias],
     ln_flat = [g_ln_w | g_ln_b].
@@ -1712,7 +1712,7 @@ def gate_blend(a: torch.Tensor, v: torch.Tensor, x2: Optional[torch.Tensor], wg,
 
 
 # ---- SpectralEMA: the chunk head's state-space memory as one scan launch (csrc/smx_ema.hip) ---------------------------
-EMA_MODES = {"aligned": 0, "polar": 1}                      # include/smx.h SMX_EMA_*
+EMA_MODES = {"aligned": _lib.SMX_EMA_ALIGNED, "polar": _lib.SMX_EMA_POLAR}
 
 
 def _ema_mode(mode: str) -> int:
@@ -1748,7 +1748,7 @@ class _EmaScan(torch.autograd.Function):
         need = ctx.needs_input_grad
         gx = torch.empty_like(chunks) if need[0] else None
         gr = torch.empty_like(rho_logit) if need[1] else None
-        gt = torch.empty_like(theta_raw) if need[2] and ctx.mode == 0 else None
+        gt = torch.empty_like(theta_raw) if need[2] and ctx.mode == _lib.SMX_EMA_ALIGNED else None
         gi = torch.empty_like(g) if init is not None and need[3] else None
         ws = _ema_ws(g.device, B, S, F)
         _call(g.device, "smx_ema_scan_backward", g.data_ptr(), chunks.data_ptr(), _ptr(init), rho_logit.data_ptr(),
@@ -1780,7 +1780,7 @@ class _EmaScanTokens(torch.autograd.Function):
         L = ctx.L
         g = _grad_c64(g)
         gr = torch.empty_like(rho_logit) if ctx.needs_input_grad[2] else None
-        gt = torch.empty_like(theta_raw) if ctx.needs_input_grad[3] and ctx.mode == 0 else None
+        gt = torch.empty_like(theta_raw) if ctx.needs_input_grad[3] and ctx.mode == _lib.SMX_EMA_ALIGNED else None
         ws = _ema_ws(g.device, B, T // L, L // 2 + 1)
         _call(g.device, "smx_ema_tokens_backward", g.data_ptr(), *ctx.args, None, rho_logit.data_ptr(),
               theta_raw.data_ptr(), None, _ptr(gr), _ptr(gt), *_ws_arg(ws), ctx.mode, B, T, L, _stream(g.device))
@@ -1959,7 +1959,7 @@ def narrow_head(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
 
 # ---- softmax cross-entropy: the losses of the dual head (csrc/smx_block.hip, k_xent_*) ------------------------------------
 
-_XENT_REDUCTION = {"mean": 0, "sum": 1, "none": 2}
+_XENT_REDUCTION = {"mean": _lib.SMX_XENT_MEAN, "sum": _lib.SMX_XENT_SUM, "none": _lib.SMX_XENT_NONE}
 
 
 @functools.lru_cache(None)
@@ -1986,14 +1986,14 @@ class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, row_stride, targets, ignore_index, reduction):
         R, V = x.shape
-        n_loss = R if reduction == 2 else 1
+        n_loss = R if reduction == _lib.SMX_XENT_NONE else 1
         buf = torch.empty(2 * R + 1 + n_loss, dtype=torch.float32, device=x.device)  # lse (R, 2) | count | loss
         ws = _workspace(x.device, _xent_ws_bytes(R, V))
         _call(x.device, "smx_xent_forward", x.data_ptr(), row_stride, targets.data_ptr(), ignore_index, reduction,
               buf.data_ptr() + 4 * (2 * R + 1), buf.data_ptr(), buf.data_ptr() + 8 * R, *_ws_arg(ws), R, V, _stream(x.device))
         ctx.meta = (row_stride, ignore_index, reduction)
         ctx.save_for_backward(x, targets, buf)
-        return buf[2 * R + 1:] if reduction == 2 else buf[2 * R + 1]
+        return buf[2 * R + 1:] if reduction == _lib.SMX_XENT_NONE else buf[2 * R + 1]
 
     @staticmethod
     @once_differentiable
