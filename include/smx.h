@@ -850,4 +850,9 @@ int smx_sparse_scatter(const void* coeffs, const long long* flat_idx, long long 
 #ifdef __cplusplus
 }
 #endif
+
+/* Entry points added after the table of this header's signatures was recorded live in headers of their own, included
+ * here: a C caller sees one ABI, and the Python binding reads each header it names (_lib.EXT_HEADERS). */
+#include "smx_freq.h"
+
 #endif /* SMX_H_ */

@@ -1,6 +1,6 @@
-"""ctypes binding of libsmx.so, derived from include/smx.h when this module is imported: the entry points' signatures,
-the fields of the three structs and the SMX_* constants are read from the header's text, so an entry point is declared
-there and nowhere else on the Python side.  No CPU fallback: if the library is missing the import of the product path
+"""ctypes binding of libsmx.so, derived from include/smx.h (and the headers it includes, EXT_HEADERS) when this module is
+imported: the entry points' signatures, the fields of the three structs and the SMX_* constants are read from the
+header's text, so an entry point is declared there and nowhere else on the Python side.  No CPU fallback: if the library is missing the import of the product path
 fails with a build hint."""
 from __future__ import annotations
 
@@ -13,6 +13,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SMX_LIB selects an experimental build of the same ABI (tuning only)
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "csrc", "libsmx.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "smx.h")      # the layout csrc/build.sh relies on too
+# headers that smx.h includes (the reader does not follow #include): entry points added since the table of smx.h's own
+# signatures was recorded (tests/golden/abi_signatures.txt); theirs is tests/golden/abi_signatures_ext.txt
+EXT_HEADERS = ("smx_freq.h",)
 
 
 class SmxError(RuntimeError):
@@ -88,10 +91,29 @@ def _read_header_file():
         return read_header(f.read())
 
 
+def _read_ext_headers():
+    """(prototypes, integer defines) of the EXT_HEADERS beside smx.h: entry points and constants only, no structs, and no
+    name that smx.h already declares"""
+    sigs, defines = {}, {}
+    for name in EXT_HEADERS:
+        path = os.path.join(os.path.dirname(HEADER_PATH), name)
+        if not os.path.exists(path):
+            raise SmxError(f"{path} not found: smx.h includes it, and the ctypes binding of its entry points is read from it.")
+        with open(path) as f:
+            s, d, st = read_header(f.read())
+        if st or set(s) & (set(sigs) | set(_SIGS)):
+            raise SmxError(f"{name}: an extension header declares entry points of its own and no structs")
+        sigs.update(s)
+        defines.update(d)
+    return sigs, defines
+
+
 _SIGS, _DEFINES, _FIELDS = _read_header_file()
+_SIGS_EXT, _DEFINES_EXT = _read_ext_headers()
 for _s in (smx_plan, smx_options, smx_shape):
     _s._fields_ = [(n, ctypes.c_int) for n in _FIELDS[_s.__name__]]
 globals().update(_DEFINES)                  # SMX_PATH_*, SMX_IO_*, SMX_PHASE_*, SMX_ERR_* ...: every integer #define
+globals().update(_DEFINES_EXT)
 
 
 _SINCE = {"smx_diag_clock": 302, "smx_dwconv3_workspace_bytes": 302, "smx_dwconv3_forward": 302,
@@ -111,7 +133,7 @@ def load(path: str):
     """dlopen one build of the library and declare its signatures (tools/ab_inproc.py loads several)."""
     import torch  # noqa: F401  (maps torch's libamdhip64 before ours resolves it)
     h = ctypes.CDLL(path)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in {**_SIGS, **_SIGS_EXT}.items():
         if name in _SINCE and h.smx_version() < _SINCE[name]:
             continue                       # an older build loaded beside the current one (A/B tools only)
         fn = getattr(h, name)

@@ -2415,4 +2415,63 @@ int smx_sparse_scatter(const void* coeffs, const long long* flat_idx, long long 
   return SMX_OK;
 }
 
+// ---- frequency attention and frequency layernorm (smx_freq.hip) -----------------------------------------------------------
+static_assert(FREQ_LN_MAX_D == SMX_FREQ_LN_MAX_D, "smx_freq.h states the limit of smx_kernels.h");
+// 0: run it, 1: zero-sized (success, nothing to enqueue), negative: refused
+static int fattn_check(int B, int H, int N) {
+  if (B < 0 || H < 0 || N < 0) return fail(SMX_ERR_INVALID, "sizes must not be negative: B=%d H=%d N=%d", B, H, N);
+  if (B == 0 || H == 0 || N == 0) return 1;
+  if ((long long)B * H * N >= (1ll << 31) || N > FATTN_MAX_N)
+    return fail(SMX_ERR_UNSUPPORTED, "B*H*N must stay below 2^31 and N at or below 2^30: B=%d H=%d N=%d", B, H, N);
+  return 0;
+}
+static size_t fattn_need(int B, int H, int N) { return WS_HEADER_BYTES + al((size_t)B * H * N * sizeof(float)); }
+int smx_freq_attention_workspace_bytes(int B, int H, int N, size_t* out) {
+  if (!out) return fail(SMX_ERR_INVALID, "out is NULL");
+  const int rc = fattn_check(B, H, N);
+  if (rc < 0) return rc;
+  *out = rc ? 0 : fattn_need(B, H, N);
+  return SMX_OK;
+}
+int smx_freq_attention_forward(const void* q, long long q_sb, long long q_sh, long long q_sn,
+                               const void* k, long long k_sb, long long k_sh, long long k_sn,
+                               const void* v, long long v_sb, long long v_sh, long long v_sn,
+                               void* out, long long o_sb, long long o_sh, long long o_sn, float temperature,
+                               void* workspace, size_t workspace_bytes, int B, int H, int N, int D, void* stream) {
+  const int rc = fattn_check(B, H, N);
+  if (rc < 0) return rc;
+  if (D < 0) return fail(SMX_ERR_INVALID, "D must not be negative, got %d", D);
+  FattnArgs a{};
+  const long long st[12] = {q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, o_sb, o_sh, o_sn};
+  for (int i = 0; i < 12; ++i) {
+    if (st[i] < 0) return fail(SMX_ERR_INVALID, "strides must not be negative");
+    (i < 3 ? a.sq : i < 6 ? a.sk : i < 9 ? a.sv : a.so)[i % 3] = st[i];
+  }
+  if (!std::isfinite(temperature) || temperature == 0.f)
+    return fail(SMX_ERR_INVALID, "temperature must be finite and not 0, got %g", (double)temperature);
+  if (rc || D == 0) return SMX_OK;
+  if (!q || !k || !v || !out) return fail(SMX_ERR_INVALID, "q, k, v and out must be non-NULL");
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 7)
+    return fail(SMX_ERR_INVALID, "q, k, v and out must be 8-byte aligned");
+  if (need_ws(workspace, workspace_bytes, fattn_need(B, H, N), "smx_freq_attention_workspace_bytes")) return SMX_ERR_INVALID;
+  if (!&launch_fattn) return fail(SMX_ERR_UNSUPPORTED, "this build holds no smx_freq unit");
+  a.q = (const float2*)q; a.k = (const float2*)k; a.v = (const float2*)v; a.out = (float2*)out;
+  a.rows = (long long)B * H * N; a.H = H; a.N = N; a.D = D;
+  a.scale = (float)(1.0 / ((double)temperature * (double)D));
+  HIP_TRY(launch_fattn(a, (float*)((char*)workspace + WS_HEADER_BYTES), (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_freq_layernorm_forward(const void* z, void* out, float eps, long long rows, int D, void* stream) {
+  if (rows < 0 || D < 0) return fail(SMX_ERR_INVALID, "sizes must not be negative: rows=%lld D=%d", rows, D);
+  if (rows == 0 || D == 0) return SMX_OK;
+  if (!z || !out) return fail(SMX_ERR_INVALID, "z and out must be non-NULL");
+  if (((uintptr_t)z | (uintptr_t)out) & 15) return fail(SMX_ERR_INVALID, "z and out must be 16-byte aligned");
+  if (!freq_ln_supported(D))
+    return fail(SMX_ERR_UNSUPPORTED, "D=%d is wider than SMX_FREQ_LN_MAX_D=%d", D, SMX_FREQ_LN_MAX_D);
+  if (rows >= (1ll << 40)) return fail(SMX_ERR_UNSUPPORTED, "rows must stay below 2^40");
+  if (!&launch_freq_ln) return fail(SMX_ERR_UNSUPPORTED, "this build holds no smx_freq unit");
+  HIP_TRY(launch_freq_ln((const float*)z, (float*)out, eps, rows, D, (hipStream_t)stream));
+  return SMX_OK;
+}
+
 }  // extern "C"

@@ -463,4 +463,28 @@ hipError_t launch_topk_compact(const float2* z, long long n, const long long* re
 hipError_t launch_sparse_scatter(const float2* coeffs, const long long* flat_idx, long long m, float2* out, long long n,
                                  int max_workgroups, hipStream_t s);
 
+// ---- frequency attention and frequency layernorm (smx_freq.hip) ---------------------------------------------------------
+struct FattnArgs {
+  const float2* q;
+  const float2* k;
+  const float2* v;
+  float2* out;
+  long long sq[3], sk[3], sv[3], so[3];   // element strides of the b, h and n axes; the innermost axis is contiguous
+  long long rows;                         // B H N
+  int H, N, D;
+  float scale;                            // 1 / (temperature D)
+};
+constexpr int FATTN_MAX_N = 1 << 30;
+constexpr int FATTN_MAX_WG = 2048;        // workgroups of k_fattn_apply above which its tiles grow past 64 rows
+int fattn_tile_rows(long long BH, int N);
+constexpr int FREQ_LN_MAX_D = 1024;       // widest complex row held in registers (SMX_FREQ_LN_MAX_D of smx_freq.h)
+inline bool freq_ln_supported(int D) { return D >= 1 && D <= FREQ_LN_MAX_D; }
+// The two launchers are WEAK references: a link that lists its units itself and leaves smx_freq out (the host-only
+// program of tests/api_trace) still resolves smx_api's entries, which refuse with SMX_ERR_UNSUPPORTED where a launcher is
+// absent.  libsmx.so always holds them (csrc/build.sh).
+// scores: B H N floats of scratch.  Two launches (scores; statistics + apply).
+__attribute__((weak)) hipError_t launch_fattn(const FattnArgs& a, float* scores, hipStream_t s);
+// z, out: (rows, D) complex64 dense, 16-byte aligned
+__attribute__((weak)) hipError_t launch_freq_ln(const float* z, float* out, float eps, long long rows, int D, hipStream_t s);
+
 }  // namespace smx

@@ -2449,3 +2449,106 @@ def ifftn(z: torch.Tensor) -> torch.Tensor:
         return torch.fft.ifftn(z)
     out = _axis_walk(z.conj().resolve_conj(), seq_fft_raw)
     return torch.conj_physical(out).div_(z.numel())
+
+
+# ---- the frequency-domain transformer ops: attention and layernorm (csrc/smx_freq.hip) --------------------------------------
+
+_fattn_ws_cache = _Memo()
+FREQ_LN_MAX_D = _lib.SMX_FREQ_LN_MAX_D
+
+
+def _freq_native(*ts) -> bool:
+    """complex64 tensors on one ROCm device that autograd does not follow: what the forward-only kernels take"""
+    t0 = ts[0]
+    if not all(isinstance(t, torch.Tensor) and t.dtype == torch.complex64 and t.is_cuda and t.device == t0.device
+               for t in ts):
+        return False
+    return not (torch.is_grad_enabled() and any(t.requires_grad for t in ts))
+
+
+def _f32_finite_nonzero(v) -> bool:
+    """a Python number that is finite and not 0 once it is the C entry's float argument (1e-50 is 0 there, 1e39 inf)"""
+    try:
+        f = ctypes.c_float(v).value
+    except (OverflowError, TypeError):
+        return False
+    return math.isfinite(f) and f != 0.0
+
+
+def _frequency_attention_torch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, temperature) -> torch.Tensor:
+    """the reference's op sequence (fft_tensor/frequency_ops.py:166-185) as whole-tensor torch ops"""
+    scores = (torch.abs(q * torch.conj(k)) / temperature).mean(dim=-1)
+    return torch.softmax(scores, dim=-1).unsqueeze(-1) * v
+
+
+def _complex_rows(t: torch.Tensor) -> torch.Tensor:
+    """`t` with a contiguous innermost axis (any strides on the others): itself where it has one, a dense copy otherwise"""
+    t = t.resolve_conj()
+    return t if t.shape[-1] <= 1 or t.stride(-1) == 1 else t.contiguous()
+
+
+def frequency_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, temperature: float = 1.0, *,
+                        merge_heads: bool = False) -> torch.Tensor:
+    """The reference's FrequencyAttention.frequency_attention for complex q, k, v of shape (B, H, N, D):
+        s[b, h, n] = mean_d(|q conj(k)| / temperature),  p = softmax_n(s),  out = p[..., None] v      (B, H, N, D).
+    merge_heads=True returns the same values as `out.transpose(1, 2).contiguous().view(B, N, H * D)`, what a multi-head
+    layer does next.
+    Native (smx_freq_attention_forward: one launch that reads q and k once and writes a score per row, one that takes the
+    softmax statistics and scales v; 32 bytes of traffic per element, bitwise reproducible) for complex64 tensors of one
+    shape on a ROCm device with a float temperature that is finite and not 0 in fp32, B H N < 2**31 and N <= 2**30, when no
+    operand requires grad or grad mode is off.
+    The operands are read through their strides -- head-transposed views of (B, N, H, D) tensors cost no copy; only an
+    operand whose innermost stride is not 1 is copied -- and with merge_heads the result is written in (B, N, H D)
+    layout directly.  Everything else (CPU tensors, other dtypes, broadcasting shapes, operands that require grad) runs
+    the definition as the reference's whole-tensor torch ops, so it differentiates and fails exactly as the reference
+    does.  There is no native backward."""
+    native = (isinstance(temperature, (int, float)) and _f32_finite_nonzero(temperature)
+              and isinstance(q, torch.Tensor) and q.dim() == 4 and _freq_native(q, k, v)
+              and q.shape == k.shape == v.shape
+              and q.shape[0] * q.shape[1] * q.shape[2] < 2 ** 31 and q.shape[2] <= 2 ** 30)      # the entry's limits
+    if not native:
+        out = _frequency_attention_torch(q, k, v, temperature)
+        if merge_heads:
+            B, H, N, D = out.shape
+            out = out.transpose(1, 2).contiguous().view(B, N, H * D)
+        return out
+    B, H, N, D = q.shape
+    dev = q.device
+    store = torch.empty((B, N, H, D) if merge_heads else (B, H, N, D), dtype=torch.complex64, device=dev)
+    out = store.permute(0, 2, 1, 3) if merge_heads else store
+    if store.numel():
+        q, k, v = _complex_rows(q), _complex_rows(k), _complex_rows(v)
+        ws = _workspace(dev, _fattn_ws_cache.get((B, H, N), lambda: _query("smx_freq_attention_workspace_bytes", B, H, N)))
+        _call(dev, "smx_freq_attention_forward", q.data_ptr(), *q.stride()[:3], k.data_ptr(), *k.stride()[:3],
+              v.data_ptr(), *v.stride()[:3], out.data_ptr(), *out.stride()[:3], float(temperature), *_ws_arg(ws),
+              B, H, N, D, _stream(dev))
+    return store.view(B, N, H * D) if merge_heads else store
+
+
+def _frequency_layernorm_torch(z: torch.Tensor, eps: float) -> torch.Tensor:
+    """the reference's op sequence (fft_tensor/frequency_ops.py:390-401)"""
+    magnitude = torch.abs(z)
+    mean_mag = magnitude.mean(dim=-1, keepdim=True)
+    std_mag = magnitude.std(dim=-1, keepdim=True)
+    return (magnitude - mean_mag) / (std_mag + eps) * torch.exp(1j * torch.angle(z))
+
+
+def frequency_layernorm(z: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    """The reference's frequency_layernorm over the last axis of a complex tensor: with m = |z|,
+        out = (m - mean(m)) / (std(m) + eps) * exp(i angle(z)),
+    std unbiased as torch.std's default (a last axis of 1 gives NaN, as in the reference) and exp(i angle(0)) = 1.
+    Native (smx_freq_layernorm_forward: one launch, one wavefront per row with the row in registers, 16 bytes of traffic
+    per element, bitwise reproducible; the unit phase is z / |z|, no trigonometry) for a complex64 tensor on a ROCm device
+    whose last axis is at most FREQ_LN_MAX_D = 1024 wide, when it does not require grad or grad mode is off.  Wider rows,
+    CPU tensors, other dtypes and inputs that require grad run the reference's whole-tensor torch ops, so they
+    differentiate exactly as the reference does.  There is no native backward."""
+    native = (isinstance(z, torch.Tensor) and z.dim() >= 1 and _freq_native(z) and z.numel() > 0
+              and z.shape[-1] <= FREQ_LN_MAX_D and isinstance(eps, (int, float)))
+    if not native:
+        return _frequency_layernorm_torch(z, eps)
+    zd = _dense(z)
+    out = torch.empty_like(zd)
+    D = z.shape[-1]
+    _call(z.device, "smx_freq_layernorm_forward", zd.data_ptr(), out.data_ptr(), float(eps), zd.numel() // D, D,
+          _stream(z.device))
+    return out
