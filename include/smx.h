@@ -852,7 +852,9 @@ int smx_sparse_scatter(const void* coeffs, const long long* flat_idx, long long 
 #endif
 
 /* Entry points added after the table of this header's signatures was recorded live in headers of their own, included
- * here: a C caller sees one ABI, and the Python binding reads each header it names (_lib.EXT_HEADERS). */
+ * here: a C caller sees one ABI, and the Python binding reads each header it names (_lib.EXT_HEADERS, and
+ * _lib.MORE_HEADERS for the ones after smx_freq.h, whose table is recorded as it stood too). */
 #include "smx_freq.h"
+#include "smx_fconv.h"
 
 #endif /* SMX_H_ */

@@ -10,13 +10,15 @@ from .wirtinger_ops import (ComplexParameter, WirtingerGradient, WirtingerSpectr
 from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft, rfft_bins, seq_fft,
                          spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens, narrow_head,
                          word_targets, cross_entropy, sample_bytes, byte_features, find_snippets, sparsify_topk,
-                         sparse_scatter, fftn, ifftn, frequency_attention)
+                         sparse_scatter, fftn, ifftn, frequency_attention, bin_contract)
 from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
 from .frequency_ops import (ComplexSemanticEmbedding, FrequencyAttention, FrequencyMatMul, FrequencyTransformerLayer,
                             frequency_layernorm, frequency_relu)
 from .sparse_tensor import MemoryManager, SparseSpectralTensor, randn_sst, sst, zeros_sst
+from .optimized_ops import OptimizedFrequencyOps, ProductionFrequencyLinear
+from .production_ready import OptimizedSparseSpectralTensor, ProductionFrequencyOps
 from .ops import spectral_activation, spectral_normalize, spectral_pool
 from .fixed_spectral import (FixedSpectralBlock, FixedSpectralLM, FrequencyConvFunc, LMConfig, SampleConfig,
                              causal_spectral_conv, generate)
@@ -57,5 +59,7 @@ __all__ = [
     "load_state_flexible", "SparseSpectralTensor", "MemoryManager", "sst", "zeros_sst", "randn_sst", "sparsify_topk",
     "sparse_scatter", "fftn", "ifftn", "spectral_normalize", "spectral_activation", "spectral_pool", "FrequencyMatMul",
     "FrequencyTransformerLayer", "ComplexSemanticEmbedding", "frequency_relu", "frequency_layernorm", "frequency_attention",
+    "bin_contract", "OptimizedFrequencyOps", "ProductionFrequencyLinear", "ProductionFrequencyOps",
+    "OptimizedSparseSpectralTensor",
 ]
 __version__ = "0.2.0"

@@ -1,4 +1,4 @@
-"""ctypes binding of libsmx.so, derived from include/smx.h (and the headers it includes, EXT_HEADERS) when this module is
+"""ctypes binding of libsmx.so, derived from include/smx.h (and the headers it includes, EXT_HEADERS and MORE_HEADERS) when this module is
 imported: the entry points' signatures, the fields of the three structs and the SMX_* constants are read from the
 header's text, so an entry point is declared there and nowhere else on the Python side.  No CPU fallback: if the library is missing the import of the product path
 fails with a build hint."""
@@ -16,6 +16,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "smx.h")      # th
 # headers that smx.h includes (the reader does not follow #include): entry points added since the table of smx.h's own
 # signatures was recorded (tests/golden/abi_signatures.txt); theirs is tests/golden/abi_signatures_ext.txt
 EXT_HEADERS = ("smx_freq.h",)
+# headers added after THAT table was recorded: one table per header ({header: prototypes}, _SIGS_MORE), each recorded in a
+# file of its own (smx_fconv.h: tests/golden/abi_signatures_fconv.txt)
+MORE_HEADERS = ("smx_fconv.h",)
 
 
 class SmxError(RuntimeError):
@@ -91,11 +94,11 @@ def _read_header_file():
         return read_header(f.read())
 
 
-def _read_ext_headers():
-    """(prototypes, integer defines) of the EXT_HEADERS beside smx.h: entry points and constants only, no structs, and no
-    name that smx.h already declares"""
+def _read_ext_headers(names=None):
+    """(prototypes, integer defines) of the EXT_HEADERS (or `names`) beside smx.h: entry points and constants only, no
+    structs, and no name that smx.h already declares"""
     sigs, defines = {}, {}
-    for name in EXT_HEADERS:
+    for name in EXT_HEADERS if names is None else names:
         path = os.path.join(os.path.dirname(HEADER_PATH), name)
         if not os.path.exists(path):
             raise SmxError(f"{path} not found: smx.h includes it, and the ctypes binding of its entry points is read from it.")
@@ -110,10 +113,17 @@ def _read_ext_headers():
 
 _SIGS, _DEFINES, _FIELDS = _read_header_file()
 _SIGS_EXT, _DEFINES_EXT = _read_ext_headers()
+_SIGS_MORE, _DEFINES_MORE = {}, {}
+for _h in MORE_HEADERS:
+    _SIGS_MORE[_h], _DEFINES_MORE[_h] = _read_ext_headers((_h,))
+    if set(_SIGS_MORE[_h]) & set(_SIGS_EXT):
+        raise SmxError(f"{_h}: an extension header declares entry points of its own")
 for _s in (smx_plan, smx_options, smx_shape):
     _s._fields_ = [(n, ctypes.c_int) for n in _FIELDS[_s.__name__]]
 globals().update(_DEFINES)                  # SMX_PATH_*, SMX_IO_*, SMX_PHASE_*, SMX_ERR_* ...: every integer #define
 globals().update(_DEFINES_EXT)
+for _d in _DEFINES_MORE.values():
+    globals().update(_d)
 
 
 _SINCE = {"smx_diag_clock": 302, "smx_dwconv3_workspace_bytes": 302, "smx_dwconv3_forward": 302,
@@ -133,7 +143,7 @@ def load(path: str):
     """dlopen one build of the library and declare its signatures (tools/ab_inproc.py loads several)."""
     import torch  # noqa: F401  (maps torch's libamdhip64 before ours resolves it)
     h = ctypes.CDLL(path)
-    for name, (res, args) in {**_SIGS, **_SIGS_EXT}.items():
+    for name, (res, args) in {**_SIGS, **_SIGS_EXT, **{n: v for t in _SIGS_MORE.values() for n, v in t.items()}}.items():
         if name in _SINCE and h.smx_version() < _SINCE[name]:
             continue                       # an older build loaded beside the current one (A/B tools only)
         fn = getattr(h, name)

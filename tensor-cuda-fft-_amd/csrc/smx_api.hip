@@ -2474,4 +2474,44 @@ int smx_freq_layernorm_forward(const void* z, void* out, float eps, long long ro
   return SMX_OK;
 }
 
+// ---- per-bin channel contraction of the FFT convolutions (smx_fconv.hip) ------------------------------------------------------
+// 0: run it, 1: zero-sized (success, nothing to enqueue), negative: refused
+static int bin_check(int B, long long P, int Ci, int Co, int max_workgroups) {
+  if (B < 0 || P < 0 || Ci < 0 || Co < 0)
+    return fail(SMX_ERR_INVALID, "sizes must not be negative: B=%d P=%lld Ci=%d Co=%d", B, P, Ci, Co);
+  if (int rc = wg_check(max_workgroups)) return rc;
+  if (B == 0 || P == 0 || Ci == 0 || Co == 0) return 1;
+  if (!&bin_contract_supported || !&launch_bin_contract_fwd || !&launch_bin_contract_bwd)
+    return fail(SMX_ERR_UNSUPPORTED, "this build holds no smx_fconv unit");
+  if (!bin_contract_supported(B, P, Ci, Co))
+    return fail(SMX_ERR_UNSUPPORTED, "unsupported size (smx_bin_contract_supported): B=%d P=%lld Ci=%d Co=%d", B, P, Ci, Co);
+  return 0;
+}
+int smx_bin_contract_supported(int B, long long P, int Ci, int Co) {
+  return &bin_contract_supported && bin_contract_supported(B, P, Ci, Co) ? 1 : 0;
+}
+int smx_bin_contract_forward(const void* x, const void* w, void* y, int B, long long P, int Ci, int Co, int max_workgroups,
+                             void* stream) {
+  const int rc = bin_check(B, P, Ci, Co, max_workgroups);
+  if (rc) return rc < 0 ? rc : SMX_OK;
+  if (!x || !w || !y) return fail(SMX_ERR_INVALID, "x, w and y must be non-NULL");
+  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 7) return fail(SMX_ERR_INVALID, "x, w and y must be 8-byte aligned");
+  HIP_TRY(launch_bin_contract_fwd((const float2*)x, (const float2*)w, (float2*)y, B, P, Ci, Co, max_workgroups,
+                                  (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_bin_contract_backward(const void* x, const void* w, const void* gy, void* gx, void* gw, int B, long long P, int Ci,
+                              int Co, int max_workgroups, void* stream) {
+  const int rc = bin_check(B, P, Ci, Co, max_workgroups);
+  if (rc) return rc < 0 ? rc : SMX_OK;
+  if (!gx && !gw) return SMX_OK;
+  if (!gy || (gx && !w) || (gw && !x))
+    return fail(SMX_ERR_INVALID, "gy, w (for gx) and x (for gw) must be non-NULL");
+  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)gy | (uintptr_t)gx | (uintptr_t)gw) & 7)
+    return fail(SMX_ERR_INVALID, "x, w, gy, gx and gw must be 8-byte aligned");
+  HIP_TRY(launch_bin_contract_bwd((const float2*)x, (const float2*)w, (const float2*)gy, (float2*)gx, (float2*)gw, B, P, Ci,
+                                  Co, max_workgroups, (hipStream_t)stream));
+  return SMX_OK;
+}
+
 }  // extern "C"

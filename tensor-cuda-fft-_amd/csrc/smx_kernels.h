@@ -487,4 +487,16 @@ __attribute__((weak)) hipError_t launch_fattn(const FattnArgs& a, float* scores,
 // z, out: (rows, D) complex64 dense, 16-byte aligned
 __attribute__((weak)) hipError_t launch_freq_ln(const float* z, float* out, float eps, long long rows, int D, hipStream_t s);
 
+// ---- per-bin channel contraction of the FFT convolutions (smx_fconv.hip) ----------------------------------------------------
+// x (B, P, Ci), w (P, Ci, Co), y / gy (B, P, Co), all complex64, dense, 8-byte aligned.  WEAK references like the two
+// above, for the same reason; smx_api's entries answer through the launchers alone, so the size rule is weak too.
+__attribute__((weak)) bool bin_contract_supported(int B, long long P, int Ci, int Co);
+// y[b, p, o] = sum_i x[b, p, i] w[p, i, o].  One launch.
+__attribute__((weak)) hipError_t launch_bin_contract_fwd(const float2* x, const float2* w, float2* y, int B, long long P, int Ci,
+                                                         int Co, int max_workgroups, hipStream_t s);
+// gx[b, p, i] = sum_o gy conj(w) (needs w), gw[p, i, o] = sum_b conj(x) gy (needs x); either may be NULL: a launch each.
+__attribute__((weak)) hipError_t launch_bin_contract_bwd(const float2* x, const float2* w, const float2* gy, float2* gx,
+                                                         float2* gw, int B, long long P, int Ci, int Co, int max_workgroups,
+                                                         hipStream_t s);
+
 }  // namespace smx

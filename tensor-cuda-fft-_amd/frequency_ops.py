@@ -14,6 +14,16 @@ from .functional import seq_fft
 from .sparse_tensor import SparseSpectralTensor
 
 
+def ifft_last_real(w_freq: torch.Tensor) -> torch.Tensor:
+    """torch.fft.ifft(w_freq, dim=-1).real of a 2-D weight.  On a ROCm device the inverse transform of a complex64 weight
+    that does not require grad is the package's own sequence transform, ifft(w) = conj(fft(conj w)) / n as
+    functional.ifftn does it; CPU tensors (and every other weight) use torch.fft."""
+    if w_freq.is_cuda and w_freq.dtype == torch.complex64 and not w_freq.requires_grad and w_freq.numel() > 0:
+        spec = _fn.seq_fft_raw(w_freq.conj().resolve_conj().unsqueeze(-1)).squeeze(-1)
+        return spec.real / w_freq.shape[-1]              # Re(conj(s) / n) = Re(s) / n
+    return torch.fft.ifft(w_freq, dim=-1).real
+
+
 class FrequencyMatMul:
     @staticmethod
     def circulant_matmul(x: torch.Tensor, w_freq: torch.Tensor) -> torch.Tensor:
@@ -28,11 +38,7 @@ class FrequencyMatMul:
             D_out, D_in = w_freq.shape
             if D_in != K and D_out != K:
                 raise ValueError(f"Dimension mismatch: x has {K}, w_freq is {w_freq.shape}")
-            if w_freq.is_cuda and w_freq.dtype == torch.complex64 and not w_freq.requires_grad and w_freq.numel() > 0:
-                spec = _fn.seq_fft_raw(w_freq.conj().resolve_conj().unsqueeze(-1)).squeeze(-1)
-                w_spatial = spec.real / D_in                 # Re(conj(s) / n) = Re(s) / n
-            else:
-                w_spatial = torch.fft.ifft(w_freq, dim=-1).real
+            w_spatial = ifft_last_real(w_freq)
             return torch.matmul(x, w_spatial.T if D_in == K else w_spatial)
         raise ValueError(f"Unexpected w_freq shape: {w_freq.shape}")
 

@@ -2552,3 +2552,72 @@ def frequency_layernorm(z: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     _call(z.device, "smx_freq_layernorm_forward", zd.data_ptr(), out.data_ptr(), float(eps), zd.numel() // D, D,
           _stream(z.device))
     return out
+
+
+# ---- the per-bin channel contraction of the FFT convolutions (csrc/smx_fconv.hip) --------------------------------------------
+
+@functools.lru_cache(4096)
+def bin_contract_supported(B: int, P: int, Ci: int, Co: int) -> bool:
+    """smx_bin_contract_supported: every size at least 1, P < 2**31, every operand below 2**40 elements.  (A property of the
+    library.)"""
+    if not all(0 < v < 2 ** 31 for v in (B, Ci, Co)) or not 0 < P < 2 ** 62:
+        return False
+    return bool(_lib.lib().smx_bin_contract_supported(int(B), int(P), int(Ci), int(Co)))
+
+
+class _BinContract(torch.autograd.Function):
+    """y[b, p, o] = sum_i x[b, p, i] w[p, i, o] (smx_bin_contract_forward) with its native backward
+    (smx_bin_contract_backward; torch's convention, grad = dL/dRe + i dL/dIm):
+        gx[b, p, i] = sum_o gy[b, p, o] conj(w[p, i, o]),   gw[p, i, o] = sum_b conj(x[b, p, i]) gy[b, p, o].
+    Only the gradients autograd asks for are computed (a launch each)."""
+
+    @staticmethod
+    def forward(ctx, x, w, max_workgroups):
+        ctx.smx_opts = _lib.effective_options()
+        B, P, Ci = x.shape
+        Co = w.shape[2]
+        y = torch.empty((B, P, Co), dtype=torch.complex64, device=x.device)
+        _call(x.device, "smx_bin_contract_forward", x.data_ptr(), w.data_ptr(), y.data_ptr(), B, P, Ci, Co, max_workgroups,
+              _stream(x.device))
+        ctx.save_for_backward(x, w)
+        ctx.mwg = max_workgroups
+        return y
+
+    @staticmethod
+    @once_differentiable
+    @_under_forward_options
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        B, P, Ci = x.shape
+        Co = w.shape[2]
+        gy = _grad_c64(gy)
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
+        if gx is not None or gw is not None:
+            _call(x.device, "smx_bin_contract_backward", x.data_ptr(), w.data_ptr(), gy.data_ptr(), _ptr(gx), _ptr(gw), B, P,
+                  Ci, Co, ctx.mwg, _stream(x.device))
+        return gx, gw, None
+
+
+def bin_contract(x: torch.Tensor, w: torch.Tensor, *, max_workgroups: int = 0) -> torch.Tensor:
+    """torch.einsum("bpi,pio->bpo", x, w): one small complex matrix product per bin p, channels innermost on every operand
+    -- x (B, P, Ci), w (P, Ci, Co), the result (B, P, Co) -- which is the layout rfft / seq_fft produce, so nothing is
+    transposed between the transforms and the contraction.  It is what the reference's FFT convolutions compute as
+    `(x_freq.unsqueeze(1) * w_freq.unsqueeze(0)).sum(dim=2)` (fft_tensor/optimized_ops.py:183-187, :247-251) over a
+    materialised (B, Co, Ci, bins) product.
+    Native (smx_bin_contract_forward / _backward: fp32 FMAs, every sum in ascending index order, bitwise reproducible,
+    capturable) for complex64 operands on one ROCm device with sizes inside smx_bin_contract_supported, whether or not
+    they require grad: this op has a native backward (gx and gw, a launch each, only those asked for).  Everything else
+    (CPU tensors, other dtypes, empty operands, sizes beyond the limits) runs the einsum.  max_workgroups (> 0) caps the
+    native tile walks: a test and tuning knob."""
+    if not (isinstance(x, torch.Tensor) and isinstance(w, torch.Tensor) and x.dim() == 3 and w.dim() == 3):
+        raise TypeError("bin_contract: x must be a (B, P, Ci) tensor and w a (P, Ci, Co) tensor")
+    if x.shape[1:] != w.shape[:2]:
+        raise ValueError(f"bin_contract: x is {tuple(x.shape)}, w is {tuple(w.shape)}: need (B, P, Ci) and (P, Ci, Co)")
+    if max_workgroups < 0:
+        raise ValueError(f"bin_contract: max_workgroups must not be negative, got {max_workgroups}")
+    native = (x.dtype == torch.complex64 and w.dtype == torch.complex64 and x.is_cuda and w.device == x.device
+              and bin_contract_supported(x.shape[0], x.shape[1], x.shape[2], w.shape[2]))
+    if not native:
+        return torch.einsum("bpi,pio->bpo", x, w)
+    return _BinContract.apply(_dense(x), _dense(w), int(max_workgroups))
