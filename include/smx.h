@@ -856,5 +856,6 @@ int smx_sparse_scatter(const void* coeffs, const long long* flat_idx, long long 
  * _lib.MORE_HEADERS for the ones after smx_freq.h, whose table is recorded as it stood too). */
 #include "smx_freq.h"
 #include "smx_fconv.h"
+#include "smx_quant.h"
 
 #endif /* SMX_H_ */

@@ -10,7 +10,8 @@ from .wirtinger_ops import (ComplexParameter, WirtingerGradient, WirtingerSpectr
 from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft, rfft_bins, seq_fft,
                          spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens, narrow_head,
                          word_targets, cross_entropy, sample_bytes, byte_features, find_snippets, sparsify_topk,
-                         sparse_scatter, fftn, ifftn, frequency_attention, bin_contract)
+                         sparse_scatter, fftn, ifftn, frequency_attention, bin_contract, polar_range, polar_quantize,
+                         polar_dequantize, log8_encode, log8_decode, log8_encode_complex, log8_decode_complex)
 from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
@@ -19,6 +20,10 @@ from .frequency_ops import (ComplexSemanticEmbedding, FrequencyAttention, Freque
 from .sparse_tensor import MemoryManager, SparseSpectralTensor, randn_sst, sst, zeros_sst
 from .optimized_ops import OptimizedFrequencyOps, ProductionFrequencyLinear
 from .production_ready import OptimizedSparseSpectralTensor, ProductionFrequencyOps
+from .polar_quantization import PolarQuantizer
+from .zero_materialize import (ConvolutionTheoremMatMul, FrequencyLinearLayer, LogarithmicQuantizer, WirtingerAutograd,
+                               frequency_conv1d, frequency_linear)
+from .llamaizer import FFTConverter
 from .ops import spectral_activation, spectral_normalize, spectral_pool
 from .fixed_spectral import (FixedSpectralBlock, FixedSpectralLM, FrequencyConvFunc, LMConfig, SampleConfig,
                              causal_spectral_conv, generate)
@@ -60,6 +65,8 @@ __all__ = [
     "sparse_scatter", "fftn", "ifftn", "spectral_normalize", "spectral_activation", "spectral_pool", "FrequencyMatMul",
     "FrequencyTransformerLayer", "ComplexSemanticEmbedding", "frequency_relu", "frequency_layernorm", "frequency_attention",
     "bin_contract", "OptimizedFrequencyOps", "ProductionFrequencyLinear", "ProductionFrequencyOps",
-    "OptimizedSparseSpectralTensor",
+    "OptimizedSparseSpectralTensor", "polar_range", "polar_quantize", "polar_dequantize", "log8_encode", "log8_decode",
+    "log8_encode_complex", "log8_decode_complex", "PolarQuantizer", "ConvolutionTheoremMatMul", "WirtingerAutograd",
+    "FrequencyLinearLayer", "LogarithmicQuantizer", "frequency_linear", "frequency_conv1d", "FFTConverter",
 ]
 __version__ = "0.2.0"

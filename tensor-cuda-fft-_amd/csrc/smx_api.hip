@@ -2514,4 +2514,101 @@ int smx_bin_contract_backward(const void* x, const void* w, const void* gy, void
   return SMX_OK;
 }
 
+// ---- the polar and log8 codecs (smx_quant.hip) ----------------------------------------------------------------------------------
+// 0: run it, 1: zero-sized (success, nothing to enqueue), negative: refused
+static int quant_check(long long n, int max_workgroups) {
+  if (n < 0) return fail(SMX_ERR_INVALID, "n must not be negative, got %lld", n);
+  if (int rc = wg_check(max_workgroups)) return rc;
+  return n == 0 ? 1 : 0;
+}
+static int quant_bits(int mag_bits, int phase_bits) {
+  if (mag_bits < 1 || mag_bits > 8 || phase_bits < 1 || phase_bits > 8)
+    return fail(SMX_ERR_INVALID, "mag_bits and phase_bits must be in 1..8, got %d and %d", mag_bits, phase_bits);
+  return SMX_OK;
+}
+static int quant_unit(const void* launcher) {
+  if (!launcher) return fail(SMX_ERR_UNSUPPORTED, "this build holds no smx_quant unit");
+  return SMX_OK;
+}
+int smx_polar_range_workspace_bytes(long long n, size_t* out) {
+  if (!out) return fail(SMX_ERR_INVALID, "out is NULL");
+  if (n < 0) return fail(SMX_ERR_INVALID, "n must not be negative, got %lld", n);
+  if (int rc = quant_unit((const void*)&quant_range_part_bytes)) return rc;
+  *out = n == 0 ? 0 : quant_range_part_bytes();
+  return SMX_OK;
+}
+int smx_polar_range(const void* z, long long n, void* out2, void* workspace, size_t workspace_bytes, int max_workgroups,
+                    void* stream) {
+  const int rc = quant_check(n, max_workgroups);
+  if (rc) return rc < 0 ? rc : SMX_OK;
+  if (!z || !out2) return fail(SMX_ERR_INVALID, "z and out2 must be non-NULL");
+  if (((uintptr_t)z & 7) || ((uintptr_t)out2 & 3)) return fail(SMX_ERR_INVALID, "z must be 8-byte, out2 4-byte aligned");
+  if (int r = quant_unit((const void*)&launch_polar_range)) return r;
+  if (need_ws(workspace, workspace_bytes, quant_range_part_bytes(), "smx_polar_range_workspace_bytes")) return SMX_ERR_INVALID;
+  HIP_TRY(launch_polar_range((const float2*)z, n, (float*)out2, (float2*)workspace, max_workgroups, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_polar_quantize(const void* z, void* mag_q, void* phase_q, long long n, int mag_bits, int phase_bits, float mag_min,
+                       float mag_max, int max_workgroups, void* stream) {
+  if (int r = quant_bits(mag_bits, phase_bits)) return r;
+  const int rc = quant_check(n, max_workgroups);
+  if (rc) return rc < 0 ? rc : SMX_OK;
+  if (!z || !mag_q || !phase_q) return fail(SMX_ERR_INVALID, "z, mag_q and phase_q must be non-NULL");
+  if ((uintptr_t)z & 7) return fail(SMX_ERR_INVALID, "z must be 8-byte aligned");
+  if (int r = quant_unit((const void*)&launch_polar_quantize)) return r;
+  HIP_TRY(launch_polar_quantize((const float2*)z, (unsigned char*)mag_q, (unsigned char*)phase_q, n, mag_bits, phase_bits,
+                                mag_min, mag_max, max_workgroups, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_polar_dequantize(const void* mag_q, const void* phase_q, void* z, long long n, int mag_bits, int phase_bits,
+                         float mag_min, float mag_max, int max_workgroups, void* stream) {
+  if (int r = quant_bits(mag_bits, phase_bits)) return r;
+  const int rc = quant_check(n, max_workgroups);
+  if (rc) return rc < 0 ? rc : SMX_OK;
+  if (!z || !mag_q || !phase_q) return fail(SMX_ERR_INVALID, "mag_q, phase_q and z must be non-NULL");
+  if ((uintptr_t)z & 7) return fail(SMX_ERR_INVALID, "z must be 8-byte aligned");
+  if (int r = quant_unit((const void*)&launch_polar_dequantize)) return r;
+  HIP_TRY(launch_polar_dequantize((const unsigned char*)mag_q, (const unsigned char*)phase_q, (float2*)z, n, mag_bits,
+                                  phase_bits, mag_min, mag_max, max_workgroups, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_log8_encode(const void* x, void* out, long long n, int max_workgroups, void* stream) {
+  const int rc = quant_check(n, max_workgroups);
+  if (rc) return rc < 0 ? rc : SMX_OK;
+  if (!x || !out) return fail(SMX_ERR_INVALID, "x and out must be non-NULL");
+  if ((uintptr_t)x & 3) return fail(SMX_ERR_INVALID, "x must be 4-byte aligned");
+  if (int r = quant_unit((const void*)&launch_log8_encode)) return r;
+  HIP_TRY(launch_log8_encode((const float*)x, (unsigned char*)out, n, max_workgroups, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_log8_decode(const void* e, void* x, long long n, int max_workgroups, void* stream) {
+  const int rc = quant_check(n, max_workgroups);
+  if (rc) return rc < 0 ? rc : SMX_OK;
+  if (!e || !x) return fail(SMX_ERR_INVALID, "e and x must be non-NULL");
+  if ((uintptr_t)x & 3) return fail(SMX_ERR_INVALID, "x must be 4-byte aligned");
+  if (int r = quant_unit((const void*)&launch_log8_decode)) return r;
+  HIP_TRY(launch_log8_decode((const unsigned char*)e, (float*)x, n, max_workgroups, (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_log8_encode_c64(const void* z, void* re_q, void* im_q, long long n, int max_workgroups, void* stream) {
+  const int rc = quant_check(n, max_workgroups);
+  if (rc) return rc < 0 ? rc : SMX_OK;
+  if (!z || !re_q || !im_q) return fail(SMX_ERR_INVALID, "z, re_q and im_q must be non-NULL");
+  if ((uintptr_t)z & 7) return fail(SMX_ERR_INVALID, "z must be 8-byte aligned");
+  if (int r = quant_unit((const void*)&launch_log8_encode_c64)) return r;
+  HIP_TRY(launch_log8_encode_c64((const float2*)z, (unsigned char*)re_q, (unsigned char*)im_q, n, max_workgroups,
+                                 (hipStream_t)stream));
+  return SMX_OK;
+}
+int smx_log8_decode_c64(const void* re_q, const void* im_q, void* z, long long n, int max_workgroups, void* stream) {
+  const int rc = quant_check(n, max_workgroups);
+  if (rc) return rc < 0 ? rc : SMX_OK;
+  if (!z || !re_q || !im_q) return fail(SMX_ERR_INVALID, "re_q, im_q and z must be non-NULL");
+  if ((uintptr_t)z & 7) return fail(SMX_ERR_INVALID, "z must be 8-byte aligned");
+  if (int r = quant_unit((const void*)&launch_log8_decode_c64)) return r;
+  HIP_TRY(launch_log8_decode_c64((const unsigned char*)re_q, (const unsigned char*)im_q, (float2*)z, n, max_workgroups,
+                                 (hipStream_t)stream));
+  return SMX_OK;
+}
+
 }  // extern "C"

@@ -499,4 +499,26 @@ __attribute__((weak)) hipError_t launch_bin_contract_bwd(const float2* x, const 
                                                          float2* gw, int B, long long P, int Ci, int Co, int max_workgroups,
                                                          hipStream_t s);
 
+// ---- the polar and log8 codecs of the compressed spectra (smx_quant.hip) -----------------------------------------------------
+// z complex64 (8-byte aligned), x fp32, the code planes uint8 at any byte address; n > 0.  WEAK references like the ones
+// above, for the same reason.
+__attribute__((weak)) size_t quant_range_part_bytes();
+// out2 = (min, max) over the elements of log2(max(|z|, 1e-9)); part: quant_range_part_bytes().  Two launches.
+__attribute__((weak)) hipError_t launch_polar_range(const float2* z, long long n, float* out2, float2* part,
+                                                    int max_workgroups, hipStream_t s);
+__attribute__((weak)) hipError_t launch_polar_quantize(const float2* z, unsigned char* mag_q, unsigned char* phase_q,
+                                                       long long n, int mag_bits, int phase_bits, float mag_min,
+                                                       float mag_max, int max_workgroups, hipStream_t s);
+__attribute__((weak)) hipError_t launch_polar_dequantize(const unsigned char* mag_q, const unsigned char* phase_q, float2* z,
+                                                         long long n, int mag_bits, int phase_bits, float mag_min,
+                                                         float mag_max, int max_workgroups, hipStream_t s);
+__attribute__((weak)) hipError_t launch_log8_encode(const float* x, unsigned char* e, long long n, int max_workgroups,
+                                                    hipStream_t s);
+__attribute__((weak)) hipError_t launch_log8_decode(const unsigned char* e, float* x, long long n, int max_workgroups,
+                                                    hipStream_t s);
+__attribute__((weak)) hipError_t launch_log8_encode_c64(const float2* z, unsigned char* re_q, unsigned char* im_q, long long n,
+                                                        int max_workgroups, hipStream_t s);
+__attribute__((weak)) hipError_t launch_log8_decode_c64(const unsigned char* re_q, const unsigned char* im_q, float2* z,
+                                                        long long n, int max_workgroups, hipStream_t s);
+
 }  // namespace smx

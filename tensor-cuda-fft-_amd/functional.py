@@ -2621,3 +2621,197 @@ def bin_contract(x: torch.Tensor, w: torch.Tensor, *, max_workgroups: int = 0) -
     if not native:
         return torch.einsum("bpi,pio->bpo", x, w)
     return _BinContract.apply(_dense(x), _dense(w), int(max_workgroups))
+
+
+# ---- the polar and log8 codecs of the compressed spectra (csrc/smx_quant.hip) ---------------------------------------------------
+
+def _codec_native(*ts, bits=()) -> bool:
+    """tensors on one ROCm device that autograd does not follow, bit counts the one-byte planes hold"""
+    t0 = ts[0]
+    if not (t0.is_cuda and all(t.device == t0.device for t in ts) and all(1 <= int(b) <= 8 for b in bits)):
+        return False
+    return not (torch.is_grad_enabled() and any(t.requires_grad for t in ts))
+
+
+def _flat(t: torch.Tensor) -> torch.Tensor:
+    """Contiguous, in place where it already is: the codecs take a complex64 tensor at any 8-byte address, an fp32 one at
+    any 4-byte address and a byte plane at any address, so a view such as z[1:] or mag_q[3:] is not copied (_dense would)."""
+    if t.is_complex():
+        t = t.resolve_conj()
+    return t.contiguous()
+
+
+def _check_wg(name: str, max_workgroups: int) -> int:
+    if max_workgroups < 0:
+        raise ValueError(f"{name}: max_workgroups must not be negative, got {max_workgroups}")
+    return int(max_workgroups)
+
+
+def _check_planes(name: str, a: torch.Tensor, b: torch.Tensor) -> None:
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
+        raise TypeError(f"{name}: the code planes must be tensors")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"{name}: the code planes differ: {tuple(a.shape)} on {a.device}, {tuple(b.shape)} on {b.device}")
+
+
+@functools.lru_cache(64)
+def _polar_range_ws_bytes(n: int) -> int:
+    return _query("smx_polar_range_workspace_bytes", n)
+
+
+def polar_range(z: torch.Tensor, *, max_workgroups: int = 0) -> torch.Tensor:
+    """(2,) float32 on z's device: the minimum and maximum over the elements of log2(max(|z|, 1e-9)), the adaptive range
+    of the reference's PolarQuantizer.quantize (fft_tensor/polar_quantization.py:29-32: abs, clamp, log2, min, max and two
+    host reads).  No host read happens here; the caller makes one (`.tolist()`).
+    complex64 on a ROCm device: smx_polar_range, two launches over re^2 + im^2 (log2 is monotone, so it is applied to the
+    two ends only); a NaN element does not enter.  Everything else runs the reference's ops.  Not differentiable."""
+    if not isinstance(z, torch.Tensor):
+        raise TypeError("polar_range: z must be a tensor")
+    if z.numel() == 0:
+        raise ValueError("polar_range: z is empty")
+    mwg = _check_wg("polar_range", max_workgroups)
+    if not (z.dtype == torch.complex64 and _codec_native(z)):
+        log_mag = torch.log2(torch.abs(z).clamp(min=1e-9))
+        return torch.stack((log_mag.min(), log_mag.max())).detach()
+    dev, zc = z.device, _flat(z)
+    out2 = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = _workspace(dev, _polar_range_ws_bytes(zc.numel()))
+    _call(dev, "smx_polar_range", zc.data_ptr(), zc.numel(), out2.data_ptr(), *_ws_arg(ws), mwg, _stream(dev))
+    return out2
+
+
+def polar_quantize(z: torch.Tensor, mag_bits: int, phase_bits: int, mag_range, *, max_workgroups: int = 0):
+    """(mag_q, phase_q), two uint8 tensors of z's shape: PolarQuantizer.quantize for a given range (mag_min, mag_max) of
+    Python floats (fft_tensor/polar_quantization.py:25-42).  With Lm = 2**mag_bits - 1 and Lp = 2**phase_bits - 1:
+        mag_q   = clamp(round((log2(max(|z|, 1e-9)) - mag_min) / (mag_max - mag_min + 1e-9) * Lm), 0, Lm)
+        phase_q = clamp(round((angle(z) + pi) / (2 pi) * Lp), 0, Lp)            (round: half to even)
+    complex64 on a ROCm device with both bit counts in 1..8: smx_polar_quantize, ONE launch that reads 8 bytes and writes 2
+    per element (the reference: about fifteen whole-tensor passes); a code can differ from the reference's by one where
+    the value before rounding lies within about 1e-5 of a rounding boundary (the device's log2 and atan2 differ from the
+    host's in the last bits).  Everything else -- CPU tensors, other dtypes, inputs that require grad, bit counts above 8,
+    whose codes wrap in the uint8 cast exactly as the reference's do -- runs the reference's op sequence.  Not
+    differentiable."""
+    if not isinstance(z, torch.Tensor):
+        raise TypeError("polar_quantize: z must be a tensor")
+    mag_min, mag_max = (float(v) for v in mag_range)
+    mwg = _check_wg("polar_quantize", max_workgroups)
+    mag_levels, phase_levels = 2 ** mag_bits, 2 ** phase_bits
+    if not (z.dtype == torch.complex64 and z.numel() > 0 and _codec_native(z, bits=(mag_bits, phase_bits))):
+        mag = torch.abs(z)
+        phase = torch.angle(z)
+        log_mag = torch.log2(mag.clamp(min=1e-9))
+        mag_norm = (log_mag - mag_min) / (mag_max - mag_min + 1e-9)
+        mag_q = (mag_norm * (mag_levels - 1)).round().clamp(0, mag_levels - 1).to(torch.uint8)
+        phase_norm = (phase + math.pi) / (2 * math.pi)
+        phase_q = (phase_norm * (phase_levels - 1)).round().clamp(0, phase_levels - 1).to(torch.uint8)
+        return mag_q, phase_q
+    dev, zc = z.device, _flat(z)
+    mag_q = torch.empty(z.shape, dtype=torch.uint8, device=dev)
+    phase_q = torch.empty(z.shape, dtype=torch.uint8, device=dev)
+    _call(dev, "smx_polar_quantize", zc.data_ptr(), mag_q.data_ptr(), phase_q.data_ptr(), zc.numel(), int(mag_bits),
+          int(phase_bits), mag_min, mag_max, mwg, _stream(dev))
+    return mag_q, phase_q
+
+
+def polar_dequantize(mag_q: torch.Tensor, phase_q: torch.Tensor, mag_bits: int, phase_bits: int, mag_range, *,
+                     max_workgroups: int = 0) -> torch.Tensor:
+    """complex64 of the planes' shape: PolarQuantizer.dequantize (fft_tensor/polar_quantization.py:44-56),
+        2 ** (mag_q / Lm * (mag_max - mag_min) + mag_min) * exp(i (phase_q / Lp * 2 pi - pi)).
+    uint8 planes on a ROCm device with both bit counts in 1..8: smx_polar_dequantize, one launch whose workgroups build the
+    256 magnitudes and 256 unit vectors in LDS and then stream 2 bytes in, 8 out, without a transcendental (the reference:
+    pow, polar and eight arithmetic passes).  Everything else runs the reference's ops."""
+    _check_planes("polar_dequantize", mag_q, phase_q)
+    mag_min, mag_max = (float(v) for v in mag_range)
+    mwg = _check_wg("polar_dequantize", max_workgroups)
+    mag_levels, phase_levels = 2 ** mag_bits, 2 ** phase_bits
+    if not (mag_q.dtype == torch.uint8 and phase_q.dtype == torch.uint8 and mag_q.numel() > 0
+            and _codec_native(mag_q, phase_q, bits=(mag_bits, phase_bits))):
+        mag_norm = mag_q.float() / (mag_levels - 1)
+        log_mag = mag_norm * (mag_max - mag_min) + mag_min
+        mag = 2.0 ** log_mag
+        phase_norm = phase_q.float() / (phase_levels - 1)
+        phase = phase_norm * 2 * math.pi - math.pi
+        return torch.polar(mag, phase)
+    dev, mq, pq = mag_q.device, _flat(mag_q), _flat(phase_q)
+    z = torch.empty(mag_q.shape, dtype=torch.complex64, device=dev)
+    _call(dev, "smx_polar_dequantize", mq.data_ptr(), pq.data_ptr(), z.data_ptr(), mq.numel(), int(mag_bits),
+          int(phase_bits), mag_min, mag_max, mwg, _stream(dev))
+    return z
+
+
+def _log8_encode_torch(x: torch.Tensor) -> torch.Tensor:
+    """LogarithmicQuantizer.log8_encode, the reference's op sequence (fft_tensor/zero_materialize.py:482-497)"""
+    sign = (x >= 0).to(torch.uint8)
+    magnitude = torch.abs(x)
+    log_mag = torch.log2(magnitude + 1e-8)
+    quantized = ((log_mag + 8) / 16 * 127).clamp(0, 127).to(torch.uint8)
+    return (sign << 7) | quantized
+
+
+def _log8_decode_torch(encoded: torch.Tensor) -> torch.Tensor:
+    """LogarithmicQuantizer.log8_decode, the reference's op sequence (fft_tensor/zero_materialize.py:510-521)"""
+    sign = ((encoded >> 7) & 1).to(torch.float32) * 2 - 1
+    quantized = (encoded & 0x7F).to(torch.float32)
+    log_mag = (quantized / 127) * 16 - 8
+    magnitude = torch.pow(2.0, log_mag)
+    return sign * magnitude
+
+
+def log8_encode(x: torch.Tensor, *, max_workgroups: int = 0) -> torch.Tensor:
+    """uint8 of x's shape, LogarithmicQuantizer.log8_encode:
+        (x >= 0) << 7 | trunc(clamp((log2(|x| + 1e-8) + 8) / 16 * 127, 0, 127))     (so +0.0 and -0.0 both carry bit 7).
+    fp32 on a ROCm device: smx_log8_encode, one launch (4 bytes in, 1 out per element; the reference: nine passes); a code
+    can differ from the reference's by one where the value before truncation lies within about 1e-5 of an integer.
+    Everything else runs the reference's ops.  Not differentiable."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("log8_encode: x must be a tensor")
+    mwg = _check_wg("log8_encode", max_workgroups)
+    if not (x.dtype == torch.float32 and x.numel() > 0 and _codec_native(x)):
+        return _log8_encode_torch(x)
+    dev, xc = x.device, _flat(x)
+    out = torch.empty(x.shape, dtype=torch.uint8, device=dev)
+    _call(dev, "smx_log8_encode", xc.data_ptr(), out.data_ptr(), xc.numel(), mwg, _stream(dev))
+    return out
+
+
+def log8_decode(encoded: torch.Tensor, *, max_workgroups: int = 0) -> torch.Tensor:
+    """float32 of the codes' shape, LogarithmicQuantizer.log8_decode: (bit 7 ? +1 : -1) * 2 ** ((e & 127) / 127 * 16 - 8).
+    uint8 on a ROCm device: smx_log8_decode, one launch that looks the 256 possible values up in an LDS table.  Everything
+    else runs the reference's ops."""
+    if not isinstance(encoded, torch.Tensor):
+        raise TypeError("log8_decode: encoded must be a tensor")
+    mwg = _check_wg("log8_decode", max_workgroups)
+    if not (encoded.dtype == torch.uint8 and encoded.numel() > 0 and _codec_native(encoded)):
+        return _log8_decode_torch(encoded)
+    dev, ec = encoded.device, _flat(encoded)
+    x = torch.empty(encoded.shape, dtype=torch.float32, device=dev)
+    _call(dev, "smx_log8_decode", ec.data_ptr(), x.data_ptr(), ec.numel(), mwg, _stream(dev))
+    return x
+
+
+def log8_encode_complex(z: torch.Tensor, *, max_workgroups: int = 0):
+    """(re_q, im_q): log8_encode of the real and of the imaginary part (LogarithmicQuantizer.compress_sparse_freq, which
+    runs two strided chains).  complex64 on a ROCm device: smx_log8_encode_c64, ONE pass over the interleaved data."""
+    if not (isinstance(z, torch.Tensor) and z.is_complex()):
+        raise TypeError("log8_encode_complex: z must be a complex tensor")
+    mwg = _check_wg("log8_encode_complex", max_workgroups)
+    if not (z.dtype == torch.complex64 and z.numel() > 0 and _codec_native(z)):
+        return _log8_encode_torch(z.real), _log8_encode_torch(z.imag)
+    dev, zc = z.device, _flat(z)
+    re_q = torch.empty(z.shape, dtype=torch.uint8, device=dev)
+    im_q = torch.empty(z.shape, dtype=torch.uint8, device=dev)
+    _call(dev, "smx_log8_encode_c64", zc.data_ptr(), re_q.data_ptr(), im_q.data_ptr(), zc.numel(), mwg, _stream(dev))
+    return re_q, im_q
+
+
+def log8_decode_complex(re_q: torch.Tensor, im_q: torch.Tensor, *, max_workgroups: int = 0) -> torch.Tensor:
+    """complex64: log8_decode(re_q) + i log8_decode(im_q).  uint8 planes on a ROCm device: smx_log8_decode_c64, one launch
+    that writes the interleaved tensor directly."""
+    _check_planes("log8_decode_complex", re_q, im_q)
+    mwg = _check_wg("log8_decode_complex", max_workgroups)
+    if not (re_q.dtype == torch.uint8 and im_q.dtype == torch.uint8 and re_q.numel() > 0 and _codec_native(re_q, im_q)):
+        return torch.complex(_log8_decode_torch(re_q), _log8_decode_torch(im_q))
+    dev, rc, ic = re_q.device, _flat(re_q), _flat(im_q)
+    z = torch.empty(re_q.shape, dtype=torch.complex64, device=dev)
+    _call(dev, "smx_log8_decode_c64", rc.data_ptr(), ic.data_ptr(), z.data_ptr(), rc.numel(), mwg, _stream(dev))
+    return z
