@@ -857,5 +857,6 @@ int smx_sparse_scatter(const void* coeffs, const long long* flat_idx, long long 
 #include "smx_freq.h"
 #include "smx_fconv.h"
 #include "smx_quant.h"
+#include "smx_rowfft.h"
 
 #endif /* SMX_H_ */

@@ -11,7 +11,8 @@ from .functional import (DropoutState, hermitian_scale, irfft, pruned_rfft, rfft
                          spectral_block_mix, spectral_filter, spectral_mix, ema_scan, ema_scan_tokens, narrow_head,
                          word_targets, cross_entropy, sample_bytes, byte_features, find_snippets, sparsify_topk,
                          sparse_scatter, fftn, ifftn, frequency_attention, bin_contract, polar_range, polar_quantize,
-                         polar_dequantize, log8_encode, log8_decode, log8_encode_complex, log8_decode_complex)
+                         polar_dequantize, log8_encode, log8_decode, log8_encode_complex, log8_decode_complex,
+                         rowfft_supported, row_fft_raw, row_fft, row_ifft)
 from .spectral_enhancements import (CausalFrequencyMask, EnhancedSpectralBlock, GatedSpectralUnit,
                                     MultiScaleSpectralFeatures, PhaseAwareSpectralMixing, RotaryFrequencyEmbedding)
 from .complex_rope import ComplexRoPE, ComplexRoPESpectralLayer, GatedLinearUnit
@@ -68,5 +69,6 @@ __all__ = [
     "OptimizedSparseSpectralTensor", "polar_range", "polar_quantize", "polar_dequantize", "log8_encode", "log8_decode",
     "log8_encode_complex", "log8_decode_complex", "PolarQuantizer", "ConvolutionTheoremMatMul", "WirtingerAutograd",
     "FrequencyLinearLayer", "LogarithmicQuantizer", "frequency_linear", "frequency_conv1d", "FFTConverter",
+    "rowfft_supported", "row_fft_raw", "row_fft", "row_ifft",
 ]
 __version__ = "0.2.0"

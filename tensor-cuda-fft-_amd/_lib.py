@@ -17,8 +17,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "smx.h")      # th
 # signatures was recorded (tests/golden/abi_signatures.txt); theirs is tests/golden/abi_signatures_ext.txt
 EXT_HEADERS = ("smx_freq.h",)
 # headers added after THAT table was recorded: one table per header ({header: prototypes}, _SIGS_MORE), each recorded in a
-# file of its own (smx_fconv.h: tests/golden/abi_signatures_fconv.txt, smx_quant.h: tests/golden/abi_signatures_quant.txt)
-MORE_HEADERS = ("smx_fconv.h", "smx_quant.h")
+# file of its own (smx_fconv.h: tests/golden/abi_signatures_fconv.txt, smx_quant.h: tests/golden/abi_signatures_quant.txt,
+# smx_rowfft.h: tests/golden/abi_signatures_rowfft.txt)
+MORE_HEADERS = ("smx_fconv.h", "smx_quant.h", "smx_rowfft.h")
 
 
 class SmxError(RuntimeError):

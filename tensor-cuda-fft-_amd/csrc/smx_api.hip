@@ -2611,4 +2611,22 @@ int smx_log8_decode_c64(const void* re_q, const void* im_q, void* z, long long n
   return SMX_OK;
 }
 
+// ---- the DFT along the contiguous last axis (smx_rowfft.hip) ------------------------------------------------------------------
+int smx_rowfft_supported(int n) { return rowfft_supported(n) ? 1 : 0; }
+int smx_rowfft(const void* in, void* out, long long rows, int n, int flags, float scale, int max_workgroups, void* stream) {
+  if (rows < 0) return fail(SMX_ERR_INVALID, "rows must not be negative, got %lld", rows);
+  if (int rc = wg_check(max_workgroups)) return rc;
+  if (flags & ~(SMX_ROWFFT_CONJ_IN | SMX_ROWFFT_CONJ_OUT | SMX_ROWFFT_REAL_IN | SMX_ROWFFT_REAL_OUT))
+    return fail(SMX_ERR_INVALID, "unknown flag bits in %d (SMX_ROWFFT_*)", flags);
+  if (!std::isfinite(scale)) return fail(SMX_ERR_INVALID, "scale must be finite");
+  if (!rowfft_supported(n))
+    return fail(SMX_ERR_UNSUPPORTED, "n must be a power of two from 2 to %d (smx_rowfft_supported), got %d", SMX_ROWFFT_MAX_N, n);
+  if (rows == 0) return SMX_OK;
+  if (!in || !out) return fail(SMX_ERR_INVALID, "in and out must be non-NULL");
+  if (((uintptr_t)in & 15) || ((uintptr_t)out & 15)) return fail(SMX_ERR_INVALID, "in and out must be 16-byte aligned");
+  if (!(const void*)&launch_rowfft) return fail(SMX_ERR_UNSUPPORTED, "this build holds no smx_rowfft unit");
+  HIP_TRY(launch_rowfft(in, out, rows, n, flags, scale, max_workgroups, (hipStream_t)stream));
+  return SMX_OK;
+}
+
 }  // extern "C"

@@ -521,4 +521,12 @@ __attribute__((weak)) hipError_t launch_log8_encode_c64(const float2* z, unsigne
 __attribute__((weak)) hipError_t launch_log8_decode_c64(const unsigned char* re_q, const unsigned char* im_q, float2* z,
                                                         long long n, int max_workgroups, hipStream_t s);
 
+// ---- the DFT along the contiguous last axis of dense rows (smx_rowfft.hip) ---------------------------------------------------
+// n: a power of two from 2 to 4096 (SMX_ROWFFT_MAX_N)
+inline bool rowfft_supported(int n) { return n >= 2 && n <= 4096 && (n & (n - 1)) == 0; }
+// in / out: (rows, n) complex64, or fp32 on the side that flags (SMX_ROWFFT_*) marks real; 16-byte aligned; rows > 0.  One
+// launch.  A WEAK reference like the ones above, for the same reason.
+__attribute__((weak)) hipError_t launch_rowfft(const void* in, void* out, long long rows, int n, int flags, float scale,
+                                               int max_workgroups, hipStream_t s);
+
 }  // namespace smx

@@ -16,9 +16,13 @@ from .sparse_tensor import SparseSpectralTensor
 
 def ifft_last_real(w_freq: torch.Tensor) -> torch.Tensor:
     """torch.fft.ifft(w_freq, dim=-1).real of a 2-D weight.  On a ROCm device the inverse transform of a complex64 weight
-    that does not require grad is the package's own sequence transform, ifft(w) = conj(fft(conj w)) / n as
-    functional.ifftn does it; CPU tensors (and every other weight) use torch.fft."""
+    that does not require grad is ONE launch of the native row transform where functional.rowfft_supported(n):
+    conjugated on the way in, scaled by 1 / n, the real part alone written (Re(ifft w) = Re(F conj w) / n).  Other
+    lengths run the package's sequence transform, ifft(w) = conj(fft(conj w)) / n as functional.ifftn does it; CPU
+    tensors (and every other weight) use torch.fft."""
     if w_freq.is_cuda and w_freq.dtype == torch.complex64 and not w_freq.requires_grad and w_freq.numel() > 0:
+        if _fn._row_native(w_freq):
+            return _fn.row_fft_raw(w_freq, conj_in=True, real_out=True, scale=1.0 / w_freq.shape[-1])
         spec = _fn.seq_fft_raw(w_freq.conj().resolve_conj().unsqueeze(-1)).squeeze(-1)
         return spec.real / w_freq.shape[-1]              # Re(conj(s) / n) = Re(s) / n
     return torch.fft.ifft(w_freq, dim=-1).real

@@ -2411,18 +2411,24 @@ def sparse_scatter(coeffs: torch.Tensor, flat_indices: torch.Tensor, shape, *, a
     return out.reshape(shape)
 
 
+def _walk_axes(z: torch.Tensor, fft1d, naxes: int) -> torch.Tensor:
+    """1-D transforms along the first `naxes` axes of the contiguous `z`, each as the middle axis of a (B, N, D) view"""
+    shape = tuple(z.shape)
+    out = z
+    for i, n in enumerate(shape[:naxes]):
+        if n > 1:
+            out = fft1d(out.reshape(math.prod(shape[:i]), n, math.prod(shape[i + 1:]))).contiguous()
+    return out.reshape(shape)
+
+
 def _axis_walk(z: torch.Tensor, fft1d) -> torch.Tensor:
     """The N-D DFT of `z` as 1-D transforms along each axis in turn.  Axis i of a contiguous tensor is the middle axis
     of the view (prod(shape[:i]), shape[i], prod(shape[i+1:])), so nothing is transposed; `fft1d` maps a contiguous
     (B, N, D) complex tensor to its DFT along dim 1.  Axes of length 1 are skipped."""
-    shape = tuple(z.shape)
-    out = z.contiguous()
-    for i, n in enumerate(shape):
-        if n > 1:
-            out = fft1d(out.reshape(math.prod(shape[:i]), n, math.prod(shape[i + 1:]))).contiguous()
+    out = _walk_axes(z.contiguous(), fft1d, z.dim())
     if out.data_ptr() == z.data_ptr():                   # no axis longer than 1: the transform is the identity
         out = out.clone()
-    return out.reshape(shape)
+    return out
 
 
 def _check_c64(name: str, z) -> None:
@@ -2430,25 +2436,152 @@ def _check_c64(name: str, z) -> None:
         raise TypeError(f"{name}: z must be a complex64 tensor")
 
 
+# ---- the DFT along the contiguous last axis (csrc/smx_rowfft.hip) and the N-D transforms on it -----------------------------------
+
+ROWFFT_MAX_N = _lib.SMX_ROWFFT_MAX_N
+
+
+@functools.lru_cache(None)
+def rowfft_supported(n: int) -> bool:
+    """True where smx_rowfft transforms rows of n points: n a power of two from 2 to 4096"""
+    return bool(_lib.lib().smx_rowfft_supported(int(n)))
+
+
+def row_fft_raw(x: torch.Tensor, *, conj_in: bool = False, conj_out: bool = False, real_out: bool = False,
+                scale: float = 1.0, out: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> torch.Tensor:
+    """One launch of smx_rowfft over the last axis of `x` (any tensor with at least one dimension, on a ROCm device):
+        out[..., k] = scale * sum_j a[..., j] exp(-2 pi i j k / n),   a = x, or conj(x) with conj_in,
+    conjugated with conj_out, its real part alone (float32) with real_out.  complex64 input gives the complex transform;
+    float32 input is taken as (x, 0) without a complex copy of it (SMX_ROWFFT_REAL_IN).  `out`: a dense 16-byte aligned
+    tensor of x's shape and the result's dtype to write into; it may be `x` itself when both have the same dtype.
+    n must satisfy rowfft_supported (SmxError otherwise).  Not differentiable: row_fft / row_ifft are."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dtype not in (torch.complex64, torch.float32):
+        raise TypeError(f"x must be complex64 or float32, got {x.dtype}")
+    if x.dim() < 1:
+        raise ValueError("row_fft_raw: x must have at least one dimension")
+    mwg = _check_wg("row_fft_raw", max_workgroups)
+    _require("x", x, None, _ANY_PATH)
+    dev, n = x.device, int(x.shape[-1])
+    xd = _dense(x)
+    odt = torch.float32 if real_out else torch.complex64
+    if out is None:
+        out = torch.empty(x.shape, dtype=odt, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == odt and out.shape == x.shape
+              and out.is_contiguous() and out.data_ptr() % 16 == 0 and not (out.is_complex() and out.is_conj())):
+        raise ValueError(f"row_fft_raw: out must be a dense, 16-byte aligned {odt} tensor of shape {tuple(x.shape)} on {dev}")
+    flags = (_lib.SMX_ROWFFT_CONJ_IN if conj_in else 0) | (_lib.SMX_ROWFFT_CONJ_OUT if conj_out else 0) \
+        | (_lib.SMX_ROWFFT_REAL_IN if x.dtype == torch.float32 else 0) | (_lib.SMX_ROWFFT_REAL_OUT if real_out else 0)
+    rows = xd.numel() // n if n else 0
+    _call(dev, "smx_rowfft", xd.data_ptr(), out.data_ptr(), rows, n, flags, float(scale), mwg, _stream(dev))
+    return out
+
+
+class _RowFFT(torch.autograd.Function):
+    """Y = scale * F a along the last axis, a = z or conj(z), conjugated on the way out or not: fft (inverse False:
+    flags 0, scale 1) and ifft (inverse True: both conjugations, scale 1 / n, as ifft z = conj(F conj z) / n).
+    Backward, in torch's convention grad_z = A^H grad_Y for Y = A z: F is symmetric, so for fft A^H = conj(F) and
+    grad_z = conj(F conj(g)) -- both conjugations, scale 1; for ifft A = conj(F) / n, A^H = F / n and grad_z = F g / n --
+    no flag, scale 1 / n.  Either is one launch of the same kernel."""
+
+    @staticmethod
+    def forward(ctx, z, inverse):
+        ctx.inverse = inverse
+        return row_fft_raw(z, conj_in=inverse, conj_out=inverse, scale=1.0 / z.shape[-1] if inverse else 1.0)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        inv = ctx.inverse
+        return row_fft_raw(_grad_c64(g), conj_in=not inv, conj_out=not inv, scale=1.0 / g.shape[-1] if inv else 1.0), None
+
+
+def _row_native(t: torch.Tensor) -> bool:
+    """the last axis of `t` has a native transform: a ROCm tensor with at least one axis whose last length is supported"""
+    return t.is_cuda and t.dim() >= 1 and rowfft_supported(t.shape[-1])
+
+
+def _seq_rows(z: torch.Tensor) -> torch.Tensor:
+    """the composition the last axis ran as before smx_rowfft, and still does for other lengths: a one-channel batch"""
+    return seq_fft(z.reshape(-1, z.shape[-1], 1)).reshape(z.shape)
+
+
+def row_fft(z: torch.Tensor) -> torch.Tensor:
+    """torch.fft.fft(z, dim=-1) of a complex64 tensor, differentiable.  On a ROCm device with rowfft_supported(n): one
+    launch of smx_rowfft per direction; other lengths there: seq_fft on the one-channel view; CPU tensors: torch.fft."""
+    _check_c64("row_fft", z)
+    if not z.is_cuda or z.dim() < 1 or z.numel() == 0:
+        return torch.fft.fft(z, dim=-1)
+    if not rowfft_supported(z.shape[-1]):
+        return _seq_rows(z)
+    return _RowFFT.apply(z, False)
+
+
+def row_ifft(z: torch.Tensor) -> torch.Tensor:
+    """torch.fft.ifft(z, dim=-1) of a complex64 tensor, differentiable: see row_fft"""
+    _check_c64("row_ifft", z)
+    if not z.is_cuda or z.dim() < 1 or z.numel() == 0:
+        return torch.fft.ifft(z, dim=-1)
+    if not rowfft_supported(z.shape[-1]):
+        return _seq_rows(z.conj()).conj() / z.shape[-1]
+    return _RowFFT.apply(z, True)
+
+
 def fftn(z: torch.Tensor) -> torch.Tensor:
-    """torch.fft.fftn(z) of a complex64 tensor over all its axes.  On a ROCm device it is composed from the native
-    sequence transform (seq_fft) axis by axis on views of the contiguous tensor: no FFT library runs, nothing is
-    transposed.  CPU tensors (and empty ones, and inputs that require grad) use torch.fft.  Not differentiable on the
-    device path."""
+    """torch.fft.fftn(z) of a complex64 tensor over all its axes.  On a ROCm device the last axis is one launch of the
+    native row transform (row_fft_raw) where rowfft_supported(its length), and the other axes -- and the last one at
+    other lengths -- are the native sequence transform (seq_fft) axis by axis on views of the contiguous tensor: no FFT
+    library runs, nothing is transposed.  CPU tensors (and empty ones, and inputs that require grad) use torch.fft.
+    Not differentiable on the device path."""
     _check_c64("fftn", z)
     if not z.is_cuda or z.numel() == 0 or z.requires_grad:
         return torch.fft.fftn(z)
+    if _row_native(z):
+        return _walk_axes(row_fft_raw(z), seq_fft_raw, z.dim() - 1)
     return _axis_walk(z.resolve_conj(), seq_fft_raw)
+
+
+def _ifftn_device(z: torch.Tensor, real_out: bool) -> torch.Tensor:
+    """conj(fftn(conj z)) / numel with the last axis last: its launch conjugates and scales on the way out (and keeps the
+    real part alone with real_out); a tensor whose other axes all have length 1 is conjugated on the way in as well"""
+    if z.dim() == 1 or math.prod(z.shape[:-1]) == 1:
+        return row_fft_raw(z, conj_in=True, conj_out=True, real_out=real_out, scale=1.0 / z.numel())
+    lead = _walk_axes(z.conj().resolve_conj().contiguous(), seq_fft_raw, z.dim() - 1)
+    return row_fft_raw(lead, conj_out=True, real_out=real_out, scale=1.0 / z.numel())
 
 
 def ifftn(z: torch.Tensor) -> torch.Tensor:
     """torch.fft.ifftn(z) of a complex64 tensor over all its axes: conj(fftn(conj z)) / numel on a ROCm device (see
-    fftn), torch.fft elsewhere.  Not differentiable on the device path."""
+    fftn; with a native last axis the closing conjugation and division are part of its launch), torch.fft elsewhere.
+    Not differentiable on the device path."""
     _check_c64("ifftn", z)
     if not z.is_cuda or z.numel() == 0 or z.requires_grad:
         return torch.fft.ifftn(z)
+    if _row_native(z):
+        return _ifftn_device(z, False)
     out = _axis_walk(z.conj().resolve_conj(), seq_fft_raw)
     return torch.conj_physical(out).div_(z.numel())
+
+
+def fftn_real(x: torch.Tensor) -> torch.Tensor:
+    """fftn(x.to(complex64)) of a real tensor.  float32 on a ROCm device with a native last axis: that axis runs first and
+    reads the fp32 rows as they are (SMX_ROWFFT_REAL_IN; the axis order of a separable transform is free), so no complex
+    copy of the input is made.  Everything else: fftn of the complex copy."""
+    if not (isinstance(x, torch.Tensor) and x.is_floating_point()):
+        raise TypeError("fftn_real: x must be a real floating-point tensor")
+    if x.dtype == torch.float32 and x.numel() > 0 and not x.requires_grad and _row_native(x):
+        return _walk_axes(row_fft_raw(x), seq_fft_raw, x.dim() - 1)
+    return fftn(x.to(torch.complex64))
+
+
+def ifftn_real(z: torch.Tensor) -> torch.Tensor:
+    """ifftn(z).real as a dense float32 tensor.  On a ROCm device with a native last axis that axis runs last and writes
+    the real part alone (SMX_ROWFFT_REAL_OUT): the complex result is never stored."""
+    _check_c64("ifftn_real", z)
+    if z.is_cuda and z.numel() > 0 and not z.requires_grad and _row_native(z):
+        return _ifftn_device(z, True)
+    return ifftn(z).real
 
 
 # ---- the frequency-domain transformer ops: attention and layernorm (csrc/smx_freq.hip) --------------------------------------

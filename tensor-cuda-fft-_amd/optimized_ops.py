@@ -68,7 +68,7 @@ class OptimizedFrequencyOps:
         everything else by torch.fft.fftn."""
         if spatial_data.is_cuda and spatial_data.dtype in (torch.float32, torch.complex64) and spatial_data.numel() > 0 \
                 and not spatial_data.requires_grad:
-            freq = _fn.fftn(spatial_data.to(torch.complex64))
+            freq = _fn.fftn(spatial_data) if spatial_data.is_complex() else _fn.fftn_real(spatial_data)
         else:
             freq = torch.fft.fftn(spatial_data)
         k = max(1, int(freq.numel() * sparsity))
@@ -86,7 +86,7 @@ class OptimizedFrequencyOps:
         coeffs = sparse_coeffs.to(device=device, dtype=torch.complex64)
         full = _fn.sparse_scatter(coeffs, indices.to(device=coeffs.device, dtype=torch.int64), tuple(output_shape))
         if full.is_cuda and full.numel() > 0 and not full.requires_grad:
-            return _fn.ifftn(full).real
+            return _fn.ifftn_real(full)
         return torch.fft.ifftn(full).real
 
     @staticmethod
@@ -200,8 +200,10 @@ class ProductionFrequencyLinear(torch.nn.Module):
     weight_indices (a reference state_dict loads with strict=True).  The initial draw is made on the CPU exactly as the
     reference makes it, so a seed gives the same layer; the reference's per-row loop that copies the kept bins is one
     gather / scatter.  In eval mode the materialised weight is cached until invalidate_cache(), as in the reference.
-    On a ROCm device the inverse transform of a complex64 weight_freq is the package's differentiable sequence transform
-    (functional.seq_fft), so forward is differentiable in weight_freq without an FFT library."""
+    On a ROCm device the inverse transform of a complex64 weight_freq runs without an FFT library: where a gradient can be
+    asked for (grad enabled and weight_freq requires grad) it is the package's differentiable sequence transform
+    (functional.seq_fft), so forward is differentiable in weight_freq; otherwise (no_grad, a frozen weight) it is
+    frequency_ops.ifft_last_real, one launch of the native row transform where the length has one."""
 
     def __init__(self, in_features: int, out_features: int, sparsity: float = 0.05, bias: bool = True):
         super().__init__()
@@ -226,7 +228,9 @@ class ProductionFrequencyLinear(torch.nn.Module):
         if self._cache_valid and self._weight_cache is not None:
             return self._weight_cache
         wf = self.weight_freq
-        if wf.is_cuda and wf.dtype == torch.complex64 and wf.numel() > 0:
+        if wf.is_cuda and wf.dtype == torch.complex64 and wf.numel() > 0 and not (torch.is_grad_enabled() and wf.requires_grad):
+            weight = ifft_last_real(wf.detach())                  # nothing to differentiate: one native row launch
+        elif wf.is_cuda and wf.dtype == torch.complex64 and wf.numel() > 0:
             weight = _fn.seq_fft(wf.conj().unsqueeze(-1)).squeeze(-1).real / wf.shape[-1]    # Re(conj(s) / n) = Re(s) / n
         else:
             weight = torch.fft.ifft(wf, dim=-1).real

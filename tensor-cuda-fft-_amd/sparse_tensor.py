@@ -70,8 +70,12 @@ class SparseSpectralTensor:
             data = torch.tensor(data)
         self.shape = tuple(data.shape)
         with torch.no_grad():
-            z = data.detach().to(device=self.device, dtype=self.dtype).to(torch.complex64)
-            freq = F.fftn(z) if self.use_cuda else torch.fft.fftn(z)
+            x = data.detach().to(device=self.device, dtype=self.dtype)
+            if self.use_cuda and x.dtype == torch.float32:
+                freq = F.fftn_real(x)                # the last axis reads the fp32 rows: no complex copy of the input
+            else:
+                z = x.to(torch.complex64)
+                freq = F.fftn(z) if self.use_cuda else torch.fft.fftn(z)
             if self.use_cuda:
                 self.freq_coeffs, flat = F.sparsify_topk(freq, self.sparsity)
             else:
@@ -123,8 +127,9 @@ class SparseSpectralTensor:
                 freq = F.sparse_scatter(self.freq_coeffs, self._flat, self.shape, assume_ascending=True)
             else:
                 freq = self._scatter_pytorch()
-            spatial = F.ifftn(freq) if self.use_cuda else torch.fft.ifftn(freq)
-            return spatial.real.to(dtype=self.dtype)
+            if self.use_cuda:
+                return F.ifftn_real(freq).to(dtype=self.dtype)   # the last axis writes the real part alone
+            return torch.fft.ifftn(freq).real.to(dtype=self.dtype)
 
     def _scatter_pytorch(self) -> torch.Tensor:
         freq = torch.zeros(self.shape, dtype=torch.complex64, device=self.device)
